@@ -8,8 +8,14 @@ thermal bubble on a 512^3 RectilinearGrid (SURVEY.md §8d "C2"), Float64, fixed 
 deterministic synthetic initial state resident in HBM before the timed region.
 
     python bench.py --gpus N --steps K --warmup W [--size 512] [--scaling strong|weak] [--workload bubble|config3] [--preflight]
+                    [--full] [--dump-outputs DIR]
 
-Prints ONE JSON line (rank 0).  N > 1: one rank per GPU, y-slab decomposition with the RCCL communicator inside the C library
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps and prints the headline line (with the per-kernel
+table and roofline of the timed steps' own HIP events).  `--full` adds the side measurements that take runs of their own, each
+reported beside the headline under its own key: `moist_variant`, `second_milestone` (compressible step, in a fresh process),
+`float32` and `cpu_baseline`.  `--dump-outputs DIR` writes the model's fields after the last timed step as DIR/<name>.npy
+(Float64; a fixed, seeded sample of each field's interior above 2^19 cells), so that two builds can be compared output for output.
+N > 1: one rank per GPU, y-slab decomposition with the RCCL communicator inside the C library
 (breeze.jl_amd/csrc/bz_comm.hip: y-halo exchange + FFT all-to-all):
   --scaling strong  (default) the size^3 domain of the N = 1 run is split N ways — BASELINE.md §4: "1/2/4/8-GPU cells/s for 512^3"
   --scaling weak    every rank owns a size^3 slab of a size x (size N) x size periodic domain (explicit only)
@@ -81,6 +87,35 @@ def dominant_roofline(kernels, cells, word_bytes, f32=False, with_traffic=True, 
         if traffic is None:
             traffic, src = load_traffic(ROOT, dom, f32, tag=traffic_tag)
     return roofline_block(dom, kernels[dom]["avg_ms"], cells, word_bytes, traffic, src, dry=dry)
+
+
+DUMP_SAMPLE = 1 << 19      # values per field: 12 fields x 4 MiB of Float64 stay within 64 MB
+DUMP_SEED = 20240601
+
+
+def dump_outputs(model, directory):
+    """What a caller of the timed seam receives after its last step (bz_time_steps_anelastic with diagnose_last = 1 leaves every field
+    current): the prognostic densities and the diagnosed fields, written as directory/<name>.npy in the model's float type.  A field whose
+    interior holds at most DUMP_SAMPLE cells is written whole ((z, y, x) shaped); a larger one as the values at DUMP_SAMPLE distinct
+    interior cells drawn with DUMP_SEED (flat (z, y, x) indices in increasing order) — the same cells in every run of the same size."""
+    import torch
+    model.synchronize()
+    fields = {"rho_u": model.momentum["ρu"], "rho_v": model.momentum["ρv"], "rho_w": model.momentum["ρw"],
+              "rho_theta": model.potential_temperature_density, "rho_qt": model.moisture_density,
+              "u": model.velocities["u"], "v": model.velocities["v"], "w": model.velocities["w"],
+              "theta": model.potential_temperature, "qt": model.specific_moisture, "T": model.temperature,
+              "p_anomaly": model.dynamics.pressure_anomaly}
+    os.makedirs(directory, exist_ok=True)
+    picks = {}
+    for name, f in fields.items():
+        t = f.interior
+        nz, ny, nx = t.shape
+        if t.numel() > DUMP_SAMPLE:
+            if t.shape not in picks:
+                flat = np.sort(np.random.default_rng(DUMP_SEED).choice(t.numel(), DUMP_SAMPLE, replace=False))
+                picks[t.shape] = tuple(torch.from_numpy(a).to(t.device) for a in (flat // (ny * nx), flat // nx % ny, flat % nx))
+            t = t[picks[t.shape]]
+        np.save(os.path.join(directory, name + ".npy"), t.cpu().numpy())
 
 
 def moist_variant(model, dt, steps=5):
@@ -947,6 +982,8 @@ def run_rank(args):
             elapsed, comm_ms, finite = t[0].item(), t[1].item(), t[2].item() == 0.0
     except Exception as exc:          # noqa: BLE001
         fail(f"timed region failed: {exc!r}")
+    if args.dump_outputs:
+        dump_outputs(model, args.dump_outputs)      # before anything else steps or changes the model
 
     cells = G[0] * G[1] * G[2]                      # all ranks together
     cells_rank = cells // world
@@ -994,24 +1031,25 @@ def run_rank(args):
             out["transport"] = transport
             if preflight_summary:
                 out["preflight"] = preflight_summary
-        if world == 1 and not use_slabs and args.workload == "bubble" and not args.no_moist_variant:
+        # the side measurements (--full): each takes runs of its own and none of them enters the headline figure
+        if args.full and world == 1 and not use_slabs and args.workload == "bubble" and not args.no_moist_variant:
             try:
                 out["moist_variant"] = moist_variant(model, dt, steps=args.steps)      # the same K as the headline: one diagnosis pass per K steps in both legs
             except Exception as exc:       # never let the side measurement take the headline line down
                 out["moist_variant"] = {"error": repr(exc)}
-        if world == 1 and not args.no_compressible and not use_slabs and args.workload == "bubble":
+        if args.full and world == 1 and not args.no_compressible and not use_slabs and args.workload == "bubble":
             try:
                 del model
                 torch.cuda.empty_cache()
                 out["second_milestone"] = milestone_in_fresh_process(bz, device)
             except Exception as exc:       # never let the side measurement take the headline line down
                 out["second_milestone"] = {"error": repr(exc)}
-        if world == 1 and not args.no_float32 and not use_slabs and args.workload == "bubble":
+        if args.full and world == 1 and not args.no_float32 and not use_slabs and args.workload == "bubble":
             try:
                 out["float32"] = float32_run(bz, device, args.size, single_steps=args.single_steps)
             except Exception as exc:
                 out["float32"] = {"error": repr(exc)}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             # the headline key is the HEADLINE size (512^3, one warm-up + one timed step, ~40 s of CPU work) when the host has the memory
             # (VERDICT r04 hygiene item); otherwise — or with --no-cpu-full-size — the bounded 256^3 sample
             full = None
@@ -1057,8 +1095,13 @@ def main():
                     help="bubble: the headline workload (configs[1]); config3: 1024 x (128 N) x 512 slabs; config4: compressible + "
                          "Kessler 512x512x128 (second milestone, split over the ranks)")
     ap.add_argument("--single-steps", action="store_true", help="K separate time_step! calls (full diagnosis after every step) instead of the multi-step seam")
-    ap.add_argument("--no-moist-variant", action="store_true", help="skip the moist run of the same grid reported under `moist_variant`")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="one GPU, bubble workload: also run the side measurements (moist_variant, second_milestone, float32, cpu_baseline); "
+                         "a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="one GPU, bubble workload: after the timed steps write the model's fields as DIR/<name>.npy (see dump_outputs)")
+    ap.add_argument("--no-moist-variant", action="store_true", help="with --full: skip the moist run of the same grid reported under `moist_variant`")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle baseline")
     ap.add_argument("--no-cpu-full-size", action="store_true", help="skip the 512^3 leg of the CPU baseline (runs only when the host has >= 96 GB free)")
     ap.add_argument("--replicas", action="store_true", help="N>1: independent replicas instead of the slab decomposition (explicit only)")
     ap.add_argument("--slab", action="store_true", help="N=1: run the slab driver (world 1) instead of the whole-step seam")
@@ -1066,17 +1109,19 @@ def main():
                     help="slab runs: the C library's RCCL communicator (default) or the Python orchestration over torch.distributed; never switched silently")
     ap.add_argument("--cpu-size", type=int, default=256)
     ap.add_argument("--cpu-budget", type=float, default=25.0, help="seconds of CPU work for the cpu_baseline leg")
-    ap.add_argument("--no-float32", action="store_true", help="skip the Float32 run reported under `float32`")
+    ap.add_argument("--no-float32", action="store_true", help="with --full: skip the Float32 run reported under `float32`")
     ap.add_argument("--config4-order", type=int, default=5, choices=(5, 7, 9), help="--workload config4: WENO order (the example uses 9)")
     ap.add_argument("--config4-float32", action="store_true", help="--workload config4 in Float32, the example's own precision (one GPU)")
-    ap.add_argument("--milestone-only", action="store_true", help="run only the compressible milestone and print its JSON object (what the default command spawns)")
+    ap.add_argument("--milestone-only", action="store_true", help="run only the compressible milestone and print its JSON object (what --full spawns)")
     ap.add_argument("--no-compressible", action="store_true",
-                    help="skip the short compressible split-explicit measurement reported under `second_milestone`")
+                    help="with --full: skip the short compressible split-explicit measurement reported under `second_milestone`")
     ap.add_argument("--launch-timeout", type=float, default=1500.0, help="self-launched ranks are killed after this many seconds")
     ap.add_argument("--collective-timeout", type=float, default=300.0, help="process-group timeout (seconds)")
     ap.add_argument("--selftest-launcher", action="store_true",
                     help="CPU/gloo: exercise the launcher and the slab communication pattern without a GPU")
     args = ap.parse_args()
+    if args.dump_outputs and (args.gpus != 1 or args.workload != "bubble" or args.slab or args.preflight or args.milestone_only):
+        ap.error("--dump-outputs writes the fields of the one-GPU bubble run (--gpus 1, --workload bubble, no --slab)")
     if args.milestone_only:
         import breeze_jl_amd as bz
         print(json.dumps(compressible_milestone(bz, "cuda:0")), flush=True)

@@ -90,3 +90,49 @@ def test_workload_shapes():
     assert G == (1024, 1024, 512) and "configs[3]" in label and scaling == "strong"
     with pytest.raises(ValueError):
         bench.problem(argparse.Namespace(size=500, scaling="strong", workload="bubble"), 8)
+
+
+def _stand_in_model(n, seed=0):
+    """The fields dump_outputs reads, as CPU tensors with halos (the device model needs a GPU)."""
+    import types
+    import torch
+    g = torch.Generator().manual_seed(seed)
+
+    def fld(zface=False):
+        parent = torch.randn((n + 6 + zface, n + 6, n + 6), dtype=torch.float64, generator=g)
+        return types.SimpleNamespace(parent=parent, interior=parent[3:3 + n + zface, 3:3 + n, 3:3 + n])
+    return types.SimpleNamespace(synchronize=lambda: None, momentum={"ρu": fld(), "ρv": fld(), "ρw": fld(True)},
+                                 velocities={"u": fld(), "v": fld(), "w": fld(True)}, potential_temperature_density=fld(),
+                                 potential_temperature=fld(), moisture_density=fld(), specific_moisture=fld(), temperature=fld(),
+                                 dynamics=types.SimpleNamespace(pressure_anomaly=fld()))
+
+
+def test_dump_outputs_writes_small_fields_whole_and_a_seeded_sample_of_large_ones(tmp_path):
+    """--dump-outputs: every field a caller of the timed seam receives, as <name>.npy in Float64; whole up to DUMP_SAMPLE cells, above
+    that the values at the same DUMP_SAMPLE distinct cells in every run; 64 MB at most whatever the grid."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    small = _stand_in_model(16)
+    bench.dump_outputs(small, str(tmp_path / "small"))
+    names = sorted(os.listdir(tmp_path / "small"))
+    assert names == sorted(n + ".npy" for n in ("rho_u", "rho_v", "rho_w", "rho_theta", "rho_qt", "u", "v", "w", "theta", "qt", "T", "p_anomaly"))
+    assert np.array_equal(np.load(tmp_path / "small" / "rho_w.npy"), small.momentum["ρw"].interior.numpy())
+    large = _stand_in_model(81)      # 81^3 > 2^19 cells
+    for run in ("a", "b"):
+        bench.dump_outputs(large, str(tmp_path / run))
+    total = 0
+    for name in names:
+        a, b = np.load(tmp_path / "a" / name), np.load(tmp_path / "b" / name)
+        assert a.dtype == np.float64 and a.shape == (bench.DUMP_SAMPLE,) and np.array_equal(a, b)
+        total += os.path.getsize(tmp_path / "a" / name)
+    assert total <= 64e6
+    w = large.momentum["ρw"].interior
+    flat = np.sort(np.random.default_rng(bench.DUMP_SEED).choice(w.numel(), bench.DUMP_SAMPLE, replace=False))
+    assert np.array_equal(np.load(tmp_path / "a" / "rho_w.npy"), w.reshape(-1).numpy()[flat])
+
+
+def test_dump_outputs_is_refused_outside_the_one_gpu_bubble_run(tmp_path):
+    for extra in (["--gpus", "2"], ["--workload", "cbl"], ["--slab"]):
+        p, lines = _run(extra + ["--dump-outputs", str(tmp_path)])
+        assert p.returncode == 2 and "--dump-outputs" in p.stderr and not lines

@@ -7,7 +7,7 @@ O=gpurun_out/$TAG; mkdir -p $O
 idx=0
 for envs in "$@"; do
   idx=$((idx+1))
-  env $envs timeout 400 python bench.py --steps ${STEPS:-10} --warmup 3 --no-cpu-baseline --no-compressible ${BENCH_ARGS:-} > $O/bench_$idx.json 2> $O/bench_$idx.err
+  env $envs timeout 400 python bench.py --full --steps ${STEPS:-10} --warmup 3 --no-cpu-baseline --no-compressible ${BENCH_ARGS:-} > $O/bench_$idx.json 2> $O/bench_$idx.err
   python - "$O/bench_$idx.json" "$envs" <<'PY'
 import json,sys
 try:

@@ -20,7 +20,7 @@ for k in ("comm_ms_per_step", "exposed_comm_ms_per_step", "transport", "error"):
     if k in d: print("   ", k, d[k])
 PY
 }
-run default python bench.py --steps 10 --warmup 3 --no-cpu-baseline
+run default python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline
 run slab1 python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-compressible --no-float32 --slab
 BZ_COMM_SELF_MESSAGES=1 run slab1_self python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-compressible --no-float32 --slab
 run cbl python bench.py --workload cbl --steps 20 --warmup 3

@@ -6,7 +6,7 @@ REPS=$1; shift
 O=gpurun_out/env_ab; mkdir -p $O
 for rep in $(seq $REPS); do
 for envs in "$@"; do
-  env $envs timeout 300 python bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-compressible > $O/bench.json 2> $O/bench.err
+  env $envs timeout 300 python bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-compressible > $O/bench.json 2> $O/bench.err
   python - "$O/bench.json" "$envs" <<'PY'
 import json,sys
 try:

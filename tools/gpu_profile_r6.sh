@@ -8,14 +8,14 @@ export TMPDIR=/tmp
 TAG=${1:-r06}
 O=gpurun_out/$TAG; mkdir -p $O
 echo "== bench (default command)"
-timeout 900 python bench.py > $O/bench.json 2> $O/bench.err; tail -c 300 $O/bench.err
+timeout 900 python bench.py --full > $O/bench.json 2> $O/bench.err; tail -c 300 $O/bench.err
 echo "== rocprofv3 kernel statistics of the default command"
 # (the profiled runs keep the compressible milestone in the process rocprofv3 watches: BZ_BENCH_MILESTONE_INPROCESS=1)
-BZ_BENCH_MILESTONE_INPROCESS=1 timeout 1200 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python bench.py --no-cpu-baseline > $O/bench_under_rocprof.json 2> $O/stats.log
+BZ_BENCH_MILESTONE_INPROCESS=1 timeout 1200 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python bench.py --full --no-cpu-baseline > $O/bench_under_rocprof.json 2> $O/stats.log
 cp $(find $O/stats -name "*kernel_stats.csv" | head -1) $O/kernel_stats.csv 2>/dev/null
 echo "== PMC traffic passes (separate passes: FETCH_SIZE, WRITE_SIZE)"
 export BZ_BENCH_MILESTONE_INPROCESS=1
-B="python bench.py --steps 2 --warmup 1 --no-cpu-baseline"      # the moist leg rides along: the general bodies are kernels of their own since round 5
+B="python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline"      # the moist leg rides along: the general bodies are kernels of their own since round 5
 timeout 900 rocprofv3 --kernel-trace --output-format csv --pmc FETCH_SIZE -d $O/pmc_fetch -- $B > $O/pmc_fetch.log 2>&1
 timeout 900 rocprofv3 --kernel-trace --output-format csv --pmc WRITE_SIZE -d $O/pmc_write -- $B > $O/pmc_write.log 2>&1
 python tools/pmc_summary.py $O/pmc_summary.json $O/pmc_fetch $O/pmc_write > $O/pmc_summary.log 2>&1

@@ -5,7 +5,7 @@ export TMPDIR=/tmp
 O=gpurun_out/r4_first; mkdir -p $O
 timeout 1500 python -m pytest tests/test_multi_step.py tests/test_gpu_parity.py tests/test_comm.py tests/test_cbl.py -m gpu -x -q > $O/pytest.log 2>&1; tail -15 $O/pytest.log
 for mode in "" "--single-steps"; do
-  timeout 400 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-compressible $mode > $O/bench_${mode:-multi}.json 2> $O/bench_${mode:-multi}.err
+  timeout 400 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-compressible $mode > $O/bench_${mode:-multi}.json 2> $O/bench_${mode:-multi}.err
   python - "$O/bench_${mode:-multi}.json" "${mode:-multi}" <<'PY'
 import json,sys
 try:

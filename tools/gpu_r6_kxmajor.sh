@@ -6,7 +6,7 @@ O=gpurun_out/r6_kxmajor; mkdir -p $O
 timeout 1500 python -m pytest tests/test_gpu_parity.py tests/test_float32.py tests/test_multi_step.py tests/test_dry_shortcut.py -m gpu -x -q > $O/pytest.log 2>&1; tail -4 $O/pytest.log
 for rep in 1 2; do
 for envs in "BZ_POISSON_KXMAJOR=0" "BZ_POISSON_KX_CHUNK_MB=200 BZ_POISSON_KX_PAD=0" "BZ_POISSON_KX_CHUNK_MB=200 BZ_POISSON_KX_PAD=1" "BZ_POISSON_KX_CHUNK_MB=256 BZ_POISSON_KX_PAD=1" "BZ_POISSON_KX_CHUNK_MB=360 BZ_POISSON_KX_PAD=1" "BZ_POISSON_KX_CHUNK_MB=200 BZ_POISSON_KX_PAD=3"; do
-  env $envs timeout 300 python bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-compressible > $O/bench.json 2> $O/bench.err
+  env $envs timeout 300 python bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-compressible > $O/bench.json 2> $O/bench.err
   python - "$O/bench.json" "$envs" <<'PY'
 import json,sys
 try:

@@ -7,7 +7,7 @@ TAG=$1; shift
 O=gpurun_out/$TAG; mkdir -p $O
 for name in base "$@"; do
   lib=$PWD/breeze.jl_amd/lib/var_$name.so; [ $name = base ] && lib=$PWD/breeze.jl_amd/lib/libbreeze_hip.so
-  BREEZE_HIP_LIB=$lib timeout 300 python bench.py --steps ${STEPS:-6} --warmup 2 --no-cpu-baseline --no-compressible --no-float32 ${BENCH_ARGS:-} > $O/b_$name.json 2> $O/b_$name.err
+  BREEZE_HIP_LIB=$lib timeout 300 python bench.py --full --steps ${STEPS:-6} --warmup 2 --no-cpu-baseline --no-compressible --no-float32 ${BENCH_ARGS:-} > $O/b_$name.json 2> $O/b_$name.err
   python - $O/b_$name.json $name <<'PY'
 import json,sys
 try:

@@ -4,7 +4,7 @@ export TMPDIR=/tmp
 L=$PWD/breeze.jl_amd/lib
 for rep in 1 2; do for name in base noxf; do
 if [ $name = base ]; then A=$L/libbreeze_hip.so; B=$L/libbreeze_hip_f32.so; else A=$L/var_noxf.so; B=$L/var32_noxf.so; fi
-BREEZE_HIP_LIB=$A BREEZE_HIP_F32_LIB=$B python bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-compressible --no-moist-variant 2>/dev/null | tail -1 | python -c "
+BREEZE_HIP_LIB=$A BREEZE_HIP_F32_LIB=$B python bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-compressible --no-moist-variant 2>/dev/null | tail -1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); k=d['kernels_ms_per_step']; f=d['float32']; kf=f['kernels_ms_per_step']
 g=lambda k,n: round(k[n]/3,3)
