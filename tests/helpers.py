@@ -69,3 +69,48 @@ def randomize(om, seed, amp_u=5.0, amp_theta=2.0, amp_q=5e-3):
 def relerr(a, b):
     scale = np.max(np.abs(b))
     return np.max(np.abs(a - b)) / (scale if scale > 0 else 1.0)
+
+
+# ---- Float32 steps: errors measured against what the step did, not against the field's background ----------------------------------------
+def increment_error(got, want, start, floor=1e-7):
+    """max|got - want| / max|want - start|: the error of a stepped field relative to the largest change the reference made to it.
+    `start` is the state both models were given (interior, Float64) before the first step.  A field the reference did not move
+    (max|want - start| <= floor * max|want|, or zero) cannot be judged this way, and is an error rather than a vacuous pass."""
+    got, want, start = (np.asarray(a, dtype=np.float64) for a in (got, want, start))
+    inc = float(np.max(np.abs(want - start)))
+    if not inc > floor * float(np.max(np.abs(want))) or inc == 0.0:
+        raise ValueError(f"increment_error: the reference moved the field by {inc:.3e} only (max |want| {np.max(np.abs(want)):.3e})")
+    return float(np.max(np.abs(got - want))) / inc
+
+
+# Tolerances of increment_error for Float32 models against the Float64 oracle (or, where stated, against a Float32 run of a second
+# kernel sequence), per field, one table for each dynamical core and one for Float32 substep storage in a Float64 compressible model.
+# Each value is at most 4x the worst error measured on the MI355X over every case that uses it (tests/test_float32.py,
+# tests/test_float32_increments.py, tests/test_gpu_compressible.py), and at most a third of the smallest error the CPU test
+# tests/test_float32_tolerances.py measures between the oracle and the oracle with a known defect (dt x 1.01, WENO7 for WENO5,
+# 5 acoustic substeps for 6).  Worst measured on the MI355X (lean and BZ_NO_LEAN=1 runs agree to the digits shown):
+#   anelastic     ru 7.6e-5 (mixed orders), rv 6.8e-5 (mixed orders), rw 3.2e-5 (BOMEX), rho theta 1.3e-3 (sweep, walls in y, first step),
+#                 rho q 4.6e-4 (mixed orders), T 2.0e-3 (sweep, walls in y, first step), tracer 2.6e-4, rho q^r 5.9e-6 (Kessler)
+#   compressible  rho_d 2.8e-4, rho theta 2.4e-4, rho q 4.8e-4, T 6.2e-4, p 3.2e-4, rho u 5.2e-4, rho w 3.3e-4
+#   substep storage (Float32 acoustic working fields in a Float64 model): rho_d 6.8e-8, rho theta 2.1e-8, rho q 6.2e-8, T 1.8e-7,
+#                 p 2.1e-8, rho u 1.8e-7, rho v 2.4e-7, rho w 4.7e-8
+# The smallest defect distances (dt x 1.01) are 6.5e-3 .. 1e-2 of the increment for every field but two of the anelastic Kessler case
+# (see tests/test_float32_tolerances.py: DT_EXEMPT).
+F32_INCREMENT_TOL = {
+    "anelastic": {"ru": 2e-4, "rv": 2e-4, "rw": 1.2e-4, "rtheta": 2e-3, "rq": 1e-3, "T": 2.9e-3, "rc0": 1e-3, "rqr": 2.3e-5},
+    "compressible": {"rho_d": 1e-3, "rtheta": 9e-4, "rq": 1.5e-3, "T": 2e-3, "p": 1.2e-3, "ru": 1.5e-3, "rw": 1.2e-3},
+    "substep_storage": {"rho_d": 2.5e-7, "rtheta": 8e-8, "rq": 2.4e-7, "T": 7e-7, "p": 8e-8, "ru": 7e-7, "rv": 9e-7, "rw": 1.8e-7},
+}
+
+
+def assert_increments(label, got, want, start, table, report=None):
+    """increment_error of every field of `got` (name -> array) against F32_INCREMENT_TOL[table]; all fields are measured and printed
+    before the assertion so that one run shows the whole picture."""
+    tol = F32_INCREMENT_TOL[table]
+    errs = {n: increment_error(got[n], want[n], start[n]) for n in got}
+    print(f"F32INC {label} [{table}]:", " ".join(f"{n}={e:.2e}" for n, e in errs.items()))
+    if report is not None:
+        report.update(errs)
+    bad = {n: (e, tol[n]) for n, e in errs.items() if not e < tol[n]}
+    assert not bad, f"{label}: increment errors beyond the Float32 tolerance {bad} (all: {errs})"
+    return errs

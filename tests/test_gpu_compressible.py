@@ -845,15 +845,21 @@ def test_float32_substep_storage_in_a_float64_model(oracle, oc, bz, td):
     def qv(x, y, z):
         return 5e-3 * np.exp(-z / 2e3) * (1 + 0.2 * np.sin(2 * np.pi * x / 8e3)) + 0 * y
 
+    import f32_cases as fc
+    from helpers import assert_increments
+    case = fc.SUBSTEP_CASES[f"substep_storage_{fc.SUBSTEP_TD.index(td)}"]      # the same set-up for the CPU tolerance test
+    assert theta(1e3, 0.0, 3e3) == fc.substep_storage_theta(1e3, 0.0, 3e3) and qv(1e3, 0.0, 3e3) == fc.substep_storage_qv(1e3, 0.0, 3e3)
     rho = om.ref.density[g.Hz:g.Hz + g.Nz][:, None, None]
     u0 = lambda x, y, z: 3.0 + 0 * x + 0 * y + 0 * z
     om.set(rho=rho, theta=theta, u=u0, v=0.0, w=0.0, qv=qv)
+    start = fc.oracle_fields(om, case.fields)
     for m in (hm, h64):
         m.set(ρ=rho, θ=theta, u=u0, v=0.0, w=0.0, qᵗ=qv)
-    for _ in range(3):
-        om.time_step(2.0)
-        hm.time_step(2.0)
-        h64.time_step(2.0)
+    for _ in range(case.steps):
+        om.time_step(case.dt)
+        hm.time_step(case.dt)
+        h64.time_step(case.dt)
+    assert_increments(case.name, fc.device_fields(hm, case.fields, compressible=True), fc.oracle_fields(om, case.fields), start, case.kind)
     worst = cmp_interior(om, hm, ("rho_d", "rtheta", "rq", "ru", "rv", "rw", "T", "p"), 2e-6)
     print("float32 substep storage vs float64 oracle:", {k: f"{v:.1e}" for k, v in worst.items()})
     diff = np.abs(hm.momentum["ρw"].interior_cpu() - h64.momentum["ρw"].interior_cpu()).max()
