@@ -68,6 +68,30 @@ class bz_bulk_surface_fluxes(C.Structure):
         "triple_point_pressure")]
 
 
+_MAPPING_FIELDS = ("stable_unstable_transition", "strongly_stable_transition", "au11", "bu11", "bu12", "au21", "au22", "bu31", "bu32", "bu33",
+                   "aw11", "aw12", "aw21", "aw22", "bw11", "bw12", "bw21", "bw22", "as11", "as21", "bs11", "bs21", "bs22")
+_PSI_FIELDS = ("gamma_d", "gamma_t", "psi_a", "psi_b", "psi_c", "psi_d")
+
+
+class bz_polynomial_coefficient(C.Structure):
+    _fields_ = ([(n, C.c_double) for n in ("a0", "a1", "a2", "roughness_length", "minimum_wind_speed")] +
+                [("stability", C.c_int32), ("reserved", C.c_int32), ("scalar_roughness_length", C.c_double)] +
+                [(n, C.c_double) for n in _MAPPING_FIELDS + _PSI_FIELDS])
+
+
+class bz_surface_flux(C.Structure):
+    _fields_ = [("enabled", C.c_int32), ("polynomial", C.c_int32), ("coefficient", C.c_double), ("gustiness", C.c_double),
+                ("surface_temperature", C.c_double), ("surface_temperature_field", _dp), ("poly", bz_polynomial_coefficient)]
+
+
+class bz_surface_layer(C.Structure):
+    _fields_ = ([("drag", bz_surface_flux), ("heat", bz_surface_flux), ("vapor", bz_surface_flux)] +
+                [(n, C.c_double) for n in ("surface_pressure", "standard_pressure", "liquid_latent_heat", "liquid_heat_capacity",
+                                           "energy_reference_temperature", "triple_point_temperature", "triple_point_pressure")] +
+                [("filtered", C.c_int32), ("filter_height_set", C.c_int32), ("filter_height", C.c_double), ("filter_timescale", C.c_double),
+                 ("filter_stage_mask", C.c_int32), ("reserved", C.c_int32)])
+
+
 class bz_tracer_fields(C.Structure):
     _fields_ = [("density", C.c_void_p), ("specific", C.c_void_p), ("U0", C.c_void_p), ("G", C.c_void_p)]
 
@@ -241,6 +265,11 @@ SYMBOLS = {
     "bz_set_bounds_preserving_advection": (C.c_int, [_ctx, C.POINTER(bz_bounds_preserving_advection)]),
     "bz_compute_closure_fields": (C.c_int, [_ctx, _sp]),
     "bz_set_bulk_surface_fluxes": (C.c_int, [_ctx, C.POINTER(bz_bulk_surface_fluxes)]),
+    "bz_set_surface_layer": (C.c_int, [_ctx, C.POINTER(bz_surface_layer)]),
+    "bz_surface_layer_initialize": (C.c_int, [_ctx, _sp]),
+    "bz_surface_layer_update": (C.c_int, [_ctx, _sp, C.c_double]),
+    "bz_surface_layer_get_filtered": (C.c_int, [_ctx, C.c_int, _dp]),
+    "bz_surface_layer_set_filtered": (C.c_int, [_ctx, C.c_int, _dp]),
     "bz_set_forcings": (C.c_int, [_ctx, C.POINTER(bz_column_forcings)]),
     "bz_set_relaxation": (C.c_int, [_ctx, C.POINTER(bz_column_relaxation)]),
     "bz_set_field_forcing": (C.c_int, [_ctx, C.c_void_p, C.c_int]),

@@ -251,6 +251,157 @@ __global__ __launch_bounds__(256) void k_bulk_bottom_flux(DevGrid g, BulkParams 
     }
 }
 
+
+// ---- PolynomialCoefficient bulk fluxes on a FilteredSurfaceVelocities state (include/breeze_hip.h: bz_surface_layer) ----
+//   coefficient chain   src/BoundaryConditions/polynomial_bulk_coefficient.jl:246-351,526-561,581-589,625-707
+//   fluxes              bulk_drag.jl:114-134, bulk_scalar_fluxes.jl:82-99,123-138,206-234, BoundaryConditions.jl:56-137
+//   filter              filtered_surface_state.jl:183-226, update_boundary_conditions.jl:12-47
+//   theta_v             AtmosphereModels/Diagnostics/potential_temperatures.jl:574-579
+// Latency-sized 2-D kernels: one thread per surface cell, every regime of the stability chain evaluated and selected (no divergence).
+struct SLCoef {
+    int on, poly, scalar;       // scalar: the Val(:scalar) correction factor (heat, vapour); 0: Val(:momentum)
+    double C, g2, T0;
+    const double *T0f;          // (Ny x Nx) centre array or nullptr
+    bz_polynomial_coefficient P;
+};
+struct SLParams {
+    SLCoef drag, heat, vapor;
+    double p0, pi0;             // surface pressure, (p0 / p_st)^(Rd / cpd)
+    double dc, L0, Ttr, ptr;    // saturation vapour pressure over a planar liquid surface (Clausius-Clapeyron, as bulk_flux)
+    int filtered;
+    double *fu, *fv, *fthv, *fth, *fq;
+};
+
+__device__ __forceinline__ double sl_theta_v(const DevGrid &g, double T, double qv, double ql)
+{
+    const double pid = pow(g.p_r[0] / g.pst, g.Rd / g.cpd);
+    return (T / pid) * (1.0 + (g.Rv / g.Rd - 1.0) * qv - ql);
+}
+
+__device__ __forceinline__ double sl_coefficient(const SLCoef &c, const SLParams &S, const DevGrid &g, double U, double T0, double h, double thv)
+{
+    if (!c.poly) return c.C;
+    const bz_polynomial_coefficient &P = c.P;
+    const double Us = fmax(U, P.minimum_wind_speed);
+    const double C10 = (P.a0 + P.a1 * Us + P.a2 / Us) * 1e-3;
+    const double ell = P.roughness_length;
+    const double alpha = log(h / ell);
+    const double r = log(10.0 / ell) / alpha;
+    const double Ch = C10 * (r * r);
+    if (!P.stability) return Ch;
+    const double beta = log(ell / P.scalar_roughness_length);
+    // theta_v0 = T0 (1 + delta q^v+_t(T0, p0)): the pressure-based saturation_total_specific_moisture (saturation_specific_humidity.jl:111-118)
+    const double ps = S.ptr * pow(T0 / S.Ttr, S.dc / g.Rv) * exp((1.0 / S.Ttr - 1.0 / T0) * S.L0 / g.Rv);
+    const double edv = g.Rd / g.Rv;
+    const double qs = edv * ps / (S.p0 + (edv - 1.0) * ps);
+    const double thv0 = T0 * (1.0 + (g.Rv / g.Rd - 1.0) * qs);
+    // bulk_richardson_number(h, theta_v, theta_v0, U, U_min) with its default g = 9.81 (:556-561)
+    const double Ri = (9.81 / ((thv + thv0) / 2)) * h * (thv - thv0) / (Us * Us);
+    // Li et al. (2010): the three regimes, then selects (:246-275)
+    const double al2 = alpha * alpha, Ri2 = Ri * Ri;
+    const double zu = (P.au11 * alpha) * Ri2 + ((P.bu11 * beta + P.bu12) * al2 + (P.au21 * beta + P.au22) * alpha +
+                                                (P.bu31 * (beta * beta) + P.bu32 * beta + P.bu33)) * Ri;
+    const double zw = ((P.aw11 * beta + P.aw12) * alpha + (P.aw21 * beta + P.aw22)) * Ri2 +
+                      ((P.bw11 * beta + P.bw12) * alpha + (P.bw21 * beta + P.bw22)) * Ri;
+    const double zs = (P.as11 * alpha + P.as21) * Ri + P.bs11 * alpha + P.bs21 * beta + P.bs22;
+    const double zeta = Ri < P.stable_unstable_transition ? zu : (Ri <= P.strongly_stable_transition ? zw : zs);
+    // Hogstrom (1996) unstable, Beljaars & Holtslag (1991) stable (:288-335)
+    const double x = sqrt(sqrt(fmax(1.0 - P.gamma_d * zeta, 0.0)));
+    const double PsiD_u = 2 * log((1.0 + x) / 2) + log((1.0 + x * x) / 2) - 2 * atan(x) + 3.141592653589793 / 2;
+    const double y = sqrt(fmax(1.0 - P.gamma_t * zeta, 0.0));
+    const double PsiT_u = 2 * log((1.0 + y) / 2);
+    const double ez = exp(-P.psi_d * zeta), cd = P.psi_c / P.psi_d;
+    const double PsiD_s = -(P.psi_a * zeta + P.psi_b * (zeta - cd) * ez + P.psi_b * P.psi_c / P.psi_d);
+    const double xs = fmax(1.0 + 2 * P.psi_a / 3 * zeta, 0.0);
+    const double PsiT_s = -(xs * sqrt(xs) + P.psi_b * (zeta - cd) * ez + P.psi_b * P.psi_c / P.psi_d - 1.0);
+    const double PsiD = zeta < 0.0 ? PsiD_u : PsiD_s, PsiT = zeta < 0.0 ? PsiT_u : PsiT_s;
+    // stability_correction_factor (:341-351)
+    const double dD = fmax(alpha - PsiD, alpha / 10);
+    const double bh = alpha + beta;
+    const double dT = fmax(bh - PsiT, bh / 10);
+    const double fm = (alpha / dD) * (alpha / dD), fs = (alpha / dD) * (bh / dT);
+    return Ch * (c.scalar ? fs : fm);
+}
+
+__global__ __launch_bounds__(256) void k_surface_layer_flux(DevGrid g, SLParams S, double *__restrict__ Gu, double *__restrict__ Gv,
+                                                            double *__restrict__ Gth, double *__restrict__ Gq,
+                                                            const double *__restrict__ u, const double *__restrict__ v,
+                                                            const double *__restrict__ th, const double *__restrict__ qv,
+                                                            const double *__restrict__ ql, const double *__restrict__ T, double scale)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x, j = blockIdx.y;
+    if (i >= g.Nx) return;
+    const long long n = g.idx(i, j, 0);
+    const int c = j * g.Nx + i;
+    const double dz = g.dzc[0], h = g.zc[0];
+    const long long sx = g.Hx ? 1 : 0, sy = g.Hy ? g.Sx : 0;      // Flat directions have no neighbours (as k_bulk_bottom_flux)
+    // the filtered fields wrap periodically and collapse in a Flat direction
+    const int ip = g.Hx ? (i + 1 == g.Nx ? 0 : i + 1) : i, im = g.Hx ? (i == 0 ? g.Nx - 1 : i - 1) : i;
+    const int jp = g.Hy ? (j + 1 == g.Ny ? 0 : j + 1) : j, jm = g.Hy ? (j == 0 ? g.Ny - 1 : j - 1) : j;
+    const bool filt = S.filtered != 0;
+    auto U = [&](int di, int dj) {
+        return filt ? S.fu[(dj < 0 ? jm : dj > 0 ? jp : j) * g.Nx + (di < 0 ? im : di > 0 ? ip : i)] : u[n + di * sx + dj * sy];
+    };
+    auto V = [&](int di, int dj) {
+        return filt ? S.fv[(dj < 0 ? jm : dj > 0 ? jp : j) * g.Nx + (di < 0 ? im : di > 0 ? ip : i)] : v[n + di * sx + dj * sy];
+    };
+    auto sq = [](double a) { return a * a; };
+    const double U2c = (sq(U(0, 0)) + sq(U(1, 0))) / 2 + (sq(V(0, 0)) + sq(V(0, 1))) / 2;
+    const double Uc = sqrt(U2c);      // the un-gusted centre wind speed of bulk_coefficient, for all three conditions
+    const double thv = filt ? S.fthv[c] : sl_theta_v(g, T[n], qv[n], ql ? ql[n] : 0.0);
+    if (S.drag.on) {
+        const double T0 = S.drag.T0f ? S.drag.T0f[c] : S.drag.T0;
+        const double rho0 = S.p0 / (g.Rd * T0);
+        const double C = sl_coefficient(S.drag, S, g, Uc, T0, h, thv);
+        const double v2 = ((sq(V(-1, 0)) + sq(V(-1, 1))) / 2 + (sq(V(0, 0)) + sq(V(0, 1))) / 2) / 2;
+        const double u2 = ((sq(U(0, -1)) + sq(U(1, -1))) / 2 + (sq(U(0, 0)) + sq(U(1, 0))) / 2) / 2;
+        const double ui = U(0, 0), vi = V(0, 0);
+        const double Ju = -rho0 * C * sqrt(sq(ui) + v2 + S.drag.g2) * ui;
+        const double Jv = -rho0 * C * sqrt(u2 + sq(vi) + S.drag.g2) * vi;
+        if (!(g.bounded_x && i == 0)) Gu[n] += scale * (Ju / dz);      // wall faces carry no tendency
+        if (!(g.bounded_y && j == 0)) Gv[n] += scale * (Jv / dz);
+    }
+    if (S.heat.on) {
+        const double T0 = S.heat.T0f ? S.heat.T0f[c] : S.heat.T0;
+        const double rho0 = S.p0 / (g.Rd * T0);
+        const double C = sl_coefficient(S.heat, S, g, Uc, T0, h, thv);
+        const double theta = filt ? S.fth[c] : th[n];
+        Gth[n] += scale * ((-rho0 * C * sqrt(U2c + S.heat.g2) * (theta - T0 / S.pi0)) / dz);
+    }
+    if (S.vapor.on) {
+        const double T0 = S.vapor.T0f ? S.vapor.T0f[c] : S.vapor.T0;
+        const double rho0 = S.p0 / (g.Rd * T0);
+        const double C = sl_coefficient(S.vapor, S, g, Uc, T0, h, thv);
+        const double ps = S.ptr * pow(T0 / S.Ttr, S.dc / g.Rv) * exp((1.0 / S.Ttr - 1.0 / T0) * S.L0 / g.Rv);
+        const double q0 = ps / (rho0 * g.Rv * T0);
+        const double q = filt ? S.fq[c] : qv[n];
+        Gq[n] += scale * ((-rho0 * C * sqrt(U2c + S.vapor.g2) * (q - q0)) / dz);
+    }
+}
+
+// f^ <- (f^ + eps f) / (1 + eps) of every filtered field in one launch; INIT: f^ <- f (initialize!)
+template <bool INIT>
+__global__ __launch_bounds__(256) void k_surface_layer_filter(DevGrid g, SLParams S, const double *__restrict__ u, const double *__restrict__ v,
+                                                              const double *__restrict__ th, const double *__restrict__ q,
+                                                              const double *__restrict__ qv, const double *__restrict__ ql,
+                                                              const double *__restrict__ T, double eps)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x, j = blockIdx.y;
+    if (i >= g.Nx) return;
+    const long long n = g.idx(i, j, 0);
+    const int c = j * g.Nx + i;
+    const double thv = sl_theta_v(g, T[n], qv[n], ql ? ql[n] : 0.0);
+    if (INIT) {
+        S.fu[c] = u[n]; S.fv[c] = v[n]; S.fthv[c] = thv; S.fth[c] = th[n]; S.fq[c] = q[n];
+    } else {
+        S.fu[c] = (S.fu[c] + eps * u[n]) / (1.0 + eps);
+        S.fv[c] = (S.fv[c] + eps * v[n]) / (1.0 + eps);
+        S.fthv[c] = (S.fthv[c] + eps * thv) / (1.0 + eps);
+        S.fth[c] = (S.fth[c] + eps * th[n]) / (1.0 + eps);
+        S.fq[c] = (S.fq[c] + eps * q[n]) / (1.0 + eps);
+    }
+}
+
 static void free_forcings(bz_ctx *ctx)
 {
     if (ctx->d_forcing) hipFree(ctx->d_forcing);
@@ -375,7 +526,8 @@ int bzi_apply_relaxation(bz_ctx *ctx, const bz_state *s, const bz_prognostic *G,
     return BZ_OK;
 }
 
-void bzi_forcing_teardown(bz_ctx *ctx) { free_forcings(ctx); free_relaxation(ctx); }
+static void free_surface_layer(bz_ctx *ctx);
+void bzi_forcing_teardown(bz_ctx *ctx) { free_forcings(ctx); free_relaxation(ctx); free_surface_layer(ctx); }
 
 extern "C" int bz_set_forcings(bz_ctx *ctx, const bz_column_forcings *f)
 {
@@ -428,18 +580,184 @@ extern "C" int bz_set_bulk_surface_fluxes(bz_ctx *ctx, const bz_bulk_surface_flu
 {
     if (ctx) ++ctx->config_epoch;      // captured steps (bz_graph.hip) belong to one configuration
     if (!ctx) return BZ_ERR_INVALID;
-    if (!b) { ctx->has_bulk = false; return BZ_OK; }
+    if (!b) { ctx->bulk_const_on = false; ctx->has_bulk = ctx->sl_on; return BZ_OK; }
     if (ctx->compressible || ctx->dg.formulation != 0 || ctx->dg.microphysics == 2) {      // y-slab contexts: through the library-owned distributed step (bz_comm.hip)
         ctx->last_error = "bz_set_bulk_surface_fluxes: implemented for the anelastic potential-temperature model";
         return BZ_ERR_UNSUPPORTED;
     }
     ctx->bulk = *b;
-    ctx->has_bulk = (b->drag_coefficient > 0.0) || (b->heat_coefficient > 0.0) || (b->vapor_coefficient > 0.0);
+    ctx->bulk_const_on = (b->drag_coefficient > 0.0) || (b->heat_coefficient > 0.0) || (b->vapor_coefficient > 0.0);
+    ctx->has_bulk = ctx->bulk_const_on || ctx->sl_on;
+    return BZ_OK;
+}
+
+
+// ---- host side of the surface layer ----
+static void free_surface_layer(bz_ctx *ctx)
+{
+    if (ctx->d_sl) hipFree(ctx->d_sl);
+    ctx->d_sl = nullptr;
+    ctx->sl_on = false;
+    ctx->sl_initialized = false;
+    ctx->has_bulk = ctx->bulk_const_on;
+}
+
+extern "C" int bz_set_surface_layer(bz_ctx *ctx, const bz_surface_layer *L)
+{
+    if (!ctx) return BZ_ERR_INVALID;
+    // validate first: a rejected request leaves what is attached untouched
+    if (L) {
+        const char *why = nullptr;
+        if (ctx->compressible) why = "CompressibleDynamics contexts are not built";
+        else if (ctx->dg.formulation != 0) why = "the StaticEnergy formulation is not built";
+        else if (ctx->dg.microphysics == 2) why = "DCMIP2016 Kessler microphysics is not built";
+        else if (ctx->slab_mode) why = "y-slab contexts are not built (the filtered fields would need neighbour rows in the exchange)";
+        else if (L->filtered && L->filter_height_set) why = "a filter reference height other than the first cell centre is not built";
+        else if (L->filtered && (ctx->dg.bounded_x || ctx->dg.bounded_y)) why = "filtered surface fields on a Bounded x or y are not built";
+        if (why) { ctx->last_error = std::string("bz_set_surface_layer: ") + why; return BZ_ERR_UNSUPPORTED; }
+        if (L->filtered && (L->filter_stage_mask & ~7)) { ctx->last_error = "bz_set_surface_layer: filter_stage_mask names stages 1 (1), 2 (2), 3 (4)"; return BZ_ERR_INVALID; }
+    }
+    ++ctx->config_epoch;      // captured steps (bz_graph.hip) belong to one configuration
+    free_surface_layer(ctx);
+    if (!L) return BZ_OK;
+    const size_t cells = (size_t)ctx->dg.Nx * ctx->dg.Ny;
+    auto fail = [&](hipError_t e) {
+        ctx->last_error = std::string("bz_set_surface_layer: ") + hipGetErrorString(e);
+        free_surface_layer(ctx);
+        return -(int)e;
+    };
+    hipError_t e;
+    if ((e = hipMalloc(&ctx->d_sl, 8 * cells * sizeof(double))) != hipSuccess) { ctx->d_sl = nullptr; return fail(e); }
+    if ((e = hipMemsetAsync(ctx->d_sl, 0, 8 * cells * sizeof(double), ctx->stream)) != hipSuccess) return fail(e);
+    const bz_surface_flux *fl[3] = {&L->drag, &L->heat, &L->vapor};
+    for (int c = 0; c < 3; ++c)
+        if (fl[c]->enabled && fl[c]->surface_temperature_field &&
+            (e = hipMemcpyAsync(ctx->d_sl + c * cells, fl[c]->surface_temperature_field, cells * sizeof(double), hipMemcpyHostToDevice, ctx->stream)) != hipSuccess)
+            return fail(e);
+    if ((e = hipStreamSynchronize(ctx->stream)) != hipSuccess) return fail(e);      // the host arrays may go away after the call
+    ctx->sl = *L;
+    ctx->sl_on = L->drag.enabled || L->heat.enabled || L->vapor.enabled;
+    ctx->has_bulk = ctx->bulk_const_on || ctx->sl_on;
+    return BZ_OK;
+}
+
+static SLParams surface_layer_params(const bz_ctx *ctx)
+{
+    const bz_surface_layer &L = ctx->sl;
+    const DevGrid &g = ctx->dg;
+    const size_t cells = (size_t)g.Nx * g.Ny;
+    SLParams S;
+    const bz_surface_flux *fl[3] = {&L.drag, &L.heat, &L.vapor};
+    SLCoef *co[3] = {&S.drag, &S.heat, &S.vapor};
+    for (int c = 0; c < 3; ++c) {
+        co[c]->on = fl[c]->enabled != 0; co[c]->poly = fl[c]->polynomial != 0; co[c]->scalar = c != 0;
+        co[c]->C = fl[c]->coefficient; co[c]->g2 = fl[c]->gustiness * fl[c]->gustiness; co[c]->T0 = fl[c]->surface_temperature;
+        co[c]->T0f = fl[c]->surface_temperature_field ? ctx->d_sl + c * cells : nullptr;
+        co[c]->P = fl[c]->poly;
+    }
+    S.p0 = L.surface_pressure;
+    S.pi0 = pow(L.surface_pressure / L.standard_pressure, g.Rd / g.cpd);
+    S.dc = ctx->constants.vapor_heat_capacity - L.liquid_heat_capacity;
+    S.L0 = L.liquid_latent_heat - S.dc * L.energy_reference_temperature;
+    S.Ttr = L.triple_point_temperature; S.ptr = L.triple_point_pressure;
+    S.filtered = L.filtered != 0;
+    double *f = ctx->d_sl + 3 * cells;
+    S.fu = f; S.fv = f + cells; S.fthv = f + 2 * cells; S.fth = f + 3 * cells; S.fq = f + 4 * cells;
+    return S;
+}
+
+static int surface_layer_flux(bz_ctx *ctx, const bz_state *s, double *Gu, double *Gv, double *Gth, double *Gq, double scale)
+{
+    const DevGrid &g = ctx->dg;
+    if (ctx->sl.filtered && !ctx->sl_initialized) {
+        ctx->last_error = "surface layer: the filtered fields are not initialised (bz_surface_layer_initialize or bz_surface_layer_set_filtered)";
+        return BZ_ERR_INVALID;
+    }
+    const SLParams S = surface_layer_params(ctx);
+    ProfileScope ps(ctx, "surface_layer_fluxes");
+    const bool sa = g.microphysics == 1;
+    hipLaunchKernelGGL(k_surface_layer_flux, dim3((g.Nx + 255) / 256, g.Ny), dim3(256), 0, ctx->stream, g, S, Gu, Gv, Gth, Gq, s->u, s->v,
+                       s->theta, sa ? g.qv_field : s->q, sa ? g.ql_field : nullptr, s->T, scale);
+    BZ_LAUNCH_CHECK();
+    return BZ_OK;
+}
+
+static int surface_layer_filter(bz_ctx *ctx, const bz_state *s, double eps, bool init)
+{
+    const DevGrid &g = ctx->dg;
+    const SLParams S = surface_layer_params(ctx);
+    ProfileScope ps(ctx, init ? "surface_layer_filter_initialize" : "surface_layer_filter");
+    const bool sa = g.microphysics == 1;
+    const double *qv = sa ? g.qv_field : s->q, *ql = sa ? g.ql_field : nullptr;
+    if (init)
+        hipLaunchKernelGGL(k_surface_layer_filter<true>, dim3((g.Nx + 255) / 256, g.Ny), dim3(256), 0, ctx->stream, g, S, s->u, s->v, s->theta, s->q,
+                           qv, ql, s->T, eps);
+    else
+        hipLaunchKernelGGL(k_surface_layer_filter<false>, dim3((g.Nx + 255) / 256, g.Ny), dim3(256), 0, ctx->stream, g, S, s->u, s->v, s->theta, s->q,
+                           qv, ql, s->T, eps);
+    BZ_LAUNCH_CHECK();
+    return BZ_OK;
+}
+
+extern "C" int bz_surface_layer_initialize(bz_ctx *ctx, const bz_state *s)
+{
+    if (!ctx || !s) return BZ_ERR_INVALID;
+    if (!ctx->sl_on || !ctx->sl.filtered) return BZ_OK;      // nothing to initialise
+    { const int rcs = bzi_refresh_diagnostics(ctx, s, "bz_surface_layer_initialize"); if (rcs) return rcs; }
+    const int rc = surface_layer_filter(ctx, s, 0.0, true);
+    if (!rc) ctx->sl_initialized = true;
+    return rc;
+}
+
+extern "C" int bz_surface_layer_update(bz_ctx *ctx, const bz_state *s, double epsilon)
+{
+    if (!ctx || !s) return BZ_ERR_INVALID;
+    if (!ctx->sl_on || !ctx->sl.filtered) return BZ_OK;
+    if (!ctx->sl_initialized) { ctx->last_error = "bz_surface_layer_update: the filtered fields are not initialised"; return BZ_ERR_INVALID; }
+    { const int rcs = bzi_refresh_diagnostics(ctx, s, "bz_surface_layer_update"); if (rcs) return rcs; }
+    return surface_layer_filter(ctx, s, epsilon, false);
+}
+
+int bzi_surface_layer_stage(bz_ctx *ctx, const bz_state *s, int stage, double dt)
+{
+    if (!ctx->sl_on || !ctx->sl.filtered || !((ctx->sl.filter_stage_mask >> stage) & 1)) return BZ_OK;
+    return surface_layer_filter(ctx, s, dt / ctx->sl.filter_timescale, false);
+}
+
+static int surface_layer_field(bz_ctx *ctx, int which, double **f)
+{
+    if (!ctx->sl_on || !ctx->sl.filtered) { ctx->last_error = "surface layer: no filtered surface state is attached"; return BZ_ERR_INVALID; }
+    if (which < 0 || which > 4) { ctx->last_error = "surface layer: which = 0 u, 1 v, 2 theta_v, 3 theta, 4 q"; return BZ_ERR_INVALID; }
+    *f = ctx->d_sl + (size_t)(3 + which) * ctx->dg.Nx * ctx->dg.Ny;
+    return BZ_OK;
+}
+
+extern "C" int bz_surface_layer_get_filtered(bz_ctx *ctx, int which, double *host)
+{
+    if (!ctx || !host) return BZ_ERR_INVALID;
+    double *f;
+    const int rc = surface_layer_field(ctx, which, &f);
+    if (rc) return rc;
+    BZ_HIP(hipMemcpyAsync(host, f, (size_t)ctx->dg.Nx * ctx->dg.Ny * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    BZ_HIP(hipStreamSynchronize(ctx->stream));
+    return BZ_OK;
+}
+
+extern "C" int bz_surface_layer_set_filtered(bz_ctx *ctx, int which, const double *host)
+{
+    if (!ctx || !host) return BZ_ERR_INVALID;
+    double *f;
+    const int rc = surface_layer_field(ctx, which, &f);
+    if (rc) return rc;
+    BZ_HIP(hipMemcpyAsync(f, host, (size_t)ctx->dg.Nx * ctx->dg.Ny * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    BZ_HIP(hipStreamSynchronize(ctx->stream));      // the host array may go away after the call
+    ctx->sl_initialized = true;      // a restored checkpoint is not overwritten by the first step
     return BZ_OK;
 }
 
 static int bulk_flux(bz_ctx *ctx, const bz_state *s, double *Gu, double *Gv, double *Gth, double *Gq, double scale)
 {
+    if (ctx->sl_on) return surface_layer_flux(ctx, s, Gu, Gv, Gth, Gq, scale);      // replaces the constant set while attached
     const DevGrid &g = ctx->dg;
     const bz_bulk_surface_fluxes &b = ctx->bulk;
     const double Rd = g.Rd;

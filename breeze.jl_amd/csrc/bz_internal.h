@@ -468,6 +468,12 @@ struct bz_ctx {
     // BulkDrag / BulkSensibleHeatFlux / BulkVaporFlux bottom conditions (bz_set_bulk_surface_fluxes, bz_forcing.hip)
     bool has_bulk = false;
     bz_bulk_surface_fluxes bulk;
+    bool bulk_const_on = false;       // the constant-coefficient set is attached (has_bulk = bulk_const_on || sl_on: every tier selection reads has_bulk)
+    // wind- and stability-dependent bulk fluxes on a filtered surface state (bz_set_surface_layer, bz_forcing.hip); replaces the constant set while attached
+    bool sl_on = false;
+    bz_surface_layer sl;              // (the host pointers inside are not kept: the arrays were copied into d_sl)
+    double *d_sl = nullptr;           // [T0 drag, T0 heat, T0 vapour, u^, v^, theta_v^, theta^, q^] (Ny x Nx) each
+    bool sl_initialized = false;
     // user tracers (bz_set_tracers, bz_tracers.hip)
     int n_tracers = 0;
     bz_tracer_fields tracers[BZ_MAX_TRACERS];
@@ -562,6 +568,7 @@ int bzi_compute_forcings(bz_ctx *ctx, const bz_state *s);      // bz_compute_for
 double *bzi_level_sum_rows(bz_ctx *ctx, long long *P);          // the array the projection + diagnosis kernel emits them into (nullptr: not applicable)
 bool bzi_level_sums_ride(const bz_ctx *ctx);
 int bzi_flux_bc(bz_ctx *ctx, const bz_state *s, double *Gu, double *Gv, double *Gth, double *Gq, double scale);
+int bzi_surface_layer_stage(bz_ctx *ctx, const bz_state *s, int stage, double dt);      // whole steps: the filter after update_state! of a stage (filter_stage_mask)
 void bzi_forcing_teardown(bz_ctx *ctx);
 int bzi_tracer_specific(bz_ctx *ctx);
 int bzi_tracer_rk3(bz_ctx *ctx, double dt, double alpha, bool first);

@@ -205,12 +205,20 @@ static void level_sums_open(bz_ctx *ctx)
     (void)bzi_level_sum_rows(ctx, &P);      // allocated here: not inside a region a graph records
 }
 
+// initialize!(model) of a filtered surface state that nobody initialised or set: before the first step, outside any recorded region
+static int surface_layer_first_step(bz_ctx *ctx, const bz_state *s)
+{
+    if (!ctx->sl_on || !ctx->sl.filtered || ctx->sl_initialized) return BZ_OK;
+    return bz_surface_layer_initialize(ctx, s);
+}
+
 extern "C" int bz_time_step_anelastic(bz_ctx *ctx, const bz_state *s, const bz_prognostic *U0,
                                       const bz_prognostic *G, double dt)
 {
     if (!ctx || !s || !U0 || !G) return BZ_ERR_INVALID;
     level_sums_open(ctx);
     int rc = bzi_scan_moisture(ctx, s);
+    if (!rc) rc = surface_layer_first_step(ctx, s);
     if (!rc) rc = one_anelastic_step(ctx, s, U0, G, dt, true);
     ctx->lsum_fresh = false;
     return rc;
@@ -230,6 +238,7 @@ extern "C" int bz_time_steps_anelastic(bz_ctx *ctx, const bz_state *s, const bz_
     if (!ctx || !s || !U0 || !G || n < 0) return BZ_ERR_INVALID;
     level_sums_open(ctx);
     if (n > 0) { const int rc = bzi_scan_moisture(ctx, s); if (rc) return rc; }
+    if (n > 0) { const int rc = surface_layer_first_step(ctx, s); if (rc) return rc; }
     for (int it = 0; it < n; ++it) {
         const int rc = one_anelastic_step(ctx, s, U0, G, dt, it == n - 1 && diagnose_last);
         if (rc) { ctx->lsum_fresh = false; return rc; }
@@ -413,6 +422,7 @@ static int anelastic_step_body(bz_ctx *ctx, const bz_state *s, const bz_prognost
             if ((rc = bzi_project_diagnose(ctx, s, alpha * dt, nullptr, nullptr, G, stage == 2, nullptr, nullptr, ride))) return rc;
             ctx->lsum_fresh = ride;
             if ((rc = bzi_tracer_specific(ctx))) return rc;
+            if ((rc = bzi_surface_layer_stage(ctx, s, stage, dt))) return rc;      // update_boundary_conditions! of the stage's update_state!
         }
         ctx->lsum_step_last = ctx->lsum_fresh;
         ctx->G_is_predictor = true;
@@ -432,6 +442,7 @@ static int anelastic_step_body(bz_ctx *ctx, const bz_state *s, const bz_prognost
             if ((rc = bzi_poisson_from_momentum(ctx, s, alpha * dt, nullptr))) return rc;
             if ((rc = bzi_project_diagnose(ctx, s, alpha * dt))) return rc;
             if ((rc = bzi_tracer_specific(ctx))) return rc;
+            if ((rc = bzi_surface_layer_stage(ctx, s, stage, dt))) return rc;
             if ((rc = bz_compute_tendencies(ctx, s, G))) return rc;
         }
         // microphysics_model_update!(model.microphysics, model) closes the step (ssp_runge_kutta_3.jl:262-263)
@@ -447,6 +458,7 @@ static int anelastic_step_body(bz_ctx *ctx, const bz_state *s, const bz_prognost
         if ((rc = bz_compute_pressure_correction(ctx, s, alpha * dt))) return rc;    // :232,246,260
         if ((rc = bz_make_pressure_correction(ctx, s, alpha * dt))) return rc;       // :233,247,261
         if ((rc = bz_update_state(ctx, s, G, 1))) return rc;                         // :236,250,270
+        if ((rc = bzi_surface_layer_stage(ctx, s, stage, dt))) return rc;
     }
     if (ctx->dg.microphysics == 2 && (rc = bzi_kessler_update(ctx, s, G, dt))) return rc;
     return BZ_OK;

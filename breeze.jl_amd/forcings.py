@@ -90,27 +90,131 @@ class FrictionVelocityDrag:
         self.ρ0, self.ustar, self.epsilon = float(ρ0), float(ustar), float(epsilon)
 
 
-class BulkDrag:
-    """BulkDrag(; coefficient = 1e-3, gustiness = 0, surface_temperature = nothing) (src/BoundaryConditions/bulk_drag.jl:60-84);
-    without a surface temperature the anelastic default Π₀ θ₀ of the reference state is used
-    (src/AnelasticEquations/anelastic_dynamics.jl:99-105)."""
+# default neutral polynomials (a₀, a₁, a₂) of Large & Yeager (2009) (polynomial_bulk_coefficient.jl:8-10)
+default_neutral_drag_polynomial = (0.142, 0.076, 2.7)
+default_neutral_sensible_heat_polynomial = (0.128, 0.068, 2.43)
+default_neutral_latent_heat_polynomial = (0.120, 0.070, 2.55)
 
-    def __init__(self, coefficient=1e-3, gustiness=0.0, surface_temperature=None):
-        self.coefficient, self.gustiness, self.surface_temperature = float(coefficient), float(gustiness), surface_temperature
+
+class StabilityFunctionParameters:
+    """StabilityFunctionParameters(; γᴰ = 19.3, γᵀ = 11.6, a = 1, b = 2/3, c = 5, d = 0.35) (polynomial_bulk_coefficient.jl:56-64):
+    Hogström (1996) unstable, Beljaars & Holtslag (1991) stable Ψ functions."""
+
+    def __init__(self, γᴰ=19.3, γᵀ=11.6, a=1, b=2 / 3, c=5, d=0.35):
+        self.γᴰ, self.γᵀ, self.a, self.b, self.c, self.d = (float(x) for x in (γᴰ, γᵀ, a, b, c, d))
+
+    def values(self):
+        return (self.γᴰ, self.γᵀ, self.a, self.b, self.c, self.d)
+
+
+class RichardsonNumberMapping:
+    """RichardsonNumberMapping(; ...) (polynomial_bulk_coefficient.jl:135-152): Li et al. (2010) regression coefficients of the
+    Ri_B → ζ mapping with the reference's defaults; its keywords aᵘ₁₁, bʷ₂₂, ... are spelled au11, bw22, ... (subscript digits are not
+    Python identifier characters)."""
+
+    def __init__(self, stable_unstable_transition=0, strongly_stable_transition=0.2,
+                 au11=0.0450, bu11=0.0030, bu12=0.0059, au21=-0.0828, au22=0.8845, bu31=0.1739, bu32=-0.9213, bu33=-0.1057,
+                 aw11=0.5738, aw12=-0.4399, aw21=-4.901, aw22=52.50, bw11=-0.0539, bw12=1.540, bw21=-0.6690, bw22=-3.282,
+                 as11=0.7529, as21=14.94, bs11=0.1569, bs21=-0.3091, bs22=-1.303):
+        kw = dict(locals())
+        kw.pop("self")
+        for k, v in kw.items():
+            setattr(self, k, float(v))
+
+    def values(self):
+        return tuple(getattr(self, n) for n in _lib._MAPPING_FIELDS)
+
+
+class FittedStabilityFunction:
+    """FittedStabilityFunction(scalar_roughness_length; richardson_number_mapping, stability_function_parameters)
+    (polynomial_bulk_coefficient.jl:204-210)."""
+
+    def __init__(self, scalar_roughness_length, richardson_number_mapping=None, stability_function_parameters=None):
+        self.scalar_roughness_length = float(scalar_roughness_length)
+        self.richardson_number_mapping = richardson_number_mapping or RichardsonNumberMapping()
+        self.stability_function_parameters = stability_function_parameters or StabilityFunctionParameters()
+
+
+_DEFAULT_STABILITY = object()
+
+
+class PolynomialCoefficient:
+    """PolynomialCoefficient(; polynomial = nothing, roughness_length = 1.5e-4, minimum_wind_speed = 0.1, stability_function =
+    FittedStabilityFunction(roughness_length / 7.3), surface = PlanarLiquidSurface()) (polynomial_bulk_coefficient.jl:466-481).
+    polynomial=None: the condition it is attached to picks its Large & Yeager polynomial; stability_function=None: no correction."""
+
+    def __init__(self, polynomial=None, roughness_length=1.5e-4, minimum_wind_speed=0.1, stability_function=_DEFAULT_STABILITY,
+                 surface=None, transfer_type=None):
+        if surface is not None and str(surface) not in ("PlanarLiquidSurface", "PlanarLiquidSurface()"):
+            raise NotImplementedError("PolynomialCoefficient: surface = PlanarLiquidSurface() is implemented")
+        self.polynomial = None if polynomial is None else tuple(float(a) for a in polynomial)
+        if self.polynomial is not None and len(self.polynomial) != 3:
+            raise ValueError("polynomial = (a₀, a₁, a₂)")
+        self.roughness_length, self.minimum_wind_speed = float(roughness_length), float(minimum_wind_speed)
+        if stability_function is _DEFAULT_STABILITY:
+            stability_function = FittedStabilityFunction(self.roughness_length / 7.3)
+        if stability_function is not None and not isinstance(stability_function, FittedStabilityFunction):
+            raise NotImplementedError("stability_function: FittedStabilityFunction or None")
+        self.stability_function, self.transfer_type = stability_function, transfer_type
+
+
+class FilteredSurfaceVelocities:
+    """FilteredSurfaceVelocities(grid; height = nothing, filter_timescale = Inf) (filtered_surface_state.jl:66-73): exponentially
+    time-filtered û, v̂, θ̂ᵥ (and, per condition, θ̂ / q̂) of the first level; the 2-D fields live in the library's context
+    (model.filtered_surface_field(name) / model.set_filtered_surface_field(name, array)).  update_stages: after which stages'
+    update_state! of a whole step the filter advances with ε = Δt / τ.  The default (1, 3) is a READING of the reference's
+    (clock.iteration, clock.stage) key (its second stage does not tick the clock, ssp_runge_kutta_3.jl:249); a host that knows its
+    clock passes what the clock says."""
+
+    def __init__(self, grid=None, height=None, filter_timescale=float("inf"), update_stages=(1, 3)):
+        self.grid, self.height, self.filter_timescale = grid, height, float(filter_timescale)
+        self.update_stages = tuple(int(s) for s in update_stages)
+        if any(s not in (1, 2, 3) for s in self.update_stages):
+            raise ValueError("update_stages names stages 1, 2, 3")
+
+    @property
+    def stage_mask(self):
+        return sum(1 << (s - 1) for s in set(self.update_stages))
+
+
+def _coefficient(c):
+    return c if isinstance(c, PolynomialCoefficient) else float(c)
+
+
+def _surface_temperature(T0):
+    return T0 if (T0 is None or callable(T0) or np.ndim(T0) > 0) else float(T0)
+
+
+class BulkDrag:
+    """BulkDrag(; coefficient = 1e-3, gustiness = 0, surface_temperature = nothing, filtered_velocities = nothing)
+    (src/BoundaryConditions/bulk_drag.jl:60-84); without a surface temperature the anelastic default Π₀ θ₀ of the reference state is
+    used (src/AnelasticEquations/anelastic_dynamics.jl:99-105).  coefficient: a number or a PolynomialCoefficient;
+    surface_temperature: a number, an (Ny, Nx) array or T₀(x) / T₀(x, y) evaluated at the cell centres."""
+    default_polynomial, transfer_type = default_neutral_drag_polynomial, "momentum"
+
+    def __init__(self, coefficient=1e-3, gustiness=0.0, surface_temperature=None, filtered_velocities=None):
+        if isinstance(coefficient, PolynomialCoefficient) and surface_temperature is None:      # bulk_drag.jl:78-80
+            raise ValueError("surface_temperature keyword argument must be provided when configuring BulkDrag with a PolynomialCoefficient")
+        self.coefficient, self.gustiness = _coefficient(coefficient), float(gustiness)
+        self.surface_temperature, self.filtered_velocities = _surface_temperature(surface_temperature), filtered_velocities
 
 
 class BulkSensibleHeatFlux:
-    """BulkSensibleHeatFlux(; coefficient, gustiness = 0, surface_temperature) (bulk_scalar_fluxes.jl:53-56)."""
+    """BulkSensibleHeatFlux(; coefficient, gustiness = 0, surface_temperature, filtered_velocities = nothing) (bulk_scalar_fluxes.jl:53-56)."""
+    default_polynomial, transfer_type = default_neutral_sensible_heat_polynomial, "scalar"
 
-    def __init__(self, coefficient, surface_temperature, gustiness=0.0):
-        self.coefficient, self.gustiness, self.surface_temperature = float(coefficient), float(gustiness), float(surface_temperature)
+    def __init__(self, coefficient, surface_temperature, gustiness=0.0, filtered_velocities=None):
+        self.coefficient, self.gustiness = _coefficient(coefficient), float(gustiness)
+        self.surface_temperature, self.filtered_velocities = _surface_temperature(surface_temperature), filtered_velocities
 
 
 class BulkVaporFlux:
-    """BulkVaporFlux(; coefficient, gustiness = 0, surface_temperature) (bulk_scalar_fluxes.jl:172-176)."""
+    """BulkVaporFlux(; coefficient, gustiness = 0, surface_temperature, filtered_velocities = nothing) (bulk_scalar_fluxes.jl:172-176)."""
+    default_polynomial, transfer_type = default_neutral_latent_heat_polynomial, "scalar"
 
-    def __init__(self, coefficient, surface_temperature, gustiness=0.0):
-        self.coefficient, self.gustiness, self.surface_temperature = float(coefficient), float(gustiness), float(surface_temperature)
+    def __init__(self, coefficient, surface_temperature, gustiness=0.0, filtered_velocities=None):
+        self.coefficient, self.gustiness = _coefficient(coefficient), float(gustiness)
+        self.surface_temperature, self.filtered_velocities = _surface_temperature(surface_temperature), filtered_velocities
 
 
 class FluxBoundaryCondition:
@@ -320,6 +424,8 @@ def materialize_forcings(grid, coriolis, forcing, boundary_conditions, T=None):
 def materialize_bulk_fluxes(boundary_conditions, reference_state, constants, T=None):
     """-> bz_bulk_surface_fluxes or None.  BulkDrag belongs on ρu / ρv (one coefficient for both), BulkSensibleHeatFlux on ρθ,
     BulkVaporFlux on the moisture density; anything else raises like the reference's regularization does."""
+    if needs_surface_layer(boundary_conditions):
+        return None                       # materialize_surface_layer
     B, found, drag = (T or _lib.types(8)).bz_bulk_surface_fluxes(), False, None
     for name, bcs in (boundary_conditions or {}).items():
         k = _key(name)
@@ -363,3 +469,129 @@ def materialize_bulk_fluxes(boundary_conditions, reference_state, constants, T=N
     B.energy_reference_temperature = c.energy_reference_temperature
     B.triple_point_temperature, B.triple_point_pressure = c.triple_point_temperature, c.triple_point_pressure
     return B
+
+
+# ---- PolynomialCoefficient / FilteredSurfaceVelocities / T₀(x, y): bz_set_surface_layer -------------------------------------------------
+def _bulk_conditions(boundary_conditions):
+    for name, bcs in (boundary_conditions or {}).items():
+        bottom = bcs.bottom if isinstance(bcs, FieldBoundaryConditions) else bcs
+        cond = bottom.condition if isinstance(bottom, FluxBoundaryCondition) else bottom
+        if isinstance(cond, (BulkDrag, BulkSensibleHeatFlux, BulkVaporFlux)):
+            yield _key(name), cond
+
+
+def needs_surface_layer(boundary_conditions):
+    """True when a bulk condition carries what the constant-coefficient entry point cannot: a PolynomialCoefficient, a surface
+    temperature that varies in the horizontal, or FilteredSurfaceVelocities."""
+    return any(isinstance(c.coefficient, PolynomialCoefficient) or c.filtered_velocities is not None or
+               callable(c.surface_temperature) or np.ndim(c.surface_temperature) > 0 for _, c in _bulk_conditions(boundary_conditions))
+
+
+def surface_temperature_field(grid, T0):
+    """A callable T₀(x) / T₀(x, y) evaluated at the cell centres, or an (Ny, Nx) array -> (Ny, Nx) Float64 array
+    (materialize_surface_field: the reference sets a Center, Center, Nothing field from the function)."""
+    if callable(T0):
+        import inspect
+        nargs = len(inspect.signature(T0).parameters)
+        x, y = np.asarray(grid.xᶜ, dtype=np.float64)[None, :], np.asarray(grid.yᶜ, dtype=np.float64)[:, None]
+        if nargs == 1:
+            one = grid.xᶜ if grid.Nx > 1 or grid.Ny == 1 else grid.yᶜ
+            v = np.array([float(T0(a)) for a in one], dtype=np.float64)
+            a = np.broadcast_to(v[None, :] if one is grid.xᶜ else v[:, None], (grid.Ny, grid.Nx))
+        elif nargs == 2:
+            a = np.array([[float(T0(float(xi), float(yj))) for xi in x[0]] for yj in y[:, 0]], dtype=np.float64)
+        else:
+            raise ValueError("surface_temperature: T₀(x) or T₀(x, y)")
+    else:
+        a = np.asarray(T0, dtype=np.float64)
+    if a.shape != (grid.Ny, grid.Nx):
+        raise ValueError(f"surface_temperature has shape {a.shape}, expected {(grid.Ny, grid.Nx)}")
+    return np.ascontiguousarray(a, dtype=np.float64)
+
+
+def fill_polynomial_record(P, coef, cond):
+    """bz_polynomial_coefficient from a PolynomialCoefficient attached to `cond` (defaults chosen by the condition's type:
+    fill_polynomial, polynomial_bulk_coefficient.jl:714-721)."""
+    P.a0, P.a1, P.a2 = coef.polynomial if coef.polynomial is not None else cond.default_polynomial
+    P.roughness_length, P.minimum_wind_speed = coef.roughness_length, coef.minimum_wind_speed
+    sf = coef.stability_function
+    P.stability = 0 if sf is None else 1
+    sf = sf or FittedStabilityFunction(coef.roughness_length / 7.3)      # (unused numbers of a switched-off correction)
+    P.scalar_roughness_length = sf.scalar_roughness_length
+    for n, v in zip(_lib._MAPPING_FIELDS, sf.richardson_number_mapping.values()):
+        setattr(P, n, v)
+    for n, v in zip(_lib._PSI_FIELDS, sf.stability_function_parameters.values()):
+        setattr(P, n, v)
+    return P
+
+
+def materialize_surface_layer(grid, boundary_conditions, reference_state, constants, T=None):
+    """-> (bz_surface_layer, keepalive arrays, FilteredSurfaceVelocities or None), or (None, None, None) when the constant-coefficient
+    entry point serves every bulk condition.  Keys as materialize_bulk_fluxes: BulkDrag on ρu / ρv (one for both), BulkSensibleHeatFlux
+    on ρθ / ρe, BulkVaporFlux on the moisture density."""
+    if not needs_surface_layer(boundary_conditions):
+        return None, None, None
+    T = T or _lib.types(8)
+    L, keep, fv, seen = T.bz_surface_layer(), [], [], {}
+    for k, cond in _bulk_conditions(boundary_conditions):
+        if isinstance(cond, BulkDrag):
+            if k not in ("ρu", "ρv"):
+                raise ValueError("BulkDrag is a momentum boundary condition (ρu, ρv)")
+            slot = "drag"
+        elif isinstance(cond, BulkSensibleHeatFlux):
+            if k not in ("ρθ", "ρe"):
+                raise ValueError("BulkSensibleHeatFlux belongs on ρθ (or ρe)")
+            slot = "heat"
+        else:
+            if k not in ("ρqe", "ρqv", "ρqt"):
+                raise ValueError("BulkVaporFlux belongs on the moisture density")
+            slot = "vapor"
+        if slot in seen:
+            if slot == "drag" and _same_condition(seen[slot], cond):
+                continue
+            raise NotImplementedError("ρu and ρv share one BulkDrag" if slot == "drag" else "Cannot specify boundary conditions on both ρθ and ρe")
+        seen[slot] = cond
+        F = getattr(L, slot)
+        F.enabled, F.gustiness = 1, cond.gustiness
+        if isinstance(cond.coefficient, PolynomialCoefficient):
+            F.polynomial = 1
+            fill_polynomial_record(F.poly, cond.coefficient, cond)
+        else:
+            F.polynomial, F.coefficient = 0, cond.coefficient
+        T0 = cond.surface_temperature
+        if T0 is None:      # default_drag_surface_temperature(::AnelasticDynamics)
+            from .thermodynamics import dry_air_gas_constant
+            T0 = (reference_state.surface_pressure / reference_state.standard_pressure) ** (
+                dry_air_gas_constant(constants) / constants.dry_air_heat_capacity) * reference_state.potential_temperature
+        if callable(T0) or np.ndim(T0) > 0:
+            a = np.ascontiguousarray(surface_temperature_field(grid, T0), dtype=T.np_real)
+            keep.append(a)
+            F.surface_temperature_field = a.ctypes.data_as(C.POINTER(T.real))
+            F.surface_temperature = float(a.flat[0])
+        else:
+            F.surface_temperature = float(T0)
+        if cond.filtered_velocities is not None:
+            fv.append(cond.filtered_velocities)
+    if fv and (len(fv) != len(seen) or any(f is not fv[0] for f in fv)):
+        raise NotImplementedError("FilteredSurfaceVelocities: one filtered state shared by every bulk condition of the model")
+    L.surface_pressure, L.standard_pressure = reference_state.surface_pressure, reference_state.standard_pressure
+    c = constants
+    L.liquid_latent_heat, L.liquid_heat_capacity = c.liquid_reference_latent_heat, c.liquid_heat_capacity
+    L.energy_reference_temperature = c.energy_reference_temperature
+    L.triple_point_temperature, L.triple_point_pressure = c.triple_point_temperature, c.triple_point_pressure
+    if fv:
+        f = fv[0]
+        L.filtered, L.filter_timescale, L.filter_stage_mask = 1, f.filter_timescale, f.stage_mask
+        if f.height is not None:
+            L.filter_height_set, L.filter_height = 1, float(f.height)
+    return L, keep, (fv[0] if fv else None)
+
+
+def _same_condition(a, b):
+    """ρu and ρv carry one BulkDrag (the example assigns the same object to both)."""
+    if a is b:
+        return True
+    Ta, Tb = a.surface_temperature, b.surface_temperature
+    same_T0 = Ta is Tb or (not callable(Ta) and not callable(Tb) and np.array_equal(Ta, Tb))
+    same_C = a.coefficient is b.coefficient or (not isinstance(a.coefficient, PolynomialCoefficient) and a.coefficient == b.coefficient)
+    return bool(same_T0 and same_C and a.gustiness == b.gustiness and a.filtered_velocities is b.filtered_velocities)

@@ -434,6 +434,14 @@ class AtmosphereModel:
             if self._kessler or formulation != "LiquidIcePotentialTemperature":
                 raise NotImplementedError("bulk surface fluxes are implemented for the potential-temperature formulation without Kessler")
             self._check(lib.bz_set_bulk_surface_fluxes(self._ctx, C.byref(Bk)), "bz_set_bulk_surface_fluxes")
+        # PolynomialCoefficient / FilteredSurfaceVelocities / T₀(x, y) conditions: the surface-layer configuration (forcings.py)
+        from .forcings import materialize_surface_layer
+        Sl, self._surface_layer_keepalive, self.filtered_velocities = materialize_surface_layer(grid, boundary_conditions, ref, c, T)
+        self._surface_filter_initialized = False
+        if Sl is not None:
+            if self._kessler or formulation != "LiquidIcePotentialTemperature":
+                raise NotImplementedError("bulk surface fluxes are implemented for the potential-temperature formulation without Kessler")
+            self._check(lib.bz_set_surface_layer(self._ctx, C.byref(Sl)), "bz_set_surface_layer")
         self._state = self._make_state()
         self._U0 = self._make_prog(self.U0)
         self._G = self._make_prog(self.G)
@@ -493,6 +501,34 @@ class AtmosphereModel:
 
     def synchronize(self):
         self._check(self._lib.bz_sync(self._ctx), "bz_sync")
+
+    # -- filtered surface state (FilteredSurfaceVelocities) --------------------
+    _FILTERED = {"u": 0, "v": 1, "θᵥ": 2, "θv": 2, "theta_v": 2, "θ": 3, "theta": 3, "q": 4}
+
+    def initialize_(self):
+        """initialize!(model) (update_boundary_conditions.jl:119-122): the filtered surface fields take the current first-level values.
+        Runs by itself before the first step unless the fields were set."""
+        self._check(self._lib.bz_surface_layer_initialize(self._ctx, C.byref(self._state)), "bz_surface_layer_initialize")
+        self._surface_filter_initialized = True
+
+    def update_filtered_surface_state_(self, Δt):
+        """update!(fv, ..., Δt) of every filtered field, ε = Δt / τ (the per-operator sequence calls it at the filter's update_stages)."""
+        self._check(self._lib.bz_surface_layer_update(self._ctx, C.byref(self._state), float(Δt) / self.filtered_velocities.filter_timescale),
+                    "bz_surface_layer_update")
+
+    def filtered_surface_field(self, name):
+        """(Ny, Nx) host copy of a filtered 2-D field: "u" (x faces), "v" (y faces), "θᵥ", "θ", "q" (centres)."""
+        a = np.empty((self.grid.Ny, self.grid.Nx), dtype=self._T.np_real)
+        self._check(self._lib.bz_surface_layer_get_filtered(self._ctx, self._FILTERED[name], a.ctypes.data_as(C.POINTER(self._T.real))),
+                    "bz_surface_layer_get_filtered")
+        return a
+
+    def set_filtered_surface_field(self, name, value):
+        """set!(fv.u, ...): checkpoints and tests."""
+        a = np.ascontiguousarray(np.broadcast_to(np.asarray(value, dtype=self._T.np_real), (self.grid.Ny, self.grid.Nx)))
+        self._check(self._lib.bz_surface_layer_set_filtered(self._ctx, self._FILTERED[name], a.ctypes.data_as(C.POINTER(self._T.real))),
+                    "bz_surface_layer_set_filtered")
+        self._surface_filter_initialized = True
 
     def _refresh_diagnostics(self):
         """update_state!(model; compute_tendencies=false) after undiagnosed steps (slab models override it with the exchanging form)."""
@@ -722,17 +758,22 @@ def time_step_(model, Δt, whole_step=True):
     entry points (same kernels, used by the parity tests)."""
     if model.clock.iteration == 0:       # maybe_prepare_first_time_step!
         update_state_(model, compute_tendencies=True)
+    fv = getattr(model, "filtered_velocities", None)
+    if fv is not None and not model._surface_filter_initialized:      # initialize!(model), after set!
+        model.initialize_()
     if whole_step:
         model._check(model._lib.bz_time_step_anelastic(model._ctx, C.byref(model._state), C.byref(model._U0),
                                                        C.byref(model._G), float(Δt)), "bz_time_step_anelastic")
     else:
         store_initial_state_(model)
-        for α in (1.0, 1.0 / 4.0, 2.0 / 3.0):
+        for stage, α in enumerate((1.0, 1.0 / 4.0, 2.0 / 3.0), start=1):
             compute_flux_bc_tendencies_(model)
             ssp_rk3_substep_(model, Δt, α)
             compute_pressure_correction_(model, α * Δt)
             make_pressure_correction_(model, α * Δt)
             update_state_(model, compute_tendencies=True)
+            if fv is not None and stage in fv.update_stages:      # update_boundary_conditions! inside update_state!
+                model.update_filtered_surface_state_(Δt)
         if getattr(model, "_kessler", False):
             from .microphysics import microphysics_model_update_
             microphysics_model_update_(model.microphysics, model, Δt=Δt)
@@ -748,6 +789,8 @@ def many_time_steps_(model, Δt, n, diagnose_last=True):
         return
     if model.clock.iteration == 0:       # maybe_prepare_first_time_step!
         update_state_(model, compute_tendencies=True)
+    if getattr(model, "filtered_velocities", None) is not None and not model._surface_filter_initialized:
+        model.initialize_()
     model._check(model._lib.bz_time_steps_anelastic(model._ctx, C.byref(model._state), C.byref(model._U0), C.byref(model._G),
                                                     float(Δt), n, 1 if diagnose_last else 0), "bz_time_steps_anelastic")
     model.clock.time += n * Δt

@@ -600,7 +600,7 @@ int bz_compute_flux_bc_tendencies(bz_ctx *ctx, const bz_state *s, const bz_progn
  * with U~ = sqrt(U^2 + gustiness^2), U^2 interpolated to the flux location (BoundaryConditions.jl:64-85), rho0 = p0 / (R^d T0)
  * (src/Thermodynamics/reference_states.jl:73-76), theta0 = T0 / (p0/p_st)^(R^d/c_pd).  A coefficient <= 0 switches that
  * condition off.  Applied by bz_compute_flux_bc_tendencies (and inside bz_time_step_anelastic) next to the constant fluxes of
- * bz_column_forcings.  PolynomialCoefficient and FilteredSurfaceVelocities are not implemented. */
+ * bz_column_forcings.  PolynomialCoefficient and FilteredSurfaceVelocities: bz_set_surface_layer below. */
 typedef struct bz_bulk_surface_fluxes {
     double drag_coefficient, drag_gustiness, drag_surface_temperature;
     double heat_coefficient, heat_gustiness, heat_surface_temperature;
@@ -610,6 +610,68 @@ typedef struct bz_bulk_surface_fluxes {
     double liquid_latent_heat, liquid_heat_capacity, energy_reference_temperature, triple_point_temperature, triple_point_pressure;
 } bz_bulk_surface_fluxes;
 int bz_set_bulk_surface_fluxes(bz_ctx *ctx, const bz_bulk_surface_fluxes *fluxes);      /* NULL detaches */
+
+/* ---- wind- and stability-dependent bulk fluxes on a filtered surface state (examples/prescribed_sea_surface_temperature.jl:39-72) ----
+ * The same three bottom conditions with, per condition, either a constant coefficient or a PolynomialCoefficient
+ * (src/BoundaryConditions/polynomial_bulk_coefficient.jl), a surface temperature that is a number or a (Ny x Nx) centre array, and
+ * optionally FilteredSurfaceVelocities (filtered_surface_state.jl).  Per surface cell and condition:
+ *   T0 = surface temperature at index (i, j) (the drag at an x or y face reads the centre array at its own index: surface_value(i, j, .)),
+ *   rho0 = p0 / (R^d T0), theta0 = T0 / (p0/p_st)^(R^d/c_pd), q^v+ = p^v+(T0) / (rho0 R^v T0)           (per cell)
+ *   U~ = sqrt(U^2 + gustiness^2) with U^2 at the flux's own location multiplies the flux (BoundaryConditions.jl:64-124),
+ *   C = polynomial: C10 (ln(10/l) / ln(h/l))^2 [x stability factor], C10 = (a0 + a1 Us + a2 / Us) 1e-3, Us = max(U, U_min), where U is
+ *       the un-gusted wind speed at the CENTRE (i, j) for all three conditions (bulk_coefficient, :687-707) and h the first centre height;
+ *       stability (FittedStabilityFunction): Ri_B from theta_v of the first cell, theta_v0 = T0 (1 + delta q^v+_t(T0, p0)) (the
+ *       pressure-based saturation_total_specific_moisture) and the literal g = 9.81 of bulk_richardson_number; Li et al. (2010) three-regime
+ *       zeta mapping, Hogstrom / Beljaars-Holtslag Psi functions, momentum or scalar correction factor.  Every branch is a select.
+ * With filtering every velocity, theta_v, theta and the vapour flux's moisture come from context-owned 2-D fields
+ *   f^ <- (f^ + eps f) / (1 + eps)   (u^ at x faces, v^ at y faces, theta_v^, theta^, q^ at centres; first-level values; the moisture is
+ *   the specific PROGNOSTIC moisture s->q (update_boundary_conditions.jl:47), while the unfiltered vapour flux reads q^v),
+ * whose neighbour reads wrap periodically and collapse onto the cell in a Flat direction.
+ * One launch per flux evaluation over the Nx x Ny surface, one launch per filter update; no synchronisation, no allocation per call;
+ * captured steps (bz_graph_enable) replay both.  The lean seam never carries these fluxes: with a configuration attached
+ * bz_time_step_anelastic / bz_time_steps_anelastic take the tiers that diagnose after every stage (every step of an n-step call),
+ * so the filter always reads current first-level diagnostics.
+ * Inside the library-owned whole steps the filter advances with eps = dt / filter_timescale after update_state! of the stages named by
+ * filter_stage_mask (bit 0: first stage ... bit 2: third stage): the reference advances it once per new (clock.iteration, clock.stage)
+ * key, which is the host clock's business.  The per-operator sequence calls bz_surface_layer_update itself.
+ * BZ_ERR_UNSUPPORTED (with bz_last_error naming the reason): compressible, StaticEnergy and Kessler contexts, y-slab contexts, a filter
+ * reference height other than the first cell centre (filter_height_set != 0), filtering on a Bounded x or y.  PlanarIceSurface: not built. */
+typedef struct bz_polynomial_coefficient {
+    double a0, a1, a2;                       /* polynomial (the host fills the defaults per condition type) */
+    double roughness_length, minimum_wind_speed;
+    int32_t stability, reserved;             /* 1: FittedStabilityFunction, 0: stability_function = nothing */
+    double scalar_roughness_length;
+    /* RichardsonNumberMapping, in the reference's field order */
+    double stable_unstable_transition, strongly_stable_transition;
+    double au11, bu11, bu12, au21, au22, bu31, bu32, bu33;
+    double aw11, aw12, aw21, aw22, bw11, bw12, bw21, bw22;
+    double as11, as21, bs11, bs21, bs22;
+    /* StabilityFunctionParameters */
+    double gamma_d, gamma_t, psi_a, psi_b, psi_c, psi_d;
+} bz_polynomial_coefficient;
+typedef struct bz_surface_flux {
+    int32_t enabled, polynomial;             /* polynomial = 0: `coefficient` is used */
+    double coefficient, gustiness;
+    double surface_temperature;              /* used when the field is NULL */
+    const double *surface_temperature_field; /* HOST (Ny x Nx), row j column i; copied by the call */
+    bz_polynomial_coefficient poly;
+} bz_surface_flux;
+typedef struct bz_surface_layer {
+    bz_surface_flux drag, heat, vapor;
+    double surface_pressure, standard_pressure;
+    double liquid_latent_heat, liquid_heat_capacity, energy_reference_temperature, triple_point_temperature, triple_point_pressure;
+    int32_t filtered, filter_height_set;
+    double filter_height, filter_timescale;
+    int32_t filter_stage_mask, reserved;
+} bz_surface_layer;
+int bz_set_surface_layer(bz_ctx *ctx, const bz_surface_layer *layer);      /* NULL detaches and frees the 2-D fields */
+/* initialize!(model): the filtered fields take the first-level values of `s` (diagnostics current) */
+int bz_surface_layer_initialize(bz_ctx *ctx, const bz_state *s);
+/* update!(fv, ..., dt) with epsilon = dt / tau */
+int bz_surface_layer_update(bz_ctx *ctx, const bz_state *s, double epsilon);
+/* the filtered 2-D fields as HOST (Ny x Nx) arrays; which = 0 u^, 1 v^, 2 theta_v^, 3 theta^, 4 q^.  get synchronises. */
+int bz_surface_layer_get_filtered(bz_ctx *ctx, int which, double *host);
+int bz_surface_layer_set_filtered(bz_ctx *ctx, int which, const double *host);
 
 /* ---- user tracers of the anelastic model: AtmosphereModel(grid; tracers = (:a, :b)) ----
  * density = model.tracers.c (prognostic rho c), specific = c = rho c / rho_r (the reference converts in place around the tendency

@@ -232,6 +232,100 @@ function attach_relaxation!(ctx, columns::NamedTuple, specific = ())
                                "bz_set_relaxation", ctx)
 end
 
+# ---- wind- and stability-dependent bulk fluxes on a filtered surface state (include/breeze_hip.h: bz_surface_layer) ----
+# The structs mirror the header field by field.  NOTHING in this section has been run: no Julia is installed where this library is built.
+struct BzPolynomialCoefficient
+    a0::Cdouble; a1::Cdouble; a2::Cdouble
+    roughness_length::Cdouble; minimum_wind_speed::Cdouble
+    stability::Int32; reserved::Int32
+    scalar_roughness_length::Cdouble
+    stable_unstable_transition::Cdouble; strongly_stable_transition::Cdouble
+    au11::Cdouble; bu11::Cdouble; bu12::Cdouble; au21::Cdouble; au22::Cdouble; bu31::Cdouble; bu32::Cdouble; bu33::Cdouble
+    aw11::Cdouble; aw12::Cdouble; aw21::Cdouble; aw22::Cdouble; bw11::Cdouble; bw12::Cdouble; bw21::Cdouble; bw22::Cdouble
+    as11::Cdouble; as21::Cdouble; bs11::Cdouble; bs21::Cdouble; bs22::Cdouble
+    gamma_d::Cdouble; gamma_t::Cdouble; psi_a::Cdouble; psi_b::Cdouble; psi_c::Cdouble; psi_d::Cdouble
+end
+
+struct BzSurfaceFlux
+    enabled::Int32; polynomial::Int32
+    coefficient::Cdouble; gustiness::Cdouble
+    surface_temperature::Cdouble
+    surface_temperature_field::Ptr{Cdouble}      # HOST (Ny × Nx), copied by the call
+    poly::BzPolynomialCoefficient
+end
+
+struct BzSurfaceLayer
+    drag::BzSurfaceFlux; heat::BzSurfaceFlux; vapor::BzSurfaceFlux
+    surface_pressure::Cdouble; standard_pressure::Cdouble
+    liquid_latent_heat::Cdouble; liquid_heat_capacity::Cdouble; energy_reference_temperature::Cdouble
+    triple_point_temperature::Cdouble; triple_point_pressure::Cdouble
+    filtered::Int32; filter_height_set::Int32
+    filter_height::Cdouble; filter_timescale::Cdouble
+    filter_stage_mask::Int32; reserved::Int32
+end
+
+"""
+`bz_polynomial_coefficient` of a materialized `PolynomialCoefficient` (polynomial filled by the condition's type).
+"""
+function polynomial_record(coef)
+    sf = coef.stability_function
+    on = !isnothing(sf)
+    sf = on ? sf : Breeze.BoundaryConditions.FittedStabilityFunction(coef.roughness_length / 7.3)
+    m, p = sf.richardson_number_mapping, sf.stability_function_parameters
+    a₀, a₁, a₂ = coef.polynomial
+    BzPolynomialCoefficient(a₀, a₁, a₂, coef.roughness_length, coef.minimum_wind_speed, Int32(on), Int32(0), sf.scalar_roughness_length,
+                            m.stable_unstable_transition, m.strongly_stable_transition,
+                            m.aᵘ₁₁, m.bᵘ₁₁, m.bᵘ₁₂, m.aᵘ₂₁, m.aᵘ₂₂, m.bᵘ₃₁, m.bᵘ₃₂, m.bᵘ₃₃,
+                            m.aʷ₁₁, m.aʷ₁₂, m.aʷ₂₁, m.aʷ₂₂, m.bʷ₁₁, m.bʷ₁₂, m.bʷ₂₁, m.bʷ₂₂,
+                            m.aˢ₁₁, m.aˢ₂₁, m.bˢ₁₁, m.bˢ₂₁, m.bˢ₂₂, p.γᴰ, p.γᵀ, p.a, p.b, p.c, p.d)
+end
+
+const NO_POLYNOMIAL = BzPolynomialCoefficient(ntuple(_ -> 0.0, 5)..., Int32(0), Int32(0), ntuple(_ -> 0.0, 30)...)
+const NO_SURFACE_FLUX = BzSurfaceFlux(Int32(0), Int32(0), 0.0, 0.0, 0.0, Ptr{Cdouble}(C_NULL), NO_POLYNOMIAL)
+
+"""
+One bulk condition (`BulkDragFunction` / `BulkSensibleHeatFluxFunction` / `BulkVaporFluxFunction`, materialized) as a `BzSurfaceFlux`;
+`T₀host` is `nothing` or the host copy `Array(interior(T₀, :, :, 1))` (x fastest), kept alive by the caller for the call.
+"""
+function surface_flux_record(bf, T₀host)
+    C = bf.coefficient
+    poly = C isa Number ? NO_POLYNOMIAL : polynomial_record(C)
+    T₀ = isnothing(T₀host) ? Cdouble(bf.surface_temperature) : Cdouble(first(T₀host))
+    BzSurfaceFlux(Int32(1), Int32(!(C isa Number)), C isa Number ? Cdouble(C) : 0.0, Cdouble(bf.gustiness), T₀,
+                  isnothing(T₀host) ? Ptr{Cdouble}(C_NULL) : pointer(T₀host), poly)
+end
+
+"""
+Attach the surface layer: `conditions = (; drag, heat, vapor)` of materialized condition functions (or `nothing`), `T₀ = (; drag, heat, vapor)`
+host arrays or `nothing`, `fv` the shared `FilteredSurfaceVelocities` or `nothing`, `stage_mask` what the model's clock does: bit s - 1 set
+when `update_state!` of stage s sees a new `(clock.iteration, clock.stage)` key.
+"""
+function attach_surface_layer!(ctx, conditions::NamedTuple, T₀::NamedTuple, p₀, pˢᵗ, constants, fv = nothing, stage_mask = 0b101)
+    rec(name) = isnothing(conditions[name]) ? NO_SURFACE_FLUX : surface_flux_record(conditions[name], T₀[name])
+    liq = constants.liquid
+    L = BzSurfaceLayer(rec(:drag), rec(:heat), rec(:vapor), p₀, pˢᵗ, liq.reference_latent_heat, liq.heat_capacity,
+                       constants.energy_reference_temperature, constants.triple_point_temperature, constants.triple_point_pressure,
+                       Int32(!isnothing(fv)), Int32(!isnothing(fv) && !isnothing(fv.height)),
+                       (isnothing(fv) || isnothing(fv.height)) ? 0.0 : Cdouble(fv.height), isnothing(fv) ? Inf : Cdouble(fv.filter_timescale),
+                       Int32(stage_mask), Int32(0))
+    GC.@preserve T₀ check(ccall((:bz_set_surface_layer, libbreeze_hip), Cint, (Ptr{Cvoid}, Ref{BzSurfaceLayer}), ctx, L), "bz_set_surface_layer", ctx)
+end
+
+detach_surface_layer!(ctx) =
+    check(ccall((:bz_set_surface_layer, libbreeze_hip), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), ctx, C_NULL), "bz_set_surface_layer", ctx)
+
+# initialize!(model) / update!(fv, …, Δt) with ϵ = Δt / τ; `s` is the Ref{BzState} of the model
+initialize_surface_layer!(ctx, s) =
+    check(ccall((:bz_surface_layer_initialize, libbreeze_hip), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), ctx, s), "bz_surface_layer_initialize", ctx)
+update_surface_layer!(ctx, s, ϵ) =
+    check(ccall((:bz_surface_layer_update, libbreeze_hip), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Cdouble), ctx, s, ϵ), "bz_surface_layer_update", ctx)
+
+# the filtered 2-D fields as host (Nx, Ny) arrays (x fastest); which = 0 û, 1 v̂, 2 θ̂ᵥ, 3 θ̂, 4 q̂
+get_filtered_surface_field!(host::Array{Float64}, ctx, which) =
+    check(ccall((:bz_surface_layer_get_filtered, libbreeze_hip), Cint, (Ptr{Cvoid}, Cint, Ptr{Cdouble}), ctx, which, host), "bz_surface_layer_get_filtered", ctx)
+set_filtered_surface_field!(ctx, which, host::Array{Float64}) =
+    check(ccall((:bz_surface_layer_set_filtered, libbreeze_hip), Cint, (Ptr{Cvoid}, Cint, Ptr{Cdouble}), ctx, which, host), "bz_surface_layer_set_filtered", ctx)
+
 """
 `Forcing(f(x, y, z, t))` / `Forcing(field)` on θ / e (specific = true) or ρθ / ρe: `F` is a CenterField the extension fills from the forcing
 (and refreshes from a callback when it depends on time); the library reads it at every tendency evaluation.
