@@ -1959,7 +1959,7 @@ extern "C" int bz_compute_slow_tendencies(bz_ctx *ctx, const bz_compressible_sta
         if (rc) return rc;
         rc = bzi_v_tendency_lds(ctx, &a, &Ga);
         if (rc) return rc;
-        rc = bzi_w_tendency_ring(ctx, &a, &Ga, nullptr, nullptr, 1);
+        rc = bzi_w_tendency_lds(ctx, &a, &Ga, nullptr, nullptr, 1);
         if (rc) return rc;
     }
     if ((rc = launch_scalar_rho3d(ctx, "density+potential_temperature_tendency", G->rho_theta, G->rho_d, s->rho_d, s->u, s->v,

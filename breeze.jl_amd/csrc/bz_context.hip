@@ -48,8 +48,6 @@ void bzi_read_tuning(bz_tuning &t)
     auto num = [](const char *n, int d) { const char *e = getenv(n); return e ? atoi(e) : d; };
     t.no_fused = on("BZ_NO_FUSED");
     t.no_fuse_rk = on("BZ_NO_FUSE_RK");
-    t.no_tend_lds = on("BZ_NO_TEND_LDS");
-    t.tend_gen = num("BZ_TEND_GEN", 0);
     t.no_lean = on("BZ_NO_LEAN");
     t.no_xcd = on("BZ_NO_XCD");
     t.no_k6_stored = on("BZ_NO_K6_STORED");
@@ -370,15 +368,13 @@ int bzi_create(bz_ctx **out, const bz_grid *grid, const bz_constants *constants,
     // sequence takes its slow tendencies from the generic kernels and is otherwise independent of the advection order)
 #endif
     if (slab_mode && (Ny < grid->Hy || Nx < 2 * grid->Hx)) { delete ctx; return BZ_ERR_UNSUPPORTED; }
-    if (ctx->tune.tend_gen) ctx->tend_gen = ctx->tune.tend_gen;
     ctx->fuse_rk = !ctx->tune.no_fuse_rk;
-    ctx->tend_lds = !ctx->tune.no_tend_lds;
     // Flat y: the anelastic model steps with one kernel per reference kernel (bz_tendency.hip); the compressible kernels reach their
     // y neighbours through wrap offsets, which are zero when Ny = 1 (bz_compressible.hip: wrap_of), and keep their fused sequence
-    if (flat_y) { if (!compressible) ctx->fused_ok = false; ctx->tend_gen = 1; ctx->tend_lds = false; }
+    if (flat_y) { if (!compressible) ctx->fused_ok = false; ctx->tiled_tendencies = false; }
     if (bounded_y && !compressible) {      // per-operator entry points: one kernel per reference kernel, row-wise buffers (bz_tendency.hip); whole steps of the dry
         ctx->walls_lean_ok = ctx->fused_ok;      // model: the lean seam with its WY kernels (bz_step.hip)
-        ctx->fused_ok = false; ctx->tend_gen = 1; ctx->tend_lds = false;
+        ctx->fused_ok = false; ctx->tiled_tendencies = false;
     }
     ctx->compressible = compressible;
     ctx->dz_min = dzc[Hz];

@@ -295,8 +295,6 @@ struct ProfileSlot {
 struct bz_tuning {
     bool no_fused = false;            // BZ_NO_FUSED: per-operator sequence instead of the fused whole-step tiers
     bool no_fuse_rk = false;          // BZ_NO_FUSE_RK
-    bool no_tend_lds = false;         // BZ_NO_TEND_LDS: generation-1 (untiled) tendency kernels
-    int tend_gen = 0;                 // BZ_TEND_GEN (0: default)
     bool no_lean = false;             // BZ_NO_LEAN: fused-RK tier instead of the lean (prognostic-only) seam
     bool no_xcd = false;              // BZ_NO_XCD: hardware block order in the lean kernels
     bool no_closure_march = false;    // BZ_NO_CLOSURE_MARCH: the cell-per-thread closure kernels everywhere
@@ -393,12 +391,12 @@ struct bz_ctx {
     double *d_tfac = nullptr;         // NXH*Ny*Nz : t_k = c_{k-1}/beta_{k-1}
     double *d_lower = nullptr;        // Nz
     double *d_scalar = nullptr;       // small scratch (mean, reductions)
-    int tend_gen = 2;                 // tendency kernel generation (BZ_TEND_GEN: 1 = gen-1 everywhere, 2 = gen-1 momentum + fused scalar pair, 3 = gen-3 u,v + pair, 4 = gen-3 everywhere)
     // y-slab decomposition (bz_create_slab): this rank owns Ny rows of Ny*y_nranks and the kx block
     // [kx0, kx0+nkx) of the zero-padded half spectrum; the horizontal transforms are done by the caller.
     int y_nranks = 1, y_rank = 0, nkx = 0, kx0 = 0, Ny_global = 0;
     bool slab_mode = false;           // created by bz_create_slab (also with one rank): caller fills y halos and does the FFTs
-    bool tend_lds = true;             // LDS y-tile variants of the u and w tendency kernels (BZ_NO_TEND_LDS=1 disables)
+    bool tiled_tendencies = true;     // order-5 tendencies by the LDS-tiled / stored-velocity kernels (bz_tendency4.hip); false on a Flat y and on an anelastic
+                                      // Bounded y, whose per-operator paths keep the generation-1 kernels of bz_tendency.hip
     bool fuse_rk = true;              // whole-step seam: RK update folded into the tendency kernels (BZ_NO_FUSE_RK=1 disables)
     bool G_is_predictor = false;      // after a fused step the G arrays hold predictor momentum, not tendencies
     bool fused_ok = true;             // Nx >= 2Hx && Ny >= 2Hy: fused halo-image stores are valid
@@ -573,7 +571,7 @@ void bzi_forcing_teardown(bz_ctx *ctx);
 int bzi_tracer_specific(bz_ctx *ctx);
 int bzi_tracer_rk3(bz_ctx *ctx, double dt, double alpha, bool first);
 int bzi_tracer_store_initial_state(bz_ctx *ctx);
-int bzi_tracer_tendencies(bz_ctx *ctx, const bz_state *s);
+int bzi_tracer_tendencies(bz_ctx *ctx, const bz_state *s, bool one_record = true);      // one_record: one profile record for all tracers
 int bzi_momentum_advection_gen1(bz_ctx *ctx, const bz_state *s, const bz_prognostic *G);
 int bzi_momentum_advection_generic(bz_ctx *ctx, const bz_state *s, const bz_prognostic *G);
 int bzi_generic_tendencies_fused_rk(bz_ctx *ctx, const bz_state *s, const bz_prognostic *U0, const bz_prognostic *G, double dt, double alpha,
@@ -583,7 +581,6 @@ int bzi_scalar_rho3d_generic(bz_ctx *ctx, double *Gc, double *Grho, const double
                              const double *c, const double *ru, const double *rv, const double *rw);
 void bzi_closure_teardown(bz_ctx *ctx);
 int bzi_apply_closure(bz_ctx *ctx, const bz_state *s, double *Gu, double *Gv, double *Gw, double *Gth, double *Gq, double scale);
-int bzi_kessler_tendencies(bz_ctx *ctx, const bz_state *s);
 int bzi_kessler_rk3(bz_ctx *ctx, double dt, double alpha, bool first);
 int bzi_kessler_update(bz_ctx *ctx, const bz_state *s, const bz_prognostic *G, double dt);
 int bzi_fill_halos_multi(bz_ctx *ctx, double *const *fields, const int *kinds, int n);
@@ -651,7 +648,6 @@ int bzi_tendencies_fused_rk(bz_ctx *ctx, const bz_state *s, const bz_prognostic 
 int bzi_create(bz_ctx **out, const bz_grid *grid, const bz_constants *constants, const bz_reference_state *ref,
                int weno_order, int y_nranks, int y_rank, bool slab_mode, bool compressible = false);
 void bzi_compressible_teardown(bz_ctx *ctx);
-int bzi_compute_tendencies3(bz_ctx *ctx, const bz_state *s, const bz_prognostic *G, bool include_w);
 bool bzi_k6_stored_ok(const bz_ctx *ctx);
 int bzi_k6_stored(bz_ctx *ctx, int comp, const bz_state *s, const bz_prognostic *G, const bz_prognostic *U0, const RKEpilogue *Ein, int bm);
 int bzi_scalar_pair_tendency(bz_ctx *ctx, const bz_state *s, const bz_prognostic *G, const bz_prognostic *U0 = nullptr,
@@ -662,5 +658,5 @@ int bzi_v_tendency_lds(bz_ctx *ctx, const bz_state *s, const bz_prognostic *G, c
                        const RKEpilogue *E = nullptr);
 // buoyancy_mode 0: anelastic buoyancy (T, q, reference columns); 1: none (SlowTendencyMode); 2: compressible slow
 // vertical momentum, s->T = pressure, s->q = total density, reference columns p_r, rho (acoustic_substepping.jl:727-752)
-int bzi_w_tendency_ring(bz_ctx *ctx, const bz_state *s, const bz_prognostic *G, const bz_prognostic *U0 = nullptr,
-                        const RKEpilogue *E = nullptr, int buoyancy_mode = 0);
+int bzi_w_tendency_lds(bz_ctx *ctx, const bz_state *s, const bz_prognostic *G, const bz_prognostic *U0 = nullptr,
+                       const RKEpilogue *E = nullptr, int buoyancy_mode = 0);

@@ -394,7 +394,7 @@ static int anelastic_step_body(bz_ctx *ctx, const bz_state *s, const bz_prognost
             const double alpha = alphas[stage];
             // momentum terms of the forcing stack in the epilogues of the stored-velocity momentum kernels (round 5): the stage's subsidence
             // profiles are built first (from the stored u, v, theta, q of the stage start, which the tendency kernels do not touch)
-            const bool fold = ctx->has_forcings && ctx->weno_R == 3 && bzi_k6_stored_ok(ctx) && ctx->tend_lds && !ctx->tune.no_fuse_forcing && !ctx->tune.no_fold_forcing;
+            const bool fold = ctx->has_forcings && ctx->weno_R == 3 && bzi_k6_stored_ok(ctx) && ctx->tiled_tendencies && !ctx->tune.no_fuse_forcing && !ctx->tune.no_fold_forcing;
             if (stage == 0) ctx->lsum_fresh = lsum_in;
             if (fold && (rc = bzi_compute_forcings(ctx, s))) return rc;
             ctx->fold_momentum_forcing = fold;

@@ -12,6 +12,7 @@
 // horizontal stencils are read straight from global memory (L1/L2 resident: the tile's rows were
 // touched by the neighbouring lanes / rows a few instructions earlier).
 #include <cstdlib>
+#include <optional>
 
 #include "bz_internal.h"
 #include "bz_weno.h"
@@ -322,87 +323,111 @@ static int pick_kchunk(const DevGrid &g, int nlev)
     return (int)((nlev + want - 1) / want);
 }
 
+// launch shape of the kernels above: 64 x TYB tiles, nlev levels in chunks of pick_kchunk
+struct Gen1Launch {
+    int kc;
+    dim3 block, grid;
+    Gen1Launch(const DevGrid &g, int nlev) : kc(pick_kchunk(g, nlev)), block(64, TYB), grid((g.Nx + 63) / 64, (g.Ny + TYB - 1) / TYB, (nlev + kc - 1) / kc) {}
+};
+
 // momentum advection by the per-operator kernels alone (no buoyancy): the slow momentum tendencies of the split-explicit compressible
 // model on (Periodic, Flat, Bounded) grids, where the LDS-tiled kernels (y halo rows in their tiles) do not apply
 int bzi_momentum_advection_gen1(bz_ctx *ctx, const bz_state *s, const bz_prognostic *G)
 {
     const DevGrid &g = ctx->dg;
-    const dim3 block(64, TYB);
-    const int kc = pick_kchunk(g, g.Nz), kcw = pick_kchunk(g, g.Nz - 1);
-    const dim3 grid((g.Nx + 63) / 64, (g.Ny + TYB - 1) / TYB, (g.Nz + kc - 1) / kc);
-    const dim3 gridw(grid.x, grid.y, (g.Nz - 1 + kcw - 1) / kcw);
+    const Gen1Launch L(g, g.Nz), Lw(g, g.Nz - 1);
     {
         ProfileScope ps(ctx, "x_momentum_tendency");
-        hipLaunchKernelGGL(k_u_tendency, grid, block, 0, ctx->stream, g, G->rho_u, s->rho_u, s->rho_v, s->rho_w, s->u, kc, RKEpilogue());
+        hipLaunchKernelGGL(k_u_tendency, L.grid, L.block, 0, ctx->stream, g, G->rho_u, s->rho_u, s->rho_v, s->rho_w, s->u, L.kc, RKEpilogue());
     }
     {
         ProfileScope ps(ctx, "y_momentum_tendency");
-        hipLaunchKernelGGL(k_v_tendency, grid, block, 0, ctx->stream, g, G->rho_v, s->rho_u, s->rho_v, s->rho_w, s->v, kc, RKEpilogue());
+        hipLaunchKernelGGL(k_v_tendency, L.grid, L.block, 0, ctx->stream, g, G->rho_v, s->rho_u, s->rho_v, s->rho_w, s->v, L.kc, RKEpilogue());
     }
     {
         ProfileScope ps(ctx, "z_momentum_tendency");
-        hipLaunchKernelGGL(k_w_tendency<false>, gridw, block, 0, ctx->stream, g, G->rho_w, s->rho_u, s->rho_v, s->rho_w, s->w,
-                           (const double *)nullptr, (const double *)nullptr, kcw);
+        hipLaunchKernelGGL(k_w_tendency<false>, Lw.grid, Lw.block, 0, ctx->stream, g, G->rho_w, s->rho_u, s->rho_v, s->rho_w, s->w,
+                           (const double *)nullptr, (const double *)nullptr, Lw.kc);
     }
     BZ_LAUNCH_CHECK();
     return BZ_OK;
 }
 
-// momentum_advection and scalar_advection of different orders (atmosphere_model.jl:80-82,148-158; examples/tropical_cyclone_world.jl:167-169,
-// examples/prescribed_sea_surface_temperature.jl:72-73: momentum WENO(order = 9), scalars WENO(order = 5)): the momentum kernels of the
-// momentum order, one scalar kernel per scalar of the scalars' order, then the order-independent terms — operator by operator, as the
-// reference launches them (update_atmosphere_model_state.jl:294-387)
-static int compute_tendencies_mixed(bz_ctx *ctx, const bz_state *s, const bz_prognostic *G)
+// The generation-1 momentum tendencies, one launch per reference kernel: what a context without the tiled kernels runs
+// (bz_ctx::tiled_tendencies).  With an RK epilogue (bzi_tendencies_fused_rk) u and v carry it together with their step-start arrays of
+// U0; k_w_tendency has no epilogue, so there the caller takes w from bzi_w_tendency_lds.
+static int momentum_tendencies_gen1(bz_ctx *ctx, const bz_state *s, const bz_prognostic *G, const RKEpilogue *Ein = nullptr,
+                                    const bz_prognostic *U0 = nullptr)
 {
     const DevGrid &g = ctx->dg;
+    const Gen1Launch L(g, g.Nz);
+    RKEpilogue E;
+    if (Ein) E = *Ein;
+    {
+        ProfileScope ps(ctx, Ein ? "x_momentum_tendency+rk3" : "x_momentum_tendency");
+        if (Ein) { E.u0 = U0->rho_u; E.u0_out = U0->rho_u; }
+        hipLaunchKernelGGL(k_u_tendency, L.grid, L.block, 0, ctx->stream, g, G->rho_u, s->rho_u, s->rho_v, s->rho_w, s->u, L.kc, E);
+    }
+    {
+        ProfileScope ps(ctx, Ein ? "y_momentum_tendency+rk3" : "y_momentum_tendency");
+        if (Ein) { E.u0 = U0->rho_v; E.u0_out = U0->rho_v; }
+        hipLaunchKernelGGL(k_v_tendency, L.grid, L.block, 0, ctx->stream, g, G->rho_v, s->rho_u, s->rho_v, s->rho_w, s->v, L.kc, E);
+    }
+    if (!Ein && g.Nz > 1) {
+        ProfileScope ps(ctx, "z_momentum_tendency");
+        const Gen1Launch Lw(g, g.Nz - 1);
+        hipLaunchKernelGGL(k_w_tendency<true>, Lw.grid, Lw.block, 0, ctx->stream, g, G->rho_w, s->rho_u, s->rho_v, s->rho_w, s->w, s->T, s->q, Lw.kc);
+    }
+    BZ_LAUNCH_CHECK();
+    return BZ_OK;
+}
+
+// One scalar of the scalars' order: Gc = -div_rhoUc(c).  scope names the launch's own profile record; nullptr where the caller's
+// ProfileScope covers several launches.
+static int scalar_tendency(bz_ctx *ctx, const char *scope, double *Gc, const double *u, const double *v, const double *w, const double *c)
+{
+    std::optional<ProfileScope> ps;
+    if (scope) ps.emplace(ctx, scope);
+    if (ctx->scalar_R != 3) return bzi_scalar_tendency_generic(ctx, Gc, u, v, w, c);
+    const DevGrid &g = ctx->dg;
+    const Gen1Launch L(g, g.Nz);
+    hipLaunchKernelGGL(k_scalar_tendency, L.grid, L.block, 0, ctx->stream, g, Gc, u, v, w, c, L.kc);
+    return BZ_OK;
+}
+
+// scalar tendencies of the user tracers: G = -div_rhoUc(c)  (update_atmosphere_model_state.jl:352-372)
+int bzi_tracer_tendencies(bz_ctx *ctx, const bz_state *s, bool one_record)
+{
     int rc;
-    if (ctx->bounded_mask && ctx->scalar_R != 3) {
-        ctx->last_error = "bounds-preserving advection is a WENO(order = 5) scalar scheme";
-        return BZ_ERR_UNSUPPORTED;
-    }
-    const dim3 block(64, TYB);
-    const int kc = pick_kchunk(g, g.Nz), kcw = pick_kchunk(g, g.Nz - 1);
-    const dim3 grid((g.Nx + 63) / 64, (g.Ny + TYB - 1) / TYB, (g.Nz + kc - 1) / kc);
-    if (ctx->weno_R != 3) {
-        if ((rc = bzi_momentum_tendencies_generic(ctx, s, G))) return rc;
-    } else if (ctx->tend_gen >= 2 && ctx->tend_lds) {      // the order-5 kernels bz_compute_tendencies itself would pick
-        if ((rc = bzi_u_tendency_lds(ctx, s, G))) return rc;
-        if ((rc = bzi_v_tendency_lds(ctx, s, G))) return rc;
-        if ((rc = bzi_w_tendency_ring(ctx, s, G))) return rc;
-    } else {
-        {
-            ProfileScope ps(ctx, "x_momentum_tendency");
-            hipLaunchKernelGGL(k_u_tendency, grid, block, 0, ctx->stream, g, G->rho_u, s->rho_u, s->rho_v, s->rho_w, s->u, kc, RKEpilogue());
-        }
-        {
-            ProfileScope ps(ctx, "y_momentum_tendency");
-            hipLaunchKernelGGL(k_v_tendency, grid, block, 0, ctx->stream, g, G->rho_v, s->rho_u, s->rho_v, s->rho_w, s->v, kc, RKEpilogue());
-        }
-        if (g.Nz > 1) {
-            ProfileScope ps(ctx, "z_momentum_tendency");
-            const dim3 gridw(grid.x, grid.y, (g.Nz - 1 + kcw - 1) / kcw);
-            hipLaunchKernelGGL(k_w_tendency<true>, gridw, block, 0, ctx->stream, g, G->rho_w, s->rho_u, s->rho_v, s->rho_w, s->w, s->T, s->q, kcw);
-        }
-    }
-    auto scalar = [&](const char *name, double *Gc, const double *c) -> int {
-        ProfileScope ps(ctx, name);
-        if (ctx->scalar_R != 3) return bzi_scalar_tendency_generic(ctx, Gc, s->u, s->v, s->w, c);
-        hipLaunchKernelGGL(k_scalar_tendency, grid, block, 0, ctx->stream, g, Gc, s->u, s->v, s->w, c, kc);
-        return BZ_OK;
-    };
-    if (ctx->scalar_R == 3 && ctx->tend_gen >= 2) {      // theta and moisture together in the LDS-tiled pair kernel, as in the single-order path
-        if ((rc = bzi_scalar_pair_tendency(ctx, s, G))) return rc;
-    } else {
-        if ((rc = scalar("potential_temperature_tendency", G->rho_theta, s->theta))) return rc;
-        if ((rc = scalar("moisture_tendency", G->rho_q, s->q))) return rc;
-    }
-    if (g.microphysics == 2) {
-        if ((rc = scalar("kessler_species_tendencies", ctx->kessler.G_cloud_liquid_density, ctx->kessler.cloud_liquid_mass_fraction))) return rc;
-        if ((rc = scalar("kessler_species_tendencies", ctx->kessler.G_rain_density, ctx->kessler.rain_mass_fraction))) return rc;
-    }
+    std::optional<ProfileScope> ps;
+    if (one_record) ps.emplace(ctx, "tracer_tendencies");
     for (int t = 0; t < ctx->n_tracers; ++t)
-        if ((rc = scalar("tracer_tendencies", ctx->tracers[t].G, ctx->tracers[t].specific))) return rc;
-    if (g.formulation == 1) {
+        if ((rc = scalar_tendency(ctx, one_record ? nullptr : "tracer_tendencies", ctx->tracers[t].G, s->u, s->v, s->w, ctx->tracers[t].specific))) return rc;
+    BZ_LAUNCH_CHECK();
+    return BZ_OK;
+}
+
+// The order-independent end of compute_tendencies! (update_atmosphere_model_state.jl:294-387), shared by every branch of
+// bz_compute_tendencies: the scalars beyond theta and moisture (by the kernel of the scalars' order), then the terms without an advection
+// scheme in them.  The static-energy buoyancy flux writes G->rho_theta and the species and tracer launches write arrays of their own, so
+// their mutual order does not matter to any bit (the order-5 sequence used to launch the flux before the tracers, the other two after).
+// Profile records stay as each sequence made them before they shared this tail (bench.py counts launches per record): different orders
+// record every scalar launch, a single order the two Kessler species together and — order 5 only — all tracers together.
+static int finish_tendencies(bz_ctx *ctx, const bz_state *s, const bz_prognostic *G)
+{
+    const DevGrid &g = ctx->dg;
+    const bool mixed = ctx->scalar_R != ctx->weno_R;
+    int rc;
+    if (g.microphysics == 2) {      // Kessler condensate species: G = -div_rhoUc(q^cl), -div_rhoUc(q^r) (prognostic_field_names(::DCMIP2016KM), dcmip2016_kessler.jl:216)
+        const char *name = "kessler_species_tendencies";
+        std::optional<ProfileScope> ps;
+        if (!mixed) ps.emplace(ctx, name);
+        const char *own = mixed ? name : nullptr;
+        if ((rc = scalar_tendency(ctx, own, ctx->kessler.G_cloud_liquid_density, s->u, s->v, s->w, ctx->kessler.cloud_liquid_mass_fraction))) return rc;
+        if ((rc = scalar_tendency(ctx, own, ctx->kessler.G_rain_density, s->u, s->v, s->w, ctx->kessler.rain_mass_fraction))) return rc;
+    }
+    if (ctx->n_tracers && (rc = bzi_tracer_tendencies(ctx, s, !mixed && ctx->weno_R == 3))) return rc;
+    if (g.formulation == 1) {      // StaticEnergy (examples/dry_thermal_bubble.jl:25): the buoyancy flux term has no advection scheme in it
         ProfileScope ps(ctx, "static_energy_buoyancy_flux");
         hipLaunchKernelGGL(k_energy_buoyancy_flux, dim3((g.Nx + 255) / 256, g.Ny, g.Nz), dim3(256), 0, ctx->stream, g, G->rho_theta, s->w, s->T, s->q);
     }
@@ -436,126 +461,49 @@ extern "C" int bz_set_scalar_advection_order(bz_ctx *ctx, int order)
 #endif
 }
 
+// momentum_advection and scalar_advection of different orders (atmosphere_model.jl:80-82,148-158; examples/tropical_cyclone_world.jl:167-169,
+// examples/prescribed_sea_surface_temperature.jl:72-73: momentum WENO(order = 9), scalars WENO(order = 5)): the momentum kernels of the
+// momentum order, one scalar kernel per scalar of the scalars' order, then the order-independent terms — operator by operator, as the
+// reference launches them (update_atmosphere_model_state.jl:294-387).  An order-5 side takes the kernels of the all-order-5 model, which
+// is the same sequence with both sides of order 5.
+static int compute_tendencies_by_operator(bz_ctx *ctx, const bz_state *s, const bz_prognostic *G)
+{
+    int rc;
+    if (ctx->bounded_mask && ctx->scalar_R != 3) {
+        ctx->last_error = "bounds-preserving advection is a WENO(order = 5) scalar scheme";
+        return BZ_ERR_UNSUPPORTED;
+    }
+    if (ctx->weno_R != 3) {
+        if ((rc = bzi_momentum_tendencies_generic(ctx, s, G))) return rc;
+    } else if (ctx->tiled_tendencies) {
+        if ((rc = bzi_u_tendency_lds(ctx, s, G))) return rc;
+        if ((rc = bzi_v_tendency_lds(ctx, s, G))) return rc;
+        if ((rc = bzi_w_tendency_lds(ctx, s, G))) return rc;
+    } else {
+        if ((rc = momentum_tendencies_gen1(ctx, s, G))) return rc;
+    }
+    if (ctx->scalar_R == 3 && ctx->tiled_tendencies) {      // theta and moisture together in the LDS-tiled pair kernel
+        if ((rc = bzi_scalar_pair_tendency(ctx, s, G))) return rc;
+    } else {
+        if ((rc = scalar_tendency(ctx, "potential_temperature_tendency", G->rho_theta, s->u, s->v, s->w, s->theta))) return rc;
+        if ((rc = scalar_tendency(ctx, "moisture_tendency", G->rho_q, s->u, s->v, s->w, s->q))) return rc;
+    }
+    return finish_tendencies(ctx, s, G);
+}
+
 extern "C" int bz_compute_tendencies(bz_ctx *ctx, const bz_state *s, const bz_prognostic *G)
 {
     if (!ctx || !s || !G) return BZ_ERR_INVALID;
     { const int rcs = bzi_refresh_diagnostics(ctx, s, "bz_compute_tendencies"); if (rcs) return rcs; }
     ctx->G_is_predictor = false;
-    const DevGrid &g = ctx->dg;
-    dim3 block(64, TYB);
-    if (ctx->scalar_R != ctx->weno_R) return compute_tendencies_mixed(ctx, s, G);
-    if (ctx->weno_R != 3) {      // WENO(order = 7 / 9): generic kernels for the five prognostic fields, then the order-independent terms
-        if (ctx->bounded_mask) {
-            ctx->last_error = "WENO(order = 7 / 9) does not implement bounds-preserving advection";
-            return BZ_ERR_UNSUPPORTED;
-        }
-        int rcg = bzi_compute_tendencies_generic(ctx, s, G);
-        if (rcg) return rcg;
-        if (g.microphysics == 2) {      // Kessler condensate species (bzi_kessler_tendencies, order-generic)
-            ProfileScope ps(ctx, "kessler_species_tendencies");
-            if ((rcg = bzi_scalar_tendency_generic(ctx, ctx->kessler.G_cloud_liquid_density, s->u, s->v, s->w, ctx->kessler.cloud_liquid_mass_fraction))) return rcg;
-            if ((rcg = bzi_scalar_tendency_generic(ctx, ctx->kessler.G_rain_density, s->u, s->v, s->w, ctx->kessler.rain_mass_fraction))) return rcg;
-        }
-        for (int t = 0; t < ctx->n_tracers; ++t) {
-            ProfileScope ps(ctx, "tracer_tendencies");
-            if ((rcg = bzi_scalar_tendency_generic(ctx, ctx->tracers[t].G, s->u, s->v, s->w, ctx->tracers[t].specific))) return rcg;
-        }
-        if (g.formulation == 1) {      // StaticEnergy (examples/dry_thermal_bubble.jl:25): the buoyancy flux term has no advection scheme in it
-            ProfileScope ps(ctx, "static_energy_buoyancy_flux");
-            hipLaunchKernelGGL(k_energy_buoyancy_flux, dim3((g.Nx + 255) / 256, g.Ny, g.Nz), dim3(256), 0, ctx->stream, g,
-                               G->rho_theta, s->w, s->T, s->q);
-        }
-        if (ctx->has_closure && (rcg = bzi_apply_closure(ctx, s, G->rho_u, G->rho_v, G->rho_w, G->rho_theta, G->rho_q, 1.0))) return rcg;
-        if (ctx->has_forcings && (rcg = bzi_apply_forcings(ctx, s, G->rho_u, G->rho_v, G->rho_theta, G->rho_q, 1.0))) return rcg;
-        return bzi_apply_relaxation(ctx, s, G);
-    }
-    if (ctx->tend_gen >= 3 && g.formulation != 0) {
-        ctx->last_error = "BZ_TEND_GEN >= 3 implements the potential-temperature formulation only";
+    if (ctx->scalar_R != ctx->weno_R || ctx->weno_R == 3) return compute_tendencies_by_operator(ctx, s, G);
+    // WENO(order = 7 / 9): generic kernels for the five prognostic fields, then the order-independent terms
+    if (ctx->bounded_mask) {
+        ctx->last_error = "WENO(order = 7 / 9) does not implement bounds-preserving advection";
         return BZ_ERR_UNSUPPORTED;
     }
-    if (ctx->tend_gen >= 3) {
-        // gen-3 kernels for the scalars and horizontal momentum; w stays gen-1 unless BZ_TEND_GEN=4
-        if (ctx->bounded_mask) { ctx->last_error = "BZ_TEND_GEN >= 3 does not implement bounds-preserving advection"; return BZ_ERR_UNSUPPORTED; }
-        int rc = bzi_compute_tendencies3(ctx, s, G, ctx->tend_gen >= 4);
-        if (rc || ctx->tend_gen >= 4) return rc;
-        ProfileScope ps(ctx, "z_momentum_tendency");
-        int kcw = pick_kchunk(g, g.Nz - 1);
-        dim3 gridw((g.Nx + 63) / 64, (g.Ny + TYB - 1) / TYB, (g.Nz - 1 + kcw - 1) / kcw);
-        hipLaunchKernelGGL(k_w_tendency<true>, gridw, block, 0, ctx->stream, g, G->rho_w, s->rho_u, s->rho_v, s->rho_w, s->w,
-                           s->T, s->q, kcw);
-        BZ_LAUNCH_CHECK();
-        return BZ_OK;
-    }
-    int kc = pick_kchunk(g, g.Nz);
-    dim3 grid((g.Nx + 63) / 64, (g.Ny + TYB - 1) / TYB, (g.Nz + kc - 1) / kc);
-    if (ctx->tend_gen >= 2 && ctx->tend_lds) {
-        int rc = bzi_u_tendency_lds(ctx, s, G);
-        if (rc) return rc;
-    } else {
-        ProfileScope ps(ctx, "x_momentum_tendency");
-        hipLaunchKernelGGL(k_u_tendency, grid, block, 0, ctx->stream, g, G->rho_u, s->rho_u, s->rho_v, s->rho_w, s->u, kc, RKEpilogue());
-    }
-    if (ctx->tend_gen >= 2 && ctx->tend_lds) {
-        int rc = bzi_v_tendency_lds(ctx, s, G);
-        if (rc) return rc;
-    } else {
-        ProfileScope ps(ctx, "y_momentum_tendency");
-        hipLaunchKernelGGL(k_v_tendency, grid, block, 0, ctx->stream, g, G->rho_v, s->rho_u, s->rho_v, s->rho_w, s->v, kc, RKEpilogue());
-    }
-    if (ctx->tend_gen >= 2) {
-        int rc = bzi_w_tendency_ring(ctx, s, G);
-        if (rc) return rc;
-    } else {
-        ProfileScope ps(ctx, "z_momentum_tendency");
-        int kcw = pick_kchunk(g, g.Nz - 1);
-        dim3 gridw(grid.x, grid.y, (g.Nz - 1 + kcw - 1) / kcw);
-        hipLaunchKernelGGL(k_w_tendency<true>, gridw, block, 0, ctx->stream, g, G->rho_w, s->rho_u, s->rho_v, s->rho_w, s->w,
-                           s->T, s->q, kcw);
-    }
-    if (ctx->tend_gen >= 2) {
-        int rc = bzi_scalar_pair_tendency(ctx, s, G);
-        if (rc) return rc;
-    } else {
-        {
-            ProfileScope ps(ctx, "potential_temperature_tendency");
-            hipLaunchKernelGGL(k_scalar_tendency, grid, block, 0, ctx->stream, g, G->rho_theta, s->u, s->v, s->w, s->theta, kc);
-        }
-        {
-            ProfileScope ps(ctx, "moisture_tendency");
-            hipLaunchKernelGGL(k_scalar_tendency, grid, block, 0, ctx->stream, g, G->rho_q, s->u, s->v, s->w, s->q, kc);
-        }
-    }
-    if (g.microphysics == 2) {
-        int rck = bzi_kessler_tendencies(ctx, s);
-        if (rck) return rck;
-    }
-    if (g.formulation == 1) {
-        ProfileScope ps(ctx, "static_energy_buoyancy_flux");
-        hipLaunchKernelGGL(k_energy_buoyancy_flux, dim3((g.Nx + 255) / 256, g.Ny, g.Nz), dim3(256), 0, ctx->stream, g,
-                           G->rho_theta, s->w, s->T, s->q);
-    }
-    if (ctx->n_tracers) {
-        int rct = bzi_tracer_tendencies(ctx, s);
-        if (rct) return rct;
-    }
-    if (ctx->bounded_mask) {
-        int rcb = bzi_bounded_tendencies(ctx, s, G);
-        if (rcb) return rcb;
-    }
-    if (ctx->has_closure) {
-        int rcc = bzi_apply_closure(ctx, s, G->rho_u, G->rho_v, G->rho_w, G->rho_theta, G->rho_q, 1.0);
-        if (rcc) return rcc;
-    }
-    if (ctx->has_forcings) {
-        int rcf = bzi_apply_forcings(ctx, s, G->rho_u, G->rho_v, G->rho_theta, G->rho_q, 1.0);
-        if (rcf) return rcf;
-    }
-    {
-        int rcr = bzi_apply_relaxation(ctx, s, G);
-        if (rcr) return rcr;
-    }
-    BZ_LAUNCH_CHECK();
-    return BZ_OK;
+    const int rc = bzi_compute_tendencies_generic(ctx, s, G);
+    return rc ? rc : finish_tendencies(ctx, s, G);
 }
 
 // compute_tendencies! with the next ssp_rk3_substep! folded into the kernels' store (whole-step seam):
@@ -564,32 +512,17 @@ int bzi_tendencies_fused_rk(bz_ctx *ctx, const bz_state *s, const bz_prognostic 
                             double alpha, bool first)
 {
     if (ctx->weno_R != 3) return bzi_generic_tendencies_fused_rk(ctx, s, U0, G, dt, alpha, first);      // WENO 7 / 9: bz_tendency_generic.hip
-    const DevGrid &g = ctx->dg;
-    dim3 block(64, TYB);
-    int kc = pick_kchunk(g, g.Nz);
-    dim3 grid((g.Nx + 63) / 64, (g.Ny + TYB - 1) / TYB, (g.Nz + kc - 1) / kc);
     RKEpilogue E;
     E.mode = first ? 1 : 2; E.dt = dt; E.alpha = alpha; E.oma = 1.0 - alpha;
-    if (ctx->tend_lds) {
-        int rcu = bzi_u_tendency_lds(ctx, s, G, U0, &E);
-        if (rcu) return rcu;
+    int rc;
+    if (ctx->tiled_tendencies) {
+        if ((rc = bzi_u_tendency_lds(ctx, s, G, U0, &E))) return rc;
+        if ((rc = bzi_v_tendency_lds(ctx, s, G, U0, &E))) return rc;
     } else {
-        ProfileScope ps(ctx, "x_momentum_tendency+rk3");
-        E.u0 = U0->rho_u; E.u0_out = U0->rho_u;
-        hipLaunchKernelGGL(k_u_tendency, grid, block, 0, ctx->stream, g, G->rho_u, s->rho_u, s->rho_v, s->rho_w, s->u, kc, E);
+        if ((rc = momentum_tendencies_gen1(ctx, s, G, &E, U0))) return rc;
     }
-    if (ctx->tend_lds) {
-        int rcv = bzi_v_tendency_lds(ctx, s, G, U0, &E);
-        if (rcv) return rcv;
-    } else {
-        ProfileScope ps(ctx, "y_momentum_tendency+rk3");
-        E.u0 = U0->rho_v; E.u0_out = U0->rho_v;
-        hipLaunchKernelGGL(k_v_tendency, grid, block, 0, ctx->stream, g, G->rho_v, s->rho_u, s->rho_v, s->rho_w, s->v, kc, E);
-    }
-    int rc = bzi_w_tendency_ring(ctx, s, G, U0, &E);
-    if (rc) return rc;
-    rc = bzi_scalar_pair_tendency(ctx, s, G, U0, &E);
-    if (rc) return rc;
+    if ((rc = bzi_w_tendency_lds(ctx, s, G, U0, &E))) return rc;
+    if ((rc = bzi_scalar_pair_tendency(ctx, s, G, U0, &E))) return rc;
     BZ_LAUNCH_CHECK();
     return BZ_OK;
 }
@@ -599,45 +532,8 @@ extern "C" int bz_compute_scalar_tendency(bz_ctx *ctx, const double *u, const do
 {
     if (!ctx || !u || !v || !w || !c || !Gc) return BZ_ERR_INVALID;
     if (ctx->compressible) { ctx->last_error = "bz_compute_scalar_tendency: anelastic contexts (the compressible model: bz_compute_moisture_tendency)"; return BZ_ERR_UNSUPPORTED; }
-    ProfileScope ps(ctx, "scalar_tendency");
-    if (ctx->scalar_R != 3) return bzi_scalar_tendency_generic(ctx, Gc, u, v, w, c);
-    const DevGrid &g = ctx->dg;
-    dim3 block(64, TYB);
-    const int kc = pick_kchunk(g, g.Nz);
-    dim3 grid((g.Nx + 63) / 64, (g.Ny + TYB - 1) / TYB, (g.Nz + kc - 1) / kc);
-    hipLaunchKernelGGL(k_scalar_tendency, grid, block, 0, ctx->stream, g, Gc, u, v, w, c, kc);
-    BZ_LAUNCH_CHECK();
-    return BZ_OK;
-}
-
-// scalar tendencies of the user tracers: G = -div_rhoUc(c)  (update_atmosphere_model_state.jl:352-372)
-int bzi_tracer_tendencies(bz_ctx *ctx, const bz_state *s)
-{
-    const DevGrid &g = ctx->dg;
-    ProfileScope ps(ctx, "tracer_tendencies");
-    dim3 block(64, TYB);
-    int kc = pick_kchunk(g, g.Nz);
-    dim3 grid((g.Nx + 63) / 64, (g.Ny + TYB - 1) / TYB, (g.Nz + kc - 1) / kc);
-    for (int t = 0; t < ctx->n_tracers; ++t)
-        hipLaunchKernelGGL(k_scalar_tendency, grid, block, 0, ctx->stream, g, ctx->tracers[t].G, s->u, s->v, s->w,
-                           ctx->tracers[t].specific, kc);
-    BZ_LAUNCH_CHECK();
-    return BZ_OK;
-}
-
-// scalar tendencies of the Kessler condensate species: G = -div_rhoUc(q^cl), -div_rhoUc(q^r)
-// (update_atmosphere_model_state.jl:352-372 with prognostic_field_names(::DCMIP2016KM), dcmip2016_kessler.jl:216)
-int bzi_kessler_tendencies(bz_ctx *ctx, const bz_state *s)
-{
-    const DevGrid &g = ctx->dg;
-    ProfileScope ps(ctx, "kessler_species_tendencies");
-    dim3 block(64, TYB);
-    int kc = pick_kchunk(g, g.Nz);
-    dim3 grid((g.Nx + 63) / 64, (g.Ny + TYB - 1) / TYB, (g.Nz + kc - 1) / kc);
-    hipLaunchKernelGGL(k_scalar_tendency, grid, block, 0, ctx->stream, g, ctx->kessler.G_cloud_liquid_density, s->u, s->v, s->w,
-                       ctx->kessler.cloud_liquid_mass_fraction, kc);
-    hipLaunchKernelGGL(k_scalar_tendency, grid, block, 0, ctx->stream, g, ctx->kessler.G_rain_density, s->u, s->v, s->w,
-                       ctx->kessler.rain_mass_fraction, kc);
+    const int rc = scalar_tendency(ctx, "scalar_tendency", Gc, u, v, w, c);
+    if (rc) return rc;
     BZ_LAUNCH_CHECK();
     return BZ_OK;
 }

@@ -9,8 +9,8 @@
 //   * 3-wide halo frame of the tile: ~1 global load per thread and level, issued one level ahead (prefetched into
 //     registers before the arithmetic of the current level, stored to the other LDS buffer after it);
 //   * x/y stencils are ds_read_b64 from the tile;  y-face fluxes are shared through a second double-buffered LDS
-//     array (one barrier per level covers both), x-face fluxes through a wave shuffle + the batched out-of-wave
-//     flux of k_tend3.
+//     array (one barrier per level covers both), x-face fluxes through a wave shuffle + the out-of-wave flux of the
+//     tile row, batched over 64 levels (lane l <-> level k + l) and broadcast with a readlane.
 // Loads per thread and level drop from ~27 to ~9 (fused theta+q kernel), reconstructions from 8 to 6 + 2/TY.
 #pragma once
 #include "bz_internal.h"
@@ -206,7 +206,113 @@ __global__ __launch_bounds__(64 * TY) void k_scalar_pair_lds(DevGrid g, const do
 // rings, the six frame rows prefetched one level ahead), y-face fluxes are shared through LDS (wave 0 also
 // evaluates the face above the tile), x-face/centre fluxes through a wave shuffle + batched out-of-wave flux.
 // ===================================================================================================
-#include "bz_tendency3_kernels.h"
+// field set, advecting fluxes and flux helpers shared by the momentum tiles below and by the stored-velocity kernels of
+// bz_tendency5_kernels.h (KIND selects the staggering of the advected field)
+enum { T3_SCALAR = 0, T3_U = 1, T3_V = 2, T3_W = 3 };
+
+struct Tend3Fields {
+    const double *ru, *rv, *rw;     // advecting momentum (momentum kernels)
+    const double *u, *v, *w;        // advecting velocities (scalar kernel)
+    const double *c;                // advected quantity: theta | q | u | v | w
+    const double *T, *q;            // buoyancy inputs (W kernel)
+    double *G;
+};
+
+// advecting flux in x at (i,j,k) [index n], for the x-flux location of KIND
+template <int KIND>
+__device__ __forceinline__ double adv_x(const DevGrid &g, const Tend3Fields &F, long long n, int k)
+{
+    const long long sy = g.Sx, sz = g.Sxy;
+    if constexpr (KIND == T3_SCALAR) {
+        return F.u[n];
+    } else if constexpr (KIND == T3_U) {        // to cell centre i
+        const double A = g.Ax[k];
+        const double *m = F.ru;
+        return bz_symm4(A * m[n - 1], A * m[n], A * m[n + 1], A * m[n + 2]);
+    } else if constexpr (KIND == T3_V) {        // to (x-face i, y-face j)
+        const double A = g.Ax[k];
+        const double *m = F.ru;
+        return bz_symm4(A * m[n - 2 * sy], A * m[n - sy], A * m[n], A * m[n + sy]);
+    } else {                                    // to (x-face i, z-face k)
+        const double *m = F.ru, *A = g.Ax;
+        return (bz_buffer_face(k, g.Nz) == 3)
+                   ? bz_symm4(A[k - 2] * m[n - 2 * sz], A[k - 1] * m[n - sz], A[k] * m[n], A[k + 1] * m[n + sz])
+                   : bz_symm2(A[k - 1] * m[n - sz], A[k] * m[n]);
+    }
+}
+template <int KIND>
+__device__ __forceinline__ double adv_y(const DevGrid &g, const Tend3Fields &F, long long n, int k)
+{
+    const long long sy = g.Sx, sz = g.Sxy;
+    if constexpr (KIND == T3_SCALAR) {
+        return F.v[n];
+    } else if constexpr (KIND == T3_U) {        // to (x-face i, y-face j)
+        const double A = g.Ay[k];
+        const double *m = F.rv;
+        return bz_symm4(A * m[n - 2], A * m[n - 1], A * m[n], A * m[n + 1]);
+    } else if constexpr (KIND == T3_V) {        // to cell centre j
+        const double A = g.Ay[k];
+        const double *m = F.rv;
+        return bz_symm4(A * m[n - sy], A * m[n], A * m[n + sy], A * m[n + 2 * sy]);
+    } else {                                    // to (y-face j, z-face k)
+        const double *m = F.rv, *A = g.Ay;
+        return (bz_buffer_face(k, g.Nz) == 3)
+                   ? bz_symm4(A[k - 2] * m[n - 2 * sz], A[k - 1] * m[n - sz], A[k] * m[n], A[k + 1] * m[n + sz])
+                   : bz_symm2(A[k - 1] * m[n - sz], A[k] * m[n]);
+    }
+}
+// horizontal flux from the advecting flux `a` and the 6 advected values straddling the target
+template <int KIND>
+__device__ __forceinline__ double hflux(const DevGrid &g, double a, double area, int k, double m3, double m2,
+                                        double m1, double p0, double p1, double p2)
+{
+    const double cR = bz_up5(m3, m2, m1, p0, p1, p2, a > 0.0);
+    if constexpr (KIND == T3_SCALAR) return g.rho[k] * ((area * a) * cR);
+    else return a * cR;
+}
+// full x flux at column i (cell or face index by KIND), row j, level k — used for the out-of-wave flux
+template <int KIND>
+__device__ __forceinline__ double flux_x_at(const DevGrid &g, const Tend3Fields &F, int i, int j, int k)
+{
+    const long long n = g.idx(i, j, k);
+    const double a = adv_x<KIND>(g, F, n, k);
+    const double *c = F.c;
+    if constexpr (KIND == T3_U) return hflux<KIND>(g, a, 0.0, k, c[n - 2], c[n - 1], c[n], c[n + 1], c[n + 2], c[n + 3]);
+    else return hflux<KIND>(g, a, g.Ax[k], k, c[n - 3], c[n - 2], c[n - 1], c[n], c[n + 1], c[n + 2]);
+}
+// vertical flux: SCALAR/U/V at z-face kt, W at cell centre kt; nt = idx(i,j,kt)
+template <int KIND>
+__device__ __forceinline__ double vflux(const DevGrid &g, const Tend3Fields &F, long long nt, int kt, double m3,
+                                        double m2, double m1, double p0, double p1, double p2)
+{
+    const long long sy = g.Sx, sz = g.Sxy;
+    const double Az = g.Az;
+    if constexpr (KIND == T3_SCALAR) {
+        const double wt = F.w[nt];
+        const double cR = bz_upB(m3, m2, m1, p0, p1, p2, wt > 0.0, bz_buffer_face(kt, g.Nz));
+        return g.rho_f[kt] * ((Az * wt) * cR);
+    } else if constexpr (KIND == T3_U) {
+        const double *m = F.rw;
+        const double wt = bz_symm4(Az * m[nt - 2], Az * m[nt - 1], Az * m[nt], Az * m[nt + 1]);
+        return wt * bz_upB(m3, m2, m1, p0, p1, p2, wt > 0.0, bz_buffer_face(kt, g.Nz));
+    } else if constexpr (KIND == T3_V) {
+        const double *m = F.rw;
+        const double wt = bz_symm4(Az * m[nt - 2 * sy], Az * m[nt - sy], Az * m[nt], Az * m[nt + sy]);
+        return wt * bz_upB(m3, m2, m1, p0, p1, p2, wt > 0.0, bz_buffer_face(kt, g.Nz));
+    } else {
+        const double *m = F.rw;
+        const int B = bz_buffer_center(kt, g.Nz);
+        const double wt = (B == 3) ? bz_symm4(Az * m[nt - sz], Az * m[nt], Az * m[nt + sz], Az * m[nt + 2 * sz])
+                                   : bz_symm2(Az * m[nt], Az * m[nt + sz]);
+        return wt * bz_upB(m3, m2, m1, p0, p1, p2, wt > 0.0, B);
+    }
+}
+__device__ __forceinline__ double buoyancy3(const DevGrid &g, double T, double q, int k)
+{   // anelastic_buoyancy.jl:36-72, dry reference state (R_m,r = Rd)
+    const double Rm = (1.0 - q) * g.Rd + q * g.Rv;
+    const double rhop = g.rho[k] * (g.Rd * g.T_r[k] / (Rm * T) - 1.0);
+    return -g.g * rhop;
+}
 
 template <int TY>
 __global__ __launch_bounds__(64 * TY) void k_u_tend_lds(DevGrid g, Tend3Fields F, int kchunk, RKEpilogue E)
@@ -306,7 +412,7 @@ __global__ __launch_bounds__(64 * TY) void k_u_tend_lds(DevGrid g, Tend3Fields F
     }
 }
 
-// z-momentum: k_w_tend_ring with the w y-stencil in an LDS tile and shared y-face fluxes.
+// z-momentum: every vertical stencil in a register ring, the w y-stencil in an LDS tile and shared y-face fluxes.
 // BM (buoyancy mode) 0: anelastic buoyancy from T, q;  3: the same with the diagnosed q^v, q^l of saturation adjustment;
 // 1: none (SlowTendencyMode);  2: compressible slow vertical
 // momentum  G^s = G_adv - dz(p - p_r) - g Iz(rho - rho_r)  with F.T = pressure, F.q = total density

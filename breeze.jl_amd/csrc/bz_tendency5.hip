@@ -81,7 +81,7 @@ void bzi_lean_teardown(bz_ctx *ctx)
     ctx->ev_fork = ctx->ev_join = nullptr;
 }
 
-// z-chunking of the LDS-tiled kernels (same rule as pick_chunk_lds of bz_tendency3.hip)
+// z-chunking of the LDS-tiled kernels (same rule as pick_chunk_lds of bz_tendency4.hip)
 // fine: chunks of >= 64 levels and >= 4096 blocks instead of >= 128 levels and >= 1024 blocks.  Measured at 512^3 in Float64 (chunk length
 // 512 / 256 / 128 / 64 / 32 / 16): scalar pair 3.10 / 3.05 / 2.99 / 2.97 / 2.98 / 3.04 ms, x momentum 1.61 / 1.60 / 1.55 / 1.54 / 1.57 / 1.65,
 // z momentum 2.03 / 2.00 / 1.99 / 1.98 / 1.99 / 2.09 — eight blocks per tile column keep every XCD's resident blocks closer together in z than

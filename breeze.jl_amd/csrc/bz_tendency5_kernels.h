@@ -17,7 +17,7 @@
 #pragma once
 #include "bz_internal.h"
 #include "bz_weno.h"
-#include "bz_tendency3_kernels.h"
+#include "bz_tendency4_kernels.h"      // Tend3Fields, adv_x / adv_y, hflux, flux_x_at, vflux, buoyancy3
 
 // element index type of the momentum kernels: 64-bit, so that the +-1, +-2, +-3 neighbours of a row fold into the immediate offset
 // of one address per array and level (with 32-bit unsigned indices every neighbour costs its own address arithmetic: measured
@@ -558,7 +558,7 @@ __global__ __launch_bounds__(64 * TY) __attribute__((amdgpu_waves_per_eu(BZ5_SCA
 }
 
 // out-of-wave x fluxes of the momentum kernels with the advected velocity derived from its momentum component
-// (flux_x_at of bz_tendency3_kernels.h with c = m / rho)
+// (flux_x_at of bz_tendency4_kernels.h with c = m / rho)
 // By: walls in y — buffer of the y-face the advecting flux of the v kernel is interpolated to (3: order 4, the periodic case)
 template <int KIND>
 __device__ __forceinline__ double flux_x_lean(const DevGrid &g, const Tend3Fields &F, const double *__restrict__ m, int i, int j, int k, int By = 3)

@@ -76,6 +76,48 @@ def test_mixed_order_tendencies_match_oracle(oracle, bz, orders):
         assert relerr(got, want) < 2e-11, (n, relerr(got, want))
 
 
+@pytest.mark.gpu
+@pytest.mark.parametrize("orders", [(5, 5), (9, 5), (9, 9)])
+def test_shared_tail_of_the_three_tendency_sequences(oracle, bz, orders):
+    """bz_compute_tendencies reaches the order-independent terms (tracers, relaxation, forcing stack) from three places — all order 5,
+    different orders, all order 7 / 9 — through one tail (csrc/bz_tendency.hip: finish_tendencies): every tendency array of a model
+    with two tracers, two sponges, an f-plane and a geostrophic forcing against the oracle."""
+    from oracle.forcings import ColumnForcings
+    from test_relaxation import _columns, theta_ref
+    f, ug = 1e-4, 15.0
+    size = (16, 12, 10)
+    g0 = oracle.Grid(size, halo=(5, 5, 5), **EXT)
+    okw = dict(tracers=2, forcings=ColumnForcings(Fu=-f * 0.0 * g0.zc, Fv=f * ug + 0.0 * g0.zc, coriolis_f=f))
+    grid = bz.RectilinearGrid(size, halo=(5, 5, 5), **EXT)
+    ref = bz.ReferenceState(grid, potential_temperature=300.0)
+    rho = ref.density[grid.Hz:grid.Hz + grid.Nz]
+    mask = bz.GaussianMask(center=1000.0, width=200.0)
+    geo = bz.geostrophic_forcings(lambda z: ug, lambda z: 0.0)
+    forcing = {"ρw": bz.Relaxation(rate=0.01, mask=mask, target=0.0), "ρθ": bz.Relaxation(rate=0.01, mask=mask, target=rho * theta_ref(g0.zc)),
+               "u": geo.u, "v": geo.v}
+    g, om, hm = _pair(oracle, bz, size, *orders, okw=okw, hkw=dict(tracers=("a", "b"), coriolis=bz.FPlane(f=f), forcing=forcing))
+    om.relaxation = _columns(g, om.ref, ("rw", "rtheta"))
+    randomize(om, seed=17)
+    x, y, z = g.nodes("ccc")
+    rho_c = om.ref.density[g.Hz:g.Hz + g.Nz][:, None, None]
+    rng = np.random.default_rng(5)
+    for t, n in enumerate(("rc0", "rc1")):
+        c = 1.0 + 0.5 * np.cos(2 * np.pi * (y / 1200.0 + t / 3.0)) * np.sin(2 * np.pi * x / 1600.0) + 0 * z + 0.1 * rng.standard_normal((g.Nz, g.Ny, g.Nx))
+        g.interior(getattr(om, n))[...] = rho_c * c
+    om.update_state()
+    push_state(om, hm, names=("ru", "rv", "rw", "rtheta", "rq"))
+    for t, n in enumerate(("a", "b")):
+        hm.tracers[n].set_interior(g.interior(getattr(om, f"rc{t}")))
+    bz.update_state_(hm, compute_tendencies=True)
+    hm.synchronize()
+    errs = {}
+    for n, k in list(PROG.items()) + [("rc0", "a"), ("rc1", "b")]:
+        got, want = hm.G[k].interior_cpu(), g.interior(om.G[n], zface=(n == "rw"))
+        errs[n] = relerr(got, want)
+    print("SHARED TAIL", orders, " ".join(f"{n}={e:.2e}" for n, e in errs.items()))
+    assert all(e < 2e-11 for e in errs.values()), errs
+
+
 def _steps(g, om, hm, n, dt, tol, extra=()):
     for _ in range(n):
         om.time_step(dt)

@@ -5,7 +5,6 @@
 #include <vector>
 #include <cmath>
 #include "../breeze.jl_amd/csrc/bz_tendency.hip"   // gen-1 kernels (also provides bz_compute_tendencies)
-#include "../breeze.jl_amd/csrc/bz_tendency3_kernels.h"
 #include "../breeze.jl_amd/csrc/bz_tendency4_kernels.h"
 #define CK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("%s: %s\n", #x, hipGetErrorString(e)); exit(1); } } while (0)
 
@@ -63,10 +62,6 @@ int main(int argc, char** argv) {
     double *th = mk(300, 3, 7), *q = mk(5e-3, 2e-3, 8), *TT = mk(280, 5, 9), *G0 = mk(0, 0, 10), *G1 = mk(0, 0, 11);
     double cells = (double)Nx * Ny * Nz;
     auto rep = [&](const char* name, float ms) { printf("%-52s %8.3f ms  %7.1f ps/cell\n", name, ms, ms * 1e9 / cells); fflush(stdout); };
-    Tend3Fields F3; F3.ru = ru; F3.rv = rv; F3.rw = rw; F3.u = u; F3.v = v; F3.w = w; F3.T = TT; F3.q = q; F3.G = G0;
-#define RUN3(KIND, CPTR, RR, TYWV, KC) F3.c = CPTR; rep("gen3 " #KIND " R=" #RR " TYW=" #TYWV " kc=" #KC, timeit([&] { \
-        dim3 grid((Nx + 63) / 64, (Ny + RR * TYWV - 1) / (RR * TYWV), ((KIND == T3_W ? Nz - 1 : Nz) + KC - 1) / KC), block(64, TYWV); \
-        hipLaunchKernelGGL((k_tend3<KIND, RR, TYWV>), grid, block, 0, 0, dg, F3, KC); }))
     {
         dim3 b1(64, 4), g1((Nx + 63) / 64, (Ny + 3) / 4, 4); int kc1 = (Nz + 3) / 4;
         rep("probe: ring + velocities only", timeit([&] { hipLaunchKernelGGL(k_probe<0>, g1, b1, 0, 0, dg, G0, u, v, w, th, kc1); }));
@@ -83,13 +78,14 @@ int main(int argc, char** argv) {
         rep("gen1 v", timeit([&] { hipLaunchKernelGGL(k_v_tendency, g1, b1, 0, 0, dg, G0, ru, rv, rw, v, kc1, RKEpilogue()); }));
         rep("gen1 w", timeit([&] { hipLaunchKernelGGL(k_w_tendency, g1, b1, 0, 0, dg, G0, ru, rv, rw, w, TT, q, kc1); }));
     }
-    {   // fused scalar pair: gen-3 (loads) vs gen-4 (LDS tile), with a result comparison
+    {   // fused scalar pair: gen-1 (one launch per scalar) vs gen-4 (LDS tile), with a result comparison
         auto cmp = [&](const char* what) {
             std::vector<double> x(nc), y(nc);
             CK(hipMemcpy(x.data(), G0, nc * sizeof(double), hipMemcpyDeviceToHost)); CK(hipMemcpy(y.data(), G1, nc * sizeof(double), hipMemcpyDeviceToHost));
             return std::make_pair(x, y); };
-        dim3 b3(64, 4), g3((Nx + 63) / 64, (Ny + 3) / 4, (Nz + 63) / 64);
-        rep("pair gen3 (k_scalar_pair<4>) kc=64", timeit([&] { hipLaunchKernelGGL((k_scalar_pair<4>), g3, b3, 0, 0, dg, u, v, w, th, q, G0, G1, 64); }));
+        dim3 b1(64, 4), g1((Nx + 63) / 64, (Ny + 3) / 4, 4); int kc1 = (Nz + 3) / 4;
+        rep("pair gen1 (2 x k_scalar_tendency)", timeit([&] { hipLaunchKernelGGL(k_scalar_tendency, g1, b1, 0, 0, dg, G0, u, v, w, th, kc1);
+                                                              hipLaunchKernelGGL(k_scalar_tendency, g1, b1, 0, 0, dg, G1, u, v, w, q, kc1); }));
         auto ref = cmp("ref");
         CK(hipMemset(G0, 0, nc * sizeof(double))); CK(hipMemset(G1, 0, nc * sizeof(double)));
         dim3 b8(64, 8), g8((Nx + 63) / 64, (Ny + 7) / 8, (Nz + 63) / 64);
@@ -97,7 +93,7 @@ int main(int argc, char** argv) {
         auto got = cmp("got");
         double e0 = 0, e1 = 0, s0 = 0, s1 = 0;
         for (size_t n = 0; n < nc; ++n) { e0 = fmax(e0, fabs(got.first[n] - ref.first[n])); e1 = fmax(e1, fabs(got.second[n] - ref.second[n])); s0 = fmax(s0, fabs(ref.first[n])); s1 = fmax(s1, fabs(ref.second[n])); }
-        printf("   gen4 vs gen3: max|dG_theta| = %.3e (scale %.3e), max|dG_q| = %.3e (scale %.3e)\n", e0, s0, e1, s1);
+        printf("   gen4 vs gen1: max|dG_theta| = %.3e (scale %.3e), max|dG_q| = %.3e (scale %.3e)\n", e0, s0, e1, s1);
         rep("pair gen4 LDS TY=4 kc=128", timeit([&] { hipLaunchKernelGGL((k_scalar_pair_lds<4>), dim3((Nx + 63) / 64, (Ny + 3) / 4, (Nz + 127) / 128), dim3(64, 4), 0, 0, dg, u, v, w, th, q, G0, G1, 128, RKEpilogue(), th, q); }));
         rep("pair gen4 LDS TY=4 kc=256", timeit([&] { hipLaunchKernelGGL((k_scalar_pair_lds<4>), dim3((Nx + 63) / 64, (Ny + 3) / 4, (Nz + 255) / 256), dim3(64, 4), 0, 0, dg, u, v, w, th, q, G0, G1, 256, RKEpilogue(), th, q); }));
         dim3 g8b((Nx + 63) / 64, (Ny + 7) / 8, (Nz + 127) / 128);
@@ -105,7 +101,7 @@ int main(int argc, char** argv) {
         dim3 b4(64, 4), g4((Nx + 63) / 64, (Ny + 3) / 4, (Nz + 63) / 64);
         rep("pair gen4 LDS TY=4 kc=64", timeit([&] { hipLaunchKernelGGL((k_scalar_pair_lds<4>), g4, b4, 0, 0, dg, u, v, w, th, q, G0, G1, 64, RKEpilogue(), th, q); }));
     }
-    {   // momentum: gen-1 / ring kernels vs the LDS y-tile kernels, with result comparison
+    {   // momentum: gen-1 kernels vs the LDS y-tile kernels, with result comparison
         auto grab = [&](double* p) { std::vector<double> x(nc); CK(hipMemcpy(x.data(), p, nc * sizeof(double), hipMemcpyDeviceToHost)); return x; };
         auto diff = [&](const std::vector<double>& a, const std::vector<double>& b) { double e = 0, s = 0; for (size_t n = 0; n < nc; ++n) { e = fmax(e, fabs(a[n] - b[n])); s = fmax(s, fabs(b[n])); } printf("   max|diff| = %.3e (scale %.3e)\n", e, s); };
         dim3 b1(64, 4), g1((Nx + 63) / 64, (Ny + 3) / 4, 4); int kc1 = (Nz + 3) / 4;
@@ -130,31 +126,16 @@ int main(int argc, char** argv) {
         rep("v LDS TY=8 kc=64", timeit([&] { hipLaunchKernelGGL((k_v_tend_lds<8>), dim3((Nx + 63) / 64, (Ny + 7) / 8, (Nz + 63) / 64), dim3(64, 8), 0, 0, dg, Fm, 64, RKEpilogue()); }));
         CK(hipMemset(G0, 0, nc * sizeof(double)));
         Fm.c = w;
-        rep("w ring TYW=4 kc=64", timeit([&] { hipLaunchKernelGGL((k_w_tend_ring<4>), dim3((Nx + 63) / 64, (Ny + 3) / 4, (Nz - 1 + 63) / 64), dim3(64, 4), 0, 0, dg, Fm, 64, RKEpilogue()); }));
+        rep("w gen1", timeit([&] { hipLaunchKernelGGL(k_w_tendency, dim3(g1.x, g1.y, (Nz - 1 + kc1 - 1) / kc1), b1, 0, 0, dg, G0, ru, rv, rw, w, TT, q, kc1); }));
         auto wref = grab(G0); CK(hipMemset(G0, 0, nc * sizeof(double)));
         rep("w LDS TY=8 kc=64", timeit([&] { hipLaunchKernelGGL((k_w_tend_lds<8>), dim3((Nx + 63) / 64, (Ny + 7) / 8, (Nz - 1 + 63) / 64), dim3(64, 8), 0, 0, dg, Fm, 64, RKEpilogue()); }));
         diff(grab(G0), wref);
         rep("w LDS TY=8 kc=128", timeit([&] { hipLaunchKernelGGL((k_w_tend_lds<8>), dim3((Nx + 63) / 64, (Ny + 7) / 8, (Nz - 1 + 127) / 128), dim3(64, 8), 0, 0, dg, Fm, 128, RKEpilogue()); }));
         rep("w LDS TY=8 kc=256", timeit([&] { hipLaunchKernelGGL((k_w_tend_lds<8>), dim3((Nx + 63) / 64, (Ny + 7) / 8, (Nz - 1 + 255) / 256), dim3(64, 8), 0, 0, dg, Fm, 256, RKEpilogue()); }));
-        rep("w ring TYW=4 kc=128", timeit([&] { hipLaunchKernelGGL((k_w_tend_ring<4>), dim3((Nx + 63) / 64, (Ny + 3) / 4, (Nz - 1 + 127) / 128), dim3(64, 4), 0, 0, dg, Fm, 128, RKEpilogue()); }));
         CK(hipMemset(G0, 0, nc * sizeof(double)));
         hipLaunchKernelGGL((k_w_tend_lds<4>), dim3((Nx + 63) / 64, (Ny + 3) / 4, (Nz - 1 + 63) / 64), dim3(64, 4), 0, 0, dg, Fm, 64, RKEpilogue());
-        printf("w LDS TY=4 vs ring:"); diff(grab(G0), wref);
+        printf("w LDS TY=4 vs gen1:"); diff(grab(G0), wref);
         rep("w LDS TY=4 kc=64", timeit([&] { hipLaunchKernelGGL((k_w_tend_lds<4>), dim3((Nx + 63) / 64, (Ny + 3) / 4, (Nz - 1 + 63) / 64), dim3(64, 4), 0, 0, dg, Fm, 64, RKEpilogue()); }));
     }
-    RUN3(T3_SCALAR, th, 1, 4, 64);
-    RUN3(T3_SCALAR, th, 2, 4, 64);
-    RUN3(T3_SCALAR, th, 2, 4, 128);
-    RUN3(T3_SCALAR, th, 2, 2, 64);
-    RUN3(T3_SCALAR, th, 3, 4, 64);
-    RUN3(T3_SCALAR, th, 4, 4, 64);
-    RUN3(T3_U, u, 1, 4, 64);
-    RUN3(T3_U, u, 2, 4, 64);
-    RUN3(T3_U, u, 3, 4, 64);
-    RUN3(T3_V, v, 1, 4, 64);
-    RUN3(T3_V, v, 2, 4, 64);
-    RUN3(T3_W, w, 1, 4, 64);
-    RUN3(T3_W, w, 2, 4, 64);
-    RUN3(T3_W, w, 3, 4, 64);
     return 0;
 }
