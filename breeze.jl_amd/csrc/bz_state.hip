@@ -128,6 +128,7 @@ __global__ __launch_bounds__(TX *TY) void k_max_abs_div(DevGrid g, const double 
         double b = g.flat_y ? 0.0 : Ay * rv[n + g.Sx] - Ay * rv[n];
         double c = Az * rw[n + g.Sxy] - Az * rw[n];
         d = fabs(g.Vinv_c[k] * (a + b + c));
+        if (d != d) d = bz_real_inf();      // NaN momentum: fmax below would drop it behind a finite lane; report +Inf, never a finite value
     }
     for (int o = 32; o > 0; o >>= 1) d = fmax(d, __shfl_down(d, o));
     if ((threadIdx.x & 63) == 0) atomicMax(out, bz_real_bits(d));

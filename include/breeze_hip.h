@@ -736,7 +736,8 @@ int bz_profile_reset(bz_ctx *ctx);
 int bz_profile_count(bz_ctx *ctx);
 int bz_profile_get(bz_ctx *ctx, int idx, const char **name, double *total_ms, int64_t *launches);
 /* divergence of momentum, max-abs over the interior, into *out (host); diagnostic for tests
- * (test/anelastic_pressure_solver_nonhydrostatic.jl:45-46). Synchronises. */
+ * (test/anelastic_pressure_solver_nonhydrostatic.jl:45-46). Fills the momentum halos itself; non-finite momentum reports +Inf,
+ * never a finite value (a NaN in any cell, or an infinite momentum, cannot pass an `assert div < tol`). Synchronises. */
 int bz_max_abs_divergence(bz_ctx *ctx, const bz_state *s, double *out);
 
 /* hipGraph replay of whole time steps (csrc/bz_graph.hip).  bz_time_step_anelastic / bz_time_step_compressible are pure functions of
