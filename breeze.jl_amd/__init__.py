@@ -28,3 +28,7 @@ from .model import compute_closure_fields_, compute_flux_bc_tendencies_  # noqa:
 from .forcings import (FilteredSurfaceVelocities, FittedStabilityFunction, PolynomialCoefficient, RichardsonNumberMapping,  # noqa: F401,E402
                        StabilityFunctionParameters)
 from . import benchmarks  # noqa: F401,E402
+from . import diagnostics  # noqa: F401,E402
+from .diagnostics import (Average, DewpointTemperature, EquivalentPotentialTemperature, LiquidIcePotentialTemperature,  # noqa: F401,E402
+                          PotentialTemperature, RelativeHumidity, SaturationSpecificHumidity, StabilityEquivalentPotentialTemperature,
+                          StaticEnergy, VirtualPotentialTemperature, compute_diagnostics, horizontal_average)

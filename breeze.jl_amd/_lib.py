@@ -179,6 +179,22 @@ class bz_split_explicit(C.Structure):
                 ("substep_distribution", C.c_int32), ("substep_float_bytes", C.c_int32), ("damping_length_scale", C.c_double)]
 
 
+class bz_diagnostic_inputs(C.Structure):
+    _fields_ = ([(n, C.c_void_p) for n in ("temperature", "vapor", "liquid", "liquid_2", "moisture", "pressure", "density")] +
+                [(n, C.c_double) for n in ("liquid_latent_heat", "liquid_heat_capacity", "energy_reference_temperature",
+                                           "triple_point_temperature", "triple_point_pressure")])
+
+
+# bz_diagnostic_kind of include/breeze_hip.h
+DIAGNOSTIC_KINDS = ("POTENTIAL_TEMPERATURE", "LIQUID_ICE_POTENTIAL_TEMPERATURE", "VIRTUAL_POTENTIAL_TEMPERATURE",
+                    "EQUIVALENT_POTENTIAL_TEMPERATURE", "STABILITY_EQUIVALENT_POTENTIAL_TEMPERATURE", "STATIC_ENERGY",
+                    "RELATIVE_HUMIDITY", "SATURATION_SPECIFIC_HUMIDITY", "SATURATION_SPECIFIC_HUMIDITY_EQUILIBRIUM",
+                    "SATURATION_SPECIFIC_HUMIDITY_TOTAL_MOISTURE", "DEWPOINT_TEMPERATURE")
+BZ_DIAG = {name: code for code, name in enumerate(DIAGNOSTIC_KINDS)}
+BZ_DIAG_DENSITY_WEIGHTED = 0x100
+BZ_MAX_DIAGNOSTICS = 24
+
+
 class bz_exner_reference_state(C.Structure):
     _fields_ = [("standard_pressure", C.c_double), ("pressure", _dp), ("density", _dp)]
 
@@ -283,6 +299,9 @@ SYMBOLS = {
     "bz_profile_get": (C.c_int, [_ctx, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_double),
                                  C.POINTER(C.c_int64)]),
     "bz_max_abs_divergence": (C.c_int, [_ctx, _sp, C.POINTER(C.c_double)]),
+    "bz_compute_diagnostics": (C.c_int, [_ctx, _sp, C.POINTER(bz_diagnostic_inputs), C.c_int32, C.POINTER(C.c_int32),
+                                         C.POINTER(C.c_void_p)]),
+    "bz_horizontal_average": (C.c_int, [_ctx, C.c_void_p, C.c_int, _dp]),
 }
 
 

@@ -403,6 +403,7 @@ extern "C" void bz_destroy(bz_ctx *ctx)
     if (ctx->d_columns) hipFree(ctx->d_columns);
     bzi_forcing_teardown(ctx);
     bzi_closure_teardown(ctx);
+    bzi_diagnostics_teardown(ctx);
     if (ctx->d_scalar) hipFree(ctx->d_scalar);
     if (ctx->d_gflux) hipFree(ctx->d_gflux);
     delete ctx;

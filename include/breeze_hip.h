@@ -727,6 +727,66 @@ int bz_cell_advection_timescale(bz_ctx *ctx, const double *u, const double *v, c
  * interior value is NaN.  Synchronises. */
 int bz_any_nan(bz_ctx *ctx, const double *field, int z_face, int32_t *out);
 
+/* ---- output diagnostics: what the run! loop evaluates between steps for its output writers (csrc/bz_diagnostics.hip) ----
+ * KernelFunctionOperations of src/AtmosphereModels/Diagnostics/ and src/Microphysics/microphysics_diagnostics.jl, evaluated by one
+ * pointwise kernel.  Notation: q = (q^v, q^l, q^i = 0), R_m = q^d R^d + q^v R^v, c_pm = q^d c_pd + q^v c_pv + q^l c_l,
+ * rho* = p / (R_m T), p^v = rho* q^v R^v T, p^v+(T) the Clausius-Clapeyron pressure over a planar liquid surface, H = p^v / p^v+.
+ *   POTENTIAL_TEMPERATURE                      theta = T / (p/p_st)^(R_m/c_pm)                      (potential_temperatures.jl:538-616)
+ *   LIQUID_ICE_POTENTIAL_TEMPERATURE           theta (1 - L_lr q^l / (c_pm T))
+ *   VIRTUAL_POTENTIAL_TEMPERATURE              T / (p/p_st)^(R^d/c_pd) (1 + (R^v/R^d - 1) q^v - q^l)
+ *   EQUIVALENT_POTENTIAL_TEMPERATURE           T (p_st/p)^(R^d/c_pm) exp(L_l(T) q^v / (c_pm T)) H^(-R^v q^v / c_pm),
+ *                                              L_l(T) = L_lr + (c_pv - c_l)(T - T_r)
+ *   STABILITY_EQUIVALENT_POTENTIAL_TEMPERATURE theta^e (T/T_r)^(c_l q^l / c_pm)
+ *   STATIC_ENERGY                              c_pm T + g z_c[k] - L_lr q^l                         (static_energy.jl:94-120)
+ *   RELATIVE_HUMIDITY                          p^v / max(p^v+(T), eps)                              (microphysics_diagnostics.jl:139-170)
+ *   SATURATION_SPECIFIC_HUMIDITY               :prognostic, p^v+ / (rho* R^v T)                     (saturation_specific_humidity.jl:124-149)
+ *   SATURATION_SPECIFIC_HUMIDITY_EQUILIBRIUM   :equilibrium, equilibrium_saturation_specific_humidity(T, p, q^ve) (vapor_saturation.jl:216-230)
+ *   SATURATION_SPECIFIC_HUMIDITY_TOTAL_MOISTURE :total_moisture, eps p^v+ / (p + (eps - 1) p^v+), eps = R^d / R^v
+ *   DEWPOINT_TEMPERATURE                       secant inversion of p^v+(T+) = p^v: T where p^v+(T) - p^v <= 0, else from the guesses T and
+ *                                              T - 20 (1 - H) with SecantSolver(reltol = 1e-4, abstol = 0, maxiter = 10) scaled by p^v
+ *                                              (vapor_saturation.jl:313-331)
+ * kind | BZ_DIAG_DENSITY_WEIGHTED is the density-weighted flavour (rho x) of a potential temperature or of the static energy. */
+typedef enum bz_diagnostic_kind {
+    BZ_DIAG_POTENTIAL_TEMPERATURE = 0,
+    BZ_DIAG_LIQUID_ICE_POTENTIAL_TEMPERATURE = 1,
+    BZ_DIAG_VIRTUAL_POTENTIAL_TEMPERATURE = 2,
+    BZ_DIAG_EQUIVALENT_POTENTIAL_TEMPERATURE = 3,
+    BZ_DIAG_STABILITY_EQUIVALENT_POTENTIAL_TEMPERATURE = 4,
+    BZ_DIAG_STATIC_ENERGY = 5,
+    BZ_DIAG_RELATIVE_HUMIDITY = 6,
+    BZ_DIAG_SATURATION_SPECIFIC_HUMIDITY = 7,
+    BZ_DIAG_SATURATION_SPECIFIC_HUMIDITY_EQUILIBRIUM = 8,
+    BZ_DIAG_SATURATION_SPECIFIC_HUMIDITY_TOTAL_MOISTURE = 9,
+    BZ_DIAG_DEWPOINT_TEMPERATURE = 10,
+    BZ_DIAG_KIND_COUNT = 11
+} bz_diagnostic_kind;
+#define BZ_DIAG_DENSITY_WEIGHTED 0x100
+#define BZ_MAX_DIAGNOSTICS 24
+/* The inputs are passed explicitly (the kernel knows no model): DEVICE parent arrays at cell centres.
+ *   temperature, vapor   T and q^v (grid_moisture_fractions: q^t without microphysics, the stored q^v otherwise)
+ *   liquid, liquid_2     q^l; either may be NULL (read as 0); liquid_2 is added to liquid (Kessler: q^cl + q^r, dcmip2016_kessler.jl:298-303)
+ *   moisture             q^ve, the specific prognostic moisture: read by the :equilibrium flavour only
+ *   pressure, density    3-D fields (CompressibleDynamics: dynamics_pressure_for_potential_temperature); if either is NULL the
+ *                        context's reference-state columns p_r[k], rho_r[k] are used
+ * and the liquid CondensedPhase, energy reference temperature and triple point of ThermodynamicConstants
+ * (src/Thermodynamics/thermodynamics_constants.jl:92,182-194), which a context without microphysics does not hold. */
+typedef struct bz_diagnostic_inputs {
+    const double *temperature, *vapor, *liquid, *liquid_2, *moisture, *pressure, *density;
+    double liquid_latent_heat, liquid_heat_capacity;
+    double energy_reference_temperature, triple_point_temperature, triple_point_pressure;
+} bz_diagnostic_inputs;
+/* n >= 1 diagnostics (kinds[m], at most BZ_MAX_DIAGNOSTICS) into n cell-centred parent arrays outputs[m] from ONE read of the inputs; only
+ * the interior is written (fill halos with bz_fill_halo_regions).  Asynchronous on the context's stream.  If the context's diagnostics are
+ * stale (bz_diagnostics_stale) they are rebuilt first from `s` (NULL is accepted while they are current, and on compressible contexts).
+ * Works on y-slab contexts as on any other: the kernel is pointwise. */
+int bz_compute_diagnostics(bz_ctx *ctx, const bz_state *s, const bz_diagnostic_inputs *inputs, int32_t n, const int32_t *kinds,
+                           double *const *outputs);
+/* Average(field, dims = (1, 2)): the mean over the interior Nx x Ny cells of every level of one centre (z_face = 0: Nz levels) or z-face
+ * (z_face != 0: Nz + 1 levels) parent array, into `profile` (HOST).  Halos are never read.  Deterministic: fixed block and summation order,
+ * no floating-point atomics; the level sum is divided by Nx Ny.  Synchronises.  y-slab contexts (bz_create_slab,
+ * bz_create_compressible_slab) return BZ_ERR_UNSUPPORTED. */
+int bz_horizontal_average(bz_ctx *ctx, const double *field, int z_face, double *profile);
+
 /* ---- instrumentation (not part of the reference interface) ---- */
 /* When enabled, every kernel group is bracketed by hipEvents on the ctx stream. */
 int bz_profile_enable(bz_ctx *ctx, int on);

@@ -570,6 +570,31 @@ function compressible_update_state!(model, ctx; compute_tendencies = true)
     return nothing
 end
 
+# ---- output diagnostics (csrc/bz_diagnostics.hip): the operations of src/AtmosphereModels/Diagnostics/ and RelativeHumidity evaluated by one
+# pointwise kernel, and Average(field, dims = (1, 2)).  An extension specialises `compute!(::Field{<:Any, <:Any, <:Any, <:KernelFunctionOperation{...}})`
+# on the kernel-function types below and forwards here; `kinds` are bz_diagnostic_kind codes (| BZ_DIAG_DENSITY_WEIGHTED for the :density flavours).
+struct BzDiagnosticInputs
+    temperature::Ptr{Cvoid}; vapor::Ptr{Cvoid}; liquid::Ptr{Cvoid}; liquid_2::Ptr{Cvoid}; moisture::Ptr{Cvoid}
+    pressure::Ptr{Cvoid}; density::Ptr{Cvoid}
+    liquid_latent_heat::Cdouble; liquid_heat_capacity::Cdouble
+    energy_reference_temperature::Cdouble; triple_point_temperature::Cdouble; triple_point_pressure::Cdouble
+end
+const BZ_DIAG_DENSITY_WEIGHTED = Int32(0x100)
+
+"n diagnostics into n centre fields from one read of T, q^v, q^l (p, rho); `s` lets the library rebuild stale diagnostics first."
+function compute_diagnostics!(ctx, s::BzState, inputs::BzDiagnosticInputs, kinds::Vector{Int32}, outputs::Vector{Ptr{Cvoid}})
+    check(ccall((:bz_compute_diagnostics, libbreeze_hip), Cint,
+                (Ptr{Cvoid}, Ref{BzState}, Ref{BzDiagnosticInputs}, Int32, Ptr{Int32}, Ptr{Ptr{Cvoid}}),
+                ctx, s, inputs, length(kinds), kinds, outputs), "bz_compute_diagnostics", ctx)
+end
+
+"Average(field, dims = (1, 2)) of one centre or z-face parent array into a host profile of Nz (Nz + 1) values."
+function horizontal_average!(profile::Vector{Float64}, ctx, field::Ptr{Cvoid}, z_face::Bool)
+    check(ccall((:bz_horizontal_average, libbreeze_hip), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Cdouble}), ctx, field, z_face, profile),
+          "bz_horizontal_average", ctx)
+    return profile
+end
+
 # hipGraph replay of whole steps (csrc/bz_graph.hip): opt-in, pays with a fixed Δt on launch-bound grids; Oceananigans fields keep
 # their device arrays for the life of the model, which is what a recorded step relies on
 graph_replay!(ctx, on::Bool = true) = check(ccall((:bz_graph_enable, libbreeze_hip), Cint, (Ptr{Cvoid}, Cint), ctx, on), "bz_graph_enable", ctx)
