@@ -302,6 +302,10 @@ SYMBOLS = {
     "bz_compute_diagnostics": (C.c_int, [_ctx, _sp, C.POINTER(bz_diagnostic_inputs), C.c_int32, C.POINTER(C.c_int32),
                                          C.POINTER(C.c_void_p)]),
     "bz_horizontal_average": (C.c_int, [_ctx, C.c_void_p, C.c_int, _dp]),
+    "bz_set_horizontal_nodes": (C.c_int, [_ctx, _dp, _dp]),
+    "bz_azimuthal_mean": (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_int32, _dp,
+                                    C.POINTER(C.c_int64)]),
+    "bz_polar_winds": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_void_p]),
 }
 
 

@@ -6,6 +6,10 @@ microphysics_diagnostics.jl) — behind bz_compute_diagnostics / bz_horizontal_a
     θᵛ, θᵉ = compute_diagnostics(model, [VirtualPotentialTemperature(model), EquivalentPotentialTemperature(model)])   # one launch
     profile = Average(RelativeHumidity(model), dims=(1, 2)).compute()      # numpy, Nz values
 
+    vθ = TangentialVelocity(model, center=(0, 0)).compute()     # (−y uᶜ + x vᶜ)/r at cell centres
+    v̄θ = azimuthal_mean(vθ, radius=150e3, Nr=30)               # .data (Nr, Nz), .counts, .r, .z
+    θ̄ = azimuthal_mean(LiquidIcePotentialTemperature(model), radius=150e3, Nr=30)      # same geometry: the ring plan is reused
+
 Moisture fractions are picked from the model as grid_moisture_fractions does: no microphysics qᵛ = qᵗ and no liquid;
 SaturationAdjustment the stored qᵛ, qˡ; Kessler qᵛ, qᶜˡ + qʳ.  Anelastic models read the reference-state columns; a compressible model
 hands its own p and ρ fields to the potential temperatures and its dynamics.reference_state (required) to the other kinds.
@@ -223,3 +227,129 @@ class Average:
     def compute(self):
         field = self.operand.compute() if isinstance(self.operand, _Operation) else self.operand
         return horizontal_average(self.model, field)
+
+
+# ---- azimuthal means and polar winds (csrc/bz_azimuthal.hip; src/AtmosphereModels/Diagnostics/azimuthal_mean.jl) ---------------------
+MAX_RINGS, MAX_SUBCELLS = 1024, 16      # the limits of bz_azimuthal_mean (include/breeze_hip.h)
+
+
+def _is_slab(model):
+    from .compressible import SlabCompressibleModel
+    from .distributed import LibrarySlabAtmosphereModel, SlabStepper
+    return isinstance(model, (SlabCompressibleModel, LibrarySlabAtmosphereModel, SlabStepper))
+
+
+def _resolve_model(operand, model, what):
+    if isinstance(operand, (_Operation, _PolarVelocity)):
+        return operand.model
+    if model is None:
+        owner = getattr(operand, "_owner", None)
+        model = owner() if owner is not None else None
+    if model is None:
+        raise ValueError(f"{what}: pass model=... for a field that does not know its model")
+    return model
+
+
+def _horizontal_model(model, what):
+    """The checks every polar operation makes on the host, before any device call."""
+    if model.grid.topology[1] == "Flat":
+        raise NotImplementedError(f"{what}: not defined on a Flat y")
+    if _is_slab(model):
+        raise NotImplementedError(f"{what}: not implemented on y-slab models (the rings span the ranks)")
+
+
+def _set_nodes(model):
+    """Hand the grid's own xᶜ, yᶜ to the context, once per model."""
+    if getattr(model, "_horizontal_nodes", None) is None:
+        T = model._T
+        nodes = [np.ascontiguousarray(a, dtype=T.np_real) for a in (model.grid.xᶜ, model.grid.yᶜ)]
+        model._check(model._lib.bz_set_horizontal_nodes(model._ctx, *[a.ctypes.data_as(C.POINTER(T.real)) for a in nodes]),
+                     "bz_set_horizontal_nodes")
+        model._horizontal_nodes = nodes
+
+
+def _center(center):
+    cx, cy = center
+    return float(cx), float(cy)
+
+
+class AzimuthalMean:
+    """What azimuthal_mean returns: `.data` (Nr, nlev) as interior(c̄, :, 1, :), `.counts` samples per ring, `.r` ring centres, `.z`."""
+
+    def __init__(self, data, counts, r, z):
+        self.data, self.counts, self.r, self.z = data, counts, r, z
+
+    def __repr__(self):
+        return f"AzimuthalMean({self.data.shape[0]} rings × {self.data.shape[1]} levels)"
+
+
+def azimuthal_mean(operand, radius, Nr, center=(0, 0), m=4, model=None):
+    """azimuthal_mean(field_or_operation; radius, Nr, center=(0, 0), m=4): the mean over Nr uniform rings on [0, radius] about `center`, by
+    binning m × m sub-cell centres per cell; a ring that catches no sample is NaN.  `model` is needed for a bare Field."""
+    Nr, m, radius = int(Nr), int(m), float(radius)
+    if not 1 <= Nr <= MAX_RINGS:
+        raise ValueError(f"azimuthal_mean: Nr must be between 1 and {MAX_RINGS}, received {Nr}")
+    if not 1 <= m <= MAX_SUBCELLS:
+        raise ValueError(f"azimuthal_mean: m must be between 1 and {MAX_SUBCELLS}, received {m}")
+    if not radius > 0 or not np.isfinite(radius):
+        raise ValueError(f"azimuthal_mean: radius must be positive, received {radius}")
+    cx, cy = _center(center)
+    model = _resolve_model(operand, model, "azimuthal_mean")
+    _horizontal_model(model, "azimuthal_mean")
+    if isinstance(operand, (_Operation, _PolarVelocity)):      # evaluates to a centre field of the model's grid: nothing to validate
+        field = operand.compute()
+    else:
+        field = operand
+        if (not isinstance(field, Field) or field.grid is not model.grid or field.dtype != model.temperature.dtype
+                or field.loc[0] is not Center or field.loc[1] is not Center):
+            raise ValueError("azimuthal_mean: the field must be a Field at (Center, Center, ·) of the model's grid")
+    if hasattr(field, "_fresh"):
+        field._fresh()      # a stale diagnostic field of the model is rebuilt first
+    _set_nodes(model)
+    g, T = model.grid, model._T
+    nlev = g.Nz + (1 if field.zface else 0)
+    prof = np.empty((nlev, Nr), dtype=T.np_real)
+    counts = np.empty(Nr, dtype=np.int64)
+    model._check(model._lib.bz_azimuthal_mean(model._ctx, C.c_void_p(field.ptr()), 1 if field.zface else 0, cx, cy, radius, Nr, m,
+                                              prof.ctypes.data_as(C.POINTER(T.real)), counts.ctypes.data_as(C.POINTER(C.c_int64))),
+                 "bz_azimuthal_mean")
+    Δr = radius / Nr
+    return AzimuthalMean(prof.T, counts, Δr * (np.arange(Nr) + 0.5), np.asarray(g.zᶠ if field.zface else g.zᶜ))
+
+
+class _PolarVelocity:
+    """A wind component in polar coordinates about `center`, at (Center, Center, Center) of one model."""
+    _slot = None
+
+    def __init__(self, model, center=(0, 0)):
+        _horizontal_model(model, type(self).__name__)
+        self.model, self.center = model, _center(center)
+
+    def compute(self, out=None):
+        """Evaluate into `out` (a centre Field of the model's grid; allocated when None) and fill its halos."""
+        model = self.model
+        if out is None:
+            out = Field(model.grid, (Center, Center, Center), model.device)
+        if out.grid is not model.grid or out.zface or out.dtype != model.temperature.dtype:
+            raise ValueError("the output must be a centre field of the model's grid")
+        u, v = model.velocities["u"], model.velocities["v"]
+        u._fresh()
+        _set_nodes(model)
+        ptrs = [None, None]
+        ptrs[self._slot] = C.c_void_p(out.ptr())
+        model._check(model._lib.bz_polar_winds(model._ctx, C.c_void_p(u.ptr()), C.c_void_p(v.ptr()), *self.center, *ptrs), "bz_polar_winds")
+        fill_halo_regions_(model, out)
+        return out
+
+    def __repr__(self):
+        return f"{type(self).__name__}(model, center={self.center})"
+
+
+class TangentialVelocity(_PolarVelocity):
+    """vθ = (−y uᶜ + x vᶜ)/r, (x, y) from `center`; NaN where a cell centre coincides with the centre, as the reference's Field."""
+    _slot = 0
+
+
+class RadialVelocity(_PolarVelocity):
+    """vʳ = (x uᶜ + y vᶜ)/r"""
+    _slot = 1

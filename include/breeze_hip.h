@@ -787,6 +787,38 @@ int bz_compute_diagnostics(bz_ctx *ctx, const bz_state *s, const bz_diagnostic_i
  * bz_create_compressible_slab) return BZ_ERR_UNSUPPORTED. */
 int bz_horizontal_average(bz_ctx *ctx, const double *field, int z_face, double *profile);
 
+/* ---- azimuthal means and polar winds (csrc/bz_azimuthal.hip; src/AtmosphereModels/Diagnostics/azimuthal_mean.jl of the reference) ---- */
+/* The cell-centre coordinates of the grid, x^c[0 .. Nx) and y^c[0 .. Ny) (HOST arrays, copied; xnodes / ynodes of the caller's grid at
+ * Center).  bz_grid carries spacings only, and the ring membership of a sample must be formed from the very coordinates the caller's grid
+ * holds, not from ones re-derived from extents.  Required once before bz_azimuthal_mean / bz_polar_winds.  Synchronises. */
+int bz_set_horizontal_nodes(bz_ctx *ctx, const double *xc, const double *yc);
+/* azimuthal_mean(field; radius, Nr, center = (center_x, center_y), m): the mean of one centre (z_face = 0: Nz levels) or z-face
+ * (z_face != 0: Nz + 1 levels) DEVICE parent array over Nr uniform rings on [0, radius], dr = radius / Nr, by binning an m x m block of
+ * sub-cell centres per cell:
+ *     x = (x^c[i] - center_x) + (2 si - m - 1) dx / (2 m),  y likewise,  1 <= si, sj <= m      (product, then quotient, then sum)
+ *     the sample is in ring ir (1-based) iff trunc(sqrt(x x + y y) / dr) + 1 == ir; samples past the radius fall in no ring
+ *     profile[k Nr + ir - 1] = sum of field[i, j, k] over the ring's samples / their number, NaN for a ring without samples
+ * all in the context's float type, without FMA contraction and with correctly rounded divide and sqrt, so that the ring of every sample is
+ * the one the reference's expression gives.  `profile` (HOST) has nlev x Nr entries, ring index fastest; `counts` (HOST, Nr entries, may
+ * be NULL) receives the number of samples per ring, the same for every level.  Halos are never read; the value of a cell without a sample
+ * inside the radius is not used at all.  A centre outside the domain is legal.
+ * Deterministic: the ring geometry is worked out once per (center, radius, Nr, m) and kept on the context; a ring's sum is accumulated in
+ * a fixed order (cell order within a wave's share, waves, then row slices), no floating-point atomics: two calls return the same bits.
+ * Runs on the context's stream and synchronises.  The caller rebuilds stale diagnostics first if `field` is one of them
+ * (bz_diagnostics_stale).
+ * Limits: 1 <= Nr <= 1024, 1 <= m <= 16, radius > 0, else BZ_ERR_INVALID with bz_last_error naming the argument.  Flat-y contexts and
+ * y-slab contexts (bz_create_slab, bz_create_compressible_slab) return BZ_ERR_UNSUPPORTED. */
+int bz_azimuthal_mean(bz_ctx *ctx, const double *field, int z_face, double center_x, double center_y, double radius, int32_t Nr, int32_t m,
+                      double *profile, int64_t *counts);
+/* Tangential and radial wind about (center_x, center_y) at cell centres, from the velocity parent arrays u (x faces) and v (y faces) with
+ * FILLED halos (the faces i + 1 = Nx and j + 1 = Ny are read):
+ *     u^c = (u[i] + u[i + 1]) / 2,  v^c = (v[j] + v[j + 1]) / 2,  x = x^c[i] - center_x,  y = y^c[j] - center_y,  r = sqrt(x x + y y)
+ *     tangential = (-y u^c + x v^c) / r,   radial = (x u^c + y v^c) / r
+ * Either output (DEVICE centre parent arrays) may be NULL; only the interior is written (fill halos with bz_fill_halo_regions).  There is no
+ * guard at r = 0: a cell centre that coincides with the centre gives NaN, as the reference's Field((-y u + x v) / r) does.  Asynchronous on
+ * the context's stream.  Flat-y contexts return BZ_ERR_UNSUPPORTED. */
+int bz_polar_winds(bz_ctx *ctx, const double *u, const double *v, double center_x, double center_y, double *tangential, double *radial);
+
 /* ---- instrumentation (not part of the reference interface) ---- */
 /* When enabled, every kernel group is bracketed by hipEvents on the ctx stream. */
 int bz_profile_enable(bz_ctx *ctx, int on);

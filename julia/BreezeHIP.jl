@@ -595,6 +595,43 @@ function horizontal_average!(profile::Vector{Float64}, ctx, field::Ptr{Cvoid}, z
     return profile
 end
 
+"Hand the grid's own cell-centre coordinates (xnodes / ynodes at Center, host vectors) to the context: needed once before azimuthal_mean / polar_winds!."
+function set_horizontal_nodes!(ctx, xc::Vector{Float64}, yc::Vector{Float64})
+    check(ccall((:bz_set_horizontal_nodes, libbreeze_hip), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}), ctx, xc, yc),
+          "bz_set_horizontal_nodes", ctx)
+end
+
+"""
+azimuthal_mean!(profile, counts, ctx, field, z_face; radius, center = (0, 0), m = 4): the reference's azimuthal_mean of one centre or z-face
+parent array into `profile` (Nr × nlev host matrix, ring index fastest, as `interior(c̄, :, 1, :)`) and the samples per ring into `counts`.
+Call `set_horizontal_nodes!(ctx, xnodes, ynodes)` once on the context first: without the grid's own cell-centre coordinates the library
+returns BZ_ERR_INVALID.
+"""
+function azimuthal_mean!(profile::Matrix{Float64}, counts::Vector{Int64}, ctx, field::Ptr{Cvoid}, z_face::Bool; radius, center = (0, 0), m = 4)
+    Nr = size(profile, 1)
+    length(counts) == Nr || throw(ArgumentError("counts must have one entry per ring"))
+    check(ccall((:bz_azimuthal_mean, libbreeze_hip), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Cdouble, Cdouble, Cdouble, Int32, Int32, Ptr{Cdouble}, Ptr{Int64}),
+                ctx, field, z_face, center[1], center[2], radius, Nr, m, profile, counts), "bz_azimuthal_mean", ctx)
+    return profile
+end
+
+"azimuthal_mean(ctx, field, z_face, nlev; radius, Nr, center = (0, 0), m = 4) -> (profile (Nr × nlev), counts); needs set_horizontal_nodes! first"
+function azimuthal_mean(ctx, field::Ptr{Cvoid}, z_face::Bool, nlev::Integer; radius, Nr, center = (0, 0), m = 4)
+    profile, counts = Matrix{Float64}(undef, Nr, nlev), Vector{Int64}(undef, Nr)
+    azimuthal_mean!(profile, counts, ctx, field, z_face; radius, center, m)
+    return profile, counts
+end
+
+"""
+Tangential and radial wind about `center` at cell centres from the velocity parent arrays (filled halos); either output may be C_NULL.
+Needs `set_horizontal_nodes!(ctx, xnodes, ynodes)` once on the context first (else BZ_ERR_INVALID); NaN where a cell centre is the centre.
+"""
+function polar_winds!(tangential::Ptr{Cvoid}, radial::Ptr{Cvoid}, ctx, u::Ptr{Cvoid}, v::Ptr{Cvoid}; center = (0, 0))
+    check(ccall((:bz_polar_winds, libbreeze_hip), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cdouble, Cdouble, Ptr{Cvoid}, Ptr{Cvoid}),
+                ctx, u, v, center[1], center[2], tangential, radial), "bz_polar_winds", ctx)
+end
+
 # hipGraph replay of whole steps (csrc/bz_graph.hip): opt-in, pays with a fixed Δt on launch-bound grids; Oceananigans fields keep
 # their device arrays for the life of the model, which is what a recorded step relies on
 graph_replay!(ctx, on::Bool = true) = check(ccall((:bz_graph_enable, libbreeze_hip), Cint, (Ptr{Cvoid}, Cint), ctx, on), "bz_graph_enable", ctx)
