@@ -234,7 +234,7 @@ int bzi_create(bz_ctx **out, const bz_grid *grid, const bz_constants *constants,
     if ((grid->topo[0] != BZ_PERIODIC && !bounded_x) || (grid->topo[1] != BZ_PERIODIC && !flat_y && !bounded_y) || grid->topo[2] != BZ_BOUNDED)
         return BZ_ERR_UNSUPPORTED;
     // compressible contexts with lateral walls ((Bounded | Periodic, Bounded | Periodic, Bounded), 3-D, single device): the acoustic substep
-    // loop with its wall / open-boundary enforcement (bz_compressible.hip: BZ_REJECT_WALLS lists what they do not run)
+    // loop with its wall / open-boundary enforcement (bz_compressible_internal.h: BZ_REJECT_WALLS lists what they do not run)
     if (compressible && (bounded_x || bounded_y)) {
         if (flat_y || slab_mode || weno_order == 2 || grid->Nx < 2 * grid->Hx || grid->Ny < 2 * grid->Hy) return BZ_ERR_UNSUPPORTED;
     } else {
@@ -370,7 +370,7 @@ int bzi_create(bz_ctx **out, const bz_grid *grid, const bz_constants *constants,
     if (slab_mode && (Ny < grid->Hy || Nx < 2 * grid->Hx)) { delete ctx; return BZ_ERR_UNSUPPORTED; }
     ctx->fuse_rk = !ctx->tune.no_fuse_rk;
     // Flat y: the anelastic model steps with one kernel per reference kernel (bz_tendency.hip); the compressible kernels reach their
-    // y neighbours through wrap offsets, which are zero when Ny = 1 (bz_compressible.hip: wrap_of), and keep their fused sequence
+    // y neighbours through wrap offsets, which are zero when Ny = 1 (bz_compressible_internal.h: wrap_of), and keep their fused sequence
     if (flat_y) { if (!compressible) ctx->fused_ok = false; ctx->tiled_tendencies = false; }
     if (bounded_y && !compressible) {      // per-operator entry points: one kernel per reference kernel, row-wise buffers (bz_tendency.hip); whole steps of the dry
         ctx->walls_lean_ok = ctx->fused_ok;      // model: the lean seam with its WY kernels (bz_step.hip)

@@ -69,26 +69,6 @@ __global__ __launch_bounds__(256) void k_poisson_source_rows(DevGrid g, double *
     rhs[(long long)i + (long long)g.Nx * ((long long)j + (long long)g.Ny * k)] = g.dzc[k] * div / dt;
 }
 
-// store v at n and at its periodic images (ox / oy = offset of the x / y image, 0 if none)
-__device__ __forceinline__ void st_img(double *__restrict__ f, long long n, double v, long long ox, long long oy)
-{
-    f[n] = v;
-    if (ox) f[n + ox] = v;
-    if (oy) {
-        f[n + oy] = v;
-        if (ox) f[n + ox + oy] = v;
-    }
-}
-// images only (the interior value is already in place)
-__device__ __forceinline__ void st_img_only(double *__restrict__ f, long long n, double v, long long ox, long long oy)
-{
-    if (ox) f[n + ox] = v;
-    if (oy) {
-        f[n + oy] = v;
-        if (ox) f[n + ox + oy] = v;
-    }
-}
-
 // y image of row j: the periodic image (wrap_y), or — walls in y — the first halo row next to a wall row (no-flux copy of a centre-in-y
 // field: the convention of the halo fill, bz_halo.hip); 0: none (interior rows; y-slabs, whose halos the neighbour ranks fill)
 __device__ __forceinline__ long long bz_y_image(const DevGrid &g, int j)

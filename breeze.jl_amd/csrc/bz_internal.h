@@ -80,6 +80,25 @@ struct RKEpilogue {
     double *u0b_out = nullptr;
 };
 #ifdef __HIPCC__
+// store v at n and at its periodic images (ox / oy = offset of the x / y image, 0 if none)
+__device__ __forceinline__ void st_img(double *__restrict__ f, long long n, double v, long long ox, long long oy)
+{
+    f[n] = v;
+    if (ox) f[n + ox] = v;
+    if (oy) {
+        f[n + oy] = v;
+        if (ox) f[n + ox + oy] = v;
+    }
+}
+// images only (the interior value is already in place)
+__device__ __forceinline__ void st_img_only(double *__restrict__ f, long long n, double v, long long ox, long long oy)
+{
+    if (ox) f[n + ox] = v;
+    if (oy) {
+        f[n + oy] = v;
+        if (ox) f[n + ox + oy] = v;
+    }
+}
 // a / b for a column constant b whose correctly rounded reciprocal rb = RN(1/b) is tabulated: q0 = a rb, one fused
 // residual, one fused correction (Markstein's division: the result is the correctly rounded quotient, i.e. bit-identical
 // to the IEEE `a / b` the diagnosis kernels use — checked on 4e8 random pairs, tools/check_cdiv.c), 3 instructions instead
@@ -483,7 +502,7 @@ struct bz_ctx {
     double *closure_nu = nullptr;     // model.closure_fields.nu_e (caller-owned centre field)
     double *d_closure_ipi = nullptr;  // (pst/p_r[k])^(Rd/cpd), k = -1 .. Nz
     double *up2_user = nullptr, *vp2_user = nullptr;   // caller-owned replacements of d_up2 / d_vp2 (bz_set_acoustic_scratch)
-    alignas(8) unsigned char ac_stage_storage[160] = {0};   // AcStage of the stage in flight (bz_compressible.hip)
+    alignas(8) unsigned char ac_stage_storage[160] = {0};   // AcStage of the stage in flight (bz_compressible_internal.h)
     // advection = (; rho_q = WENO(order = 5, bounds = (lo, hi))) (bz_set_bounds_preserving_advection, bz_bounded.hip)
     int bounded_mask = 0;             // 1 moisture, 2 microphysical species, 4 tracers
     double bounded_lo = 0.0, bounded_hi = 1.0;

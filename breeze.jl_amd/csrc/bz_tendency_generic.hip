@@ -201,7 +201,7 @@ __device__ __forceinline__ double rk_out(const FluxBuf &F, double G, long long n
 // Block order (round 5).  Consecutive workgroup ids go round-robin to the 8 XCDs, each with its own L2: in launch order (x fastest, then y)
 // the rows j - 5 .. j + 5 an order-9 y stencil reads belonged to workgroups of OTHER XCDs, and the marching kernel's grid — 8 tiles wide at
 // 512 cells — gave every XCD a tile COLUMN, its x neighbours behind another L2.  Here XCD c owns the band [c gy/8, (c+1) gy/8) of the grid's
-// y extent and walks it x fastest, then y, then z (bz_fused.hip: bz_stream_block; bz_compressible.hip: k_ac_column_forward).  Grids whose y
+// y extent and walks it x fastest, then y, then z (bz_fused.hip: bz_stream_block; bz_acoustic_kernels.h: k_ac_column_forward).  Grids whose y
 // extent is not a multiple of 8 keep launch order.  The indices are wave-uniform (column tables stay scalar loads).
 #ifndef GEN_XCD
 #define GEN_XCD 1

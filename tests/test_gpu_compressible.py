@@ -190,7 +190,7 @@ def test_slow_tendencies_match_oracle(oracle, oc, bz, stretched):
 @pytest.mark.parametrize("size", [(64, 8, 20), (128, 8, 70)])
 def test_slow_tendencies_on_rows_of_64_cells_take_the_exchange_kernel(oracle, oc, bz, size, monkeypatch):
     """Rows of a multiple of 64 cells with Ny a multiple of 4: the rho theta (+ rho_d) and moisture tendencies run
-    k_scalar_tendency_rho3d_x (csrc/bz_compressible.hip: every face flux evaluated once, exchanged by lane shuffle / LDS rows in groups of
+    k_scalar_tendency_rho3d_x (csrc/bz_cmp_scalar.hip: every face flux evaluated once, exchanged by lane shuffle / LDS rows in groups of
     four levels, short level chunks on small grids) — against the oracle at the tolerance of the test above, and against the kernel it
     replaces (BZ_NO_RHO3D_EXCHANGE=1; an ulp of a flux apart).  128 x 8 x 70: two tiles in x, two tile rows (outside rows across the
     periodic boundary), level chunks of 8 with partial groups."""
@@ -337,7 +337,7 @@ def test_time_steps_on_rows_of_64_cells_match_oracle(oracle, oc, bz):
 @pytest.mark.parametrize("size", [(128, 32, 12), (64, 64, 10)])
 def test_forward_sweep_with_xcd_bands_matches_oracle(oracle, oc, bz, size, monkeypatch):
     """Round 5: where the forward sweep's grid has a multiple of 8 tile rows (Ny a multiple of 32) every XCD owns a band of tile rows and walks
-    it x fastest (csrc/bz_compressible.hip: k_ac_column_forward, AcParams::xcd; in launch order an XCD owns a tile COLUMN and every x
+    it x fastest (csrc/bz_acoustic_kernels.h: k_ac_column_forward, AcParams::xcd; in launch order an XCD owns a tile COLUMN and every x
     neighbour sits behind another L2).  Two tile columns x one row per band, and one column x two rows per band: three steps against the
     oracle and bit for bit against the launch-order run (BZ_AC_XCD=0)."""
     def run(xcd):

@@ -273,6 +273,20 @@ def test_wall_contexts_run_the_acoustic_loop_only(oracle, oc, bz):
 
 
 @pytest.mark.gpu
+def test_update_state_on_walls_names_itself_in_the_error(oracle, oc, bz):
+    """bz_compressible_update_state on a Bounded x returns BZ_ERR_UNSUPPORTED (2) before it launches anything, and bz_last_error names the
+    function that was called — not the Kessler update, whose name an earlier copy of the rejection carried."""
+    import ctypes as C
+    om = oracle_model(oracle, oc, TOPOLOGIES[0])
+    hm = hip_model(bz, om, TOPOLOGIES[0])
+    rc = hm._lib.bz_compressible_update_state(hm._ctx, C.byref(hm._state), C.byref(hm._G), C.byref(hm._sub), 1)
+    assert rc == 2
+    msg = hm._lib.bz_last_error(hm._ctx).decode()
+    assert "bz_compressible_update_state" in msg
+    assert "kessler" not in msg.lower()
+
+
+@pytest.mark.gpu
 def test_lateral_boundary_setter_validates_its_arguments(oracle, oc, bz):
     """bz_set_acoustic_lateral_boundaries: the factor must lie in (0, 1] (time_discretizations.jl:573-574) and an open side needs a Bounded
     topology in its direction; a periodic context refuses any open side."""

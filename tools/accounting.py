@@ -81,7 +81,7 @@ COMPULSORY_WORDS = {
     "moisture_tendency": 6, "scalar_tendencies": 11, "scalar_tendency": 5, "ssp_rk3_substep": 20, "ssp_rk3_substep+store_initial_state": 20,
     "make_pressure_correction": 7, "compute_velocities": 6, "compute_auxiliary_thermodynamic_variables": 5, "poisson_source_term": 4,
     "poisson_fft_forward": 4, "poisson_fft_inverse": 4,
-    # compressible split-explicit path (bz_compressible.hip)
+    # compressible split-explicit path (bz_compressible.hip and the units listed at its top)
     # round 6: the horizontal gradient of p^L is folded into the slow momentum tendencies once per stage (stages of >= 5 substeps), so the
     # forward sweep reads Gp_ru, Gp_rv instead of G_ru, G_rv AND p: 22 words (23 in a stage that keeps p^L in the substep)
     "acoustic_horizontal+column_forward": 22,          # R rho', (rho theta)' x 2 levels, theta_L, C, (rho u)', (rho v)', G x 4, (rho w)', G^s, <u>, <v>; W (rho u)', (rho v)', <u>, <v>, both predictors, rhs
@@ -110,7 +110,7 @@ ACOUSTIC_SUBSTEP_COMPULSORY_WORDS = 32                 # forward 22 + backward 1
 
 def acoustic_substep_words(nsub, dry, fold_min=5, pair_avg=True):
     """Mean compulsory words per cell of the forward and the backward sweep over the substeps of one step, from the substep counts of the
-    three stages.  A stage of fewer than fold_min substeps keeps p^L in the substep (+1 word, bz_compressible.hip: AcStage::pfold); in a
+    three stages.  A stage of fewer than fold_min substeps keeps p^L in the substep (+1 word, bz_acoustic.hip: AcStage::pfold); in a
     DRY whole step (rho q identically zero, found by the opening scan) stages 1 and 2 carry no time-average accumulators: the forward sweep
     neither reads nor writes <u>, <v> (-4 words), the backward sweep <w> (-2) (AcParams::skip_avg_if_dry).  pair_avg: in a stage that does
     accumulate, <u>, <v> are added two substeps at a time (AcParams::acc_mode): of the substeps 2 .. N, floor((N - 1) / 2) leave the

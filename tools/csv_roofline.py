@@ -39,7 +39,7 @@ def main():
             continue
         word = 4 if f32 else 8
         # substep_floattype = Float32 inside a Float64 model (k_ac_*<..., float>): the working fields of the acoustic loop are 4-byte words,
-        # (rho w)', right-hand side, factors, averaged velocities and every model field stay 8-byte (csrc/bz_compressible.hip: AcFieldsT)
+        # (rho w)', right-hand side, factors, averaged velocities and every model field stay 8-byte (csrc/bz_compressible_internal.h: AcFieldsT)
         mixed = None
         if (not f32) and name.startswith("k_ac_") and ", float>" in name.split("(")[0]:
             mixed = {"acoustic_horizontal+column_forward": 10 * 4 + 13 * 8, "acoustic_column_backward": 5 * 4 + 5 * 8}.get(group.split(" | ")[0], 0)
