@@ -27,7 +27,7 @@ __global__ __launch_bounds__(64 * CTY) void k_scalar_tendency_rho3d(DevGrid g, d
     const int k1 = min(k0 + kchunk, g.Nz);
     const long long sy = g.Sx, sz = g.Sxy;
     long long n = g.idx(i, j, k0);
-    // moisture launch of a dry model (the moisture scan's word, bz_step.hip: bzi_scan_moisture): the advected field is identically zero,
+    // moisture launch of a dry model (the moisture scan's word, bz_moisture.hip: bzi_scan_moisture): the advected field is identically zero,
     // every flux an exact zero — the tendency is written as such without reading anything
     if (zero_if_dry && __builtin_amdgcn_readfirstlane(*zero_if_dry) == 1) {
         for (int k = k0; k < k1; ++k, n += sz) Gc[n] = 0.0;

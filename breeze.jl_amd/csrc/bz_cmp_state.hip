@@ -364,15 +364,7 @@ extern "C" int bz_compressible_kessler_update(bz_ctx *ctx, const bz_compressible
     BZ_REQUIRE_COMPRESSIBLE();
     if (!valid_state(s) || !valid_prog(G) || !valid_sub(sub)) return BZ_ERR_INVALID;
     if (ctx->dg.microphysics != 2) { ctx->last_error = "bz_compressible_kessler_update: no Kessler microphysics attached"; return BZ_ERR_INVALID; }
-    const bz_kessler_model_fields &K = ctx->kessler;
-    bz_kessler_fields F;
-    F.density = s->rho_d; F.pressure = s->p;
-    F.potential_temperature = s->theta; F.potential_temperature_density = s->rho_theta;
-    F.moisture_density = s->rho_q; F.cloud_liquid_density = K.cloud_liquid_density; F.rain_density = K.rain_density;
-    F.vapor_mass_fraction = K.vapor_mass_fraction; F.cloud_liquid_mass_fraction = K.cloud_liquid_mass_fraction;
-    F.rain_mass_fraction = K.rain_mass_fraction; F.rain_terminal_velocity = K.rain_terminal_velocity;
-    F.precipitation_rate = K.precipitation_rate;
-    int rc = bz_kessler_microphysics_update(ctx, &ctx->kessler_params, &F, dt, ctx->kessler_pst);
+    const int rc = bzi_kessler_columns(ctx, s->theta, s->rho_theta, s->rho_q, s->rho_d, s->p, dt);
     if (rc) return rc;
     // the columns are rank-local; on a y-slab the update_state! that follows needs the neighbour exchanges of the driver
     if (ctx->slab_mode) return BZ_OK;

@@ -599,7 +599,7 @@ static int dist_projection(bz_ctx *ctx, const bz_state *s, const bz_prognostic *
     }
     if ((rc = dist_poisson(ctx, s, predictor, dt))) return rc;
     if ((rc = exchange_phi_below(ctx))) return rc;
-    if (join_side) BZ_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));      // the scalar-pair kernel of this stage has finished
+    if (join_side && (rc = bzi_scalar_pair_join(ctx))) return rc;      // the scalar-pair kernel of this stage has finished
     if (lean) return bzi_project_lean(ctx, s, dt, c->rhs, c->phi_below, predictor, oa, ob);
     return bzi_project_diagnose(ctx, s, dt, c->rhs, c->phi_below, predictor, true, rtheta_in, rq_in);
 }
@@ -645,7 +645,6 @@ extern "C" int bz_comm_update_state_and_project(bz_ctx *ctx, const bz_state *s, 
     return state_halo_exchange(ctx, s, s->rho_theta, s->rho_q, true, ctx->stream);
 }
 
-// time_step!(model, dt) on y-slabs: the lean whole-step seam of bz_step.hip with the exchanges in between
 // ---- small all-reduce (column data: horizontal averages of the forcing stack) ---------------------------------------------------------
 __global__ void k_sum_blocks(const double *__restrict__ blocks, double *__restrict__ out, int n, int W)
 {
@@ -687,22 +686,16 @@ int bzi_comm_allreduce_sum(bz_ctx *ctx, double *buf, int n)
     return BZ_OK;
 }
 
-// ---- distributed step of the models the lean seam does not cover: saturation adjustment, SmagorinskyLilly, column forcings, bottom
-// fluxes (the physics list of BASELINE configs[2]) — the fused-RK tier of bz_time_step_anelastic (bz_step.hip) with the exchanges of the
-// slab decomposition: per stage the tendency kernels with the RK update folded in, the closure (its viscosity kernel covers one row
-// beyond each slab edge, so nu_e needs no exchange), the forcing stack (horizontal averages all-reduced over the ranks), bottom fluxes,
-// the distributed pressure solve + projection + diagnosis, and one y-halo exchange of everything the next stage's stencils read.
 // Operator-by-operator distributed step: the reference's own call order (ssp_runge_kutta_3.jl:223-270) with the exchanges of
 // bz_comm_update_state_and_project in place of the local halo fills.  Every model option the single-GPU per-operator tier runs takes
 // this path on slabs when the fused tiers do not apply: StaticEnergy, Kessler species, bounds-preserving advection, WENO(order = 7 / 9).
 static int dist_time_step_operators(bz_ctx *ctx, const bz_state *s, const bz_prognostic *U0, const bz_prognostic *G, double dt)
 {
-    const double alphas[3] = {1.0, 1.0 / 4.0, 2.0 / 3.0};
     int rc;
     if (ctx->G_is_predictor && (rc = bz_compute_tendencies(ctx, s, G))) return rc;      // state and halos are current since the last step's end
     if ((rc = bz_store_initial_state(ctx, s, U0))) return rc;
     for (int stage = 0; stage < 3; ++stage) {
-        const double alpha = alphas[stage];
+        const double alpha = BZ_SSP_RK3_ALPHA[stage];
         if ((rc = bz_compute_flux_bc_tendencies(ctx, s, G))) return rc;
         if ((rc = bz_ssp_rk3_substep(ctx, s, U0, G, dt, alpha))) return rc;
         // pressure solve with its all-to-alls, projection + diagnostics in one kernel, exchange.  The diagnostics run ONCE per stage, as
@@ -717,41 +710,28 @@ static int dist_time_step_operators(bz_ctx *ctx, const bz_state *s, const bz_pro
         if ((rc = bz_compute_tendencies(ctx, s, G))) return rc;
     }
     if (ctx->dg.microphysics == 2) {      // microphysics_model_update! closes the step: rank-local columns, then update_state! with exchanges
-        const bz_kessler_model_fields &K = ctx->kessler;
-        bz_kessler_fields F;
-        F.density = nullptr; F.pressure = nullptr;
-        F.potential_temperature = s->theta; F.potential_temperature_density = s->rho_theta;
-        F.moisture_density = s->rho_q; F.cloud_liquid_density = K.cloud_liquid_density; F.rain_density = K.rain_density;
-        F.vapor_mass_fraction = K.vapor_mass_fraction; F.cloud_liquid_mass_fraction = K.cloud_liquid_mass_fraction;
-        F.rain_mass_fraction = K.rain_mass_fraction; F.rain_terminal_velocity = K.rain_terminal_velocity;
-        F.precipitation_rate = K.precipitation_rate;
-        if ((rc = bz_kessler_microphysics_update(ctx, &ctx->kessler_params, &F, dt, ctx->kessler_pst))) return rc;
+        if ((rc = bzi_kessler_columns(ctx, s->theta, s->rho_theta, s->rho_q, nullptr, nullptr, dt))) return rc;
         if ((rc = bz_comm_update_state_and_project(ctx, s, G, dt, 0))) return rc;
         if ((rc = bz_compute_tendencies(ctx, s, G))) return rc;
     }
     return BZ_OK;
 }
 
-static int dist_time_step_general(bz_ctx *ctx, const bz_state *s, const bz_prognostic *U0, const bz_prognostic *G, double dt)
+// Distributed step of the models the lean seam does not cover: saturation adjustment, SmagorinskyLilly, column forcings, bottom
+// fluxes (the physics list of BASELINE configs[2]) — the fused-RK tier of bz_time_step_anelastic (bz_step.hip) with the exchanges of the
+// slab decomposition: per stage the tendency kernels with the RK update folded in, the closure (its viscosity kernel covers one row
+// beyond each slab edge, so nu_e needs no exchange), the forcing stack (horizontal averages all-reduced over the ranks), bottom fluxes,
+// the distributed pressure solve + projection + diagnosis, and one y-halo exchange of everything the next stage's stencils read.
+static int dist_time_step_fused_rk(bz_ctx *ctx, const bz_state *s, const bz_prognostic *U0, const bz_prognostic *G, double dt)
 {
     const DevGrid &g = ctx->dg;
-    if (!(ctx->fused_ok && ctx->fuse_rk && g.formulation == 0 && g.microphysics != 2 && !ctx->bounded_mask && ctx->weno_R == 3 && ctx->scalar_R == 3 && !ctx->has_relaxation))
-        return dist_time_step_operators(ctx, s, U0, G, dt);
     const int32_t nc = g.Nz + 2 * g.Hz, nf = nc + 1;
-    const double alphas[3] = {1.0, 1.0 / 4.0, 2.0 / 3.0};
     int rc;
-    BZ_HIP(hipMemsetAsync(G->rho_w + g.Sxy * g.Hz, 0, g.Sxy * sizeof(double), ctx->stream));
-    BZ_HIP(hipMemsetAsync(G->rho_w + g.Sxy * (g.Hz + g.Nz), 0, g.Sxy * sizeof(double), ctx->stream));
+    if ((rc = bzi_zero_wall_faces(ctx, G))) return rc;
     for (int stage = 0; stage < 3; ++stage) {
-        const double alpha = alphas[stage];
+        const double alpha = BZ_SSP_RK3_ALPHA[stage];
         if ((rc = bzi_tendencies_fused_rk(ctx, s, U0, G, dt, alpha, stage == 0))) return rc;
-        if (ctx->n_tracers) {       // tracers ride beside the fused kernels: tendency from the previous-stage state, RK in place
-            if ((rc = bzi_tracer_tendencies(ctx, s))) return rc;
-            if ((rc = bzi_tracer_rk3(ctx, dt, alpha, stage == 0))) return rc;
-        }
-        if (ctx->has_closure && (rc = bzi_apply_closure(ctx, s, G->rho_u, G->rho_v, G->rho_w, s->rho_theta, s->rho_q, alpha * dt))) return rc;
-        if (ctx->has_forcings && (rc = bzi_apply_forcings(ctx, s, G->rho_u, G->rho_v, s->rho_theta, s->rho_q, alpha * dt))) return rc;
-        if ((ctx->has_forcings || ctx->has_bulk) && (rc = bzi_flux_bc(ctx, s, G->rho_u, G->rho_v, s->rho_theta, s->rho_q, alpha * dt))) return rc;
+        if ((rc = bzi_fused_rk_physics(ctx, s, G, dt, alpha, stage == 0, false))) return rc;      // (no momentum terms folded into the kernels here)
         if ((rc = dist_projection(ctx, s, G, alpha * dt, false, nullptr, nullptr, nullptr, nullptr))) return rc;
         if ((rc = bzi_tracer_specific(ctx))) return rc;
         double *f[BZ_COMM_MAX_FIELDS] = {s->rho_u, s->rho_v, s->rho_w, s->u, s->v, s->w, s->theta, s->q, s->T, s->rho_theta, s->rho_q};
@@ -777,58 +757,34 @@ int bzi_comm_join_pending(bz_ctx *ctx)
     return BZ_OK;
 }
 
-int bzi_dist_time_step(bz_ctx *ctx, const bz_state *s, const bz_prognostic *U0, const bz_prognostic *G, double dt, bool diagnose)
+// time_step!(model, dt) on y-slabs, lean tier: the lean whole-step seam of bz_step.hip (step_lean) with the exchanges in between
+static int dist_time_step_lean(bz_ctx *ctx, const bz_state *s, const bz_prognostic *U0, const bz_prognostic *G, double dt, bool diagnose)
 {
     BzComm *c = ctx->comm;
-    const DevGrid &g = ctx->dg;
-    ctx->lean_step_last = false;
-    if (!(ctx->fused_ok && ctx->weno_R == 3 && ctx->scalar_R == 3 && ctx->dg.formulation == 0 && ctx->dg.microphysics == 0 && !ctx->has_forcings && !ctx->has_relaxation && !ctx->has_bulk &&
-          !ctx->has_closure && ctx->n_tracers == 0 && !ctx->bounded_mask && (long long)g.Sxy * (g.Nz + 2 * g.Hz + 1) < (1LL << 32))) {
-        // these tiers start from the stored diagnostics: rebuild them if undiagnosed lean steps came before
-        const int rcs = ctx->diagnostics_stale ? bz_comm_update_state_and_project(ctx, s, G, 1.0, 0) : BZ_OK;
-        return rcs ? rcs : dist_time_step_general(ctx, s, U0, G, dt);
-    }
     int rc;
-    const double alphas[3] = {1.0, 1.0 / 4.0, 2.0 / 3.0};
-    BZ_HIP(hipMemsetAsync(G->rho_w + g.Sxy * g.Hz, 0, g.Sxy * sizeof(double), ctx->stream));
-    BZ_HIP(hipMemsetAsync(G->rho_w + g.Sxy * (g.Hz + g.Nz), 0, g.Sxy * sizeof(double), ctx->stream));
-    BZ_HIP(hipMemsetAsync(U0->rho_w + g.Sxy * g.Hz, 0, g.Sxy * sizeof(double), ctx->stream));
-    BZ_HIP(hipMemsetAsync(U0->rho_w + g.Sxy * (g.Hz + g.Nz), 0, g.Sxy * sizeof(double), ctx->stream));
+    if ((rc = bzi_zero_wall_faces(ctx, G, U0))) return rc;
+    // The scalar-pair kernel feeds nothing of the pressure solve: with messages in flight (W > 1) it runs on the context's second
+    // stream beside the source term, the transforms and both all-to-alls, and is joined before the projection kernel.
+    const bool fork = (c->W > 1 || c->self_messages || ctx->side_scalar) && !ctx->tune.comm_no_side_scalar;
+    const int first_part = fork ? 1 : 3;
     for (int stage = 0; stage < 3; ++stage) {
-        const double alpha = alphas[stage];
+        const double alpha = BZ_SSP_RK3_ALPHA[stage];
         // buffer rotation and the undiagnosed last stage of bz_time_steps_anelastic: as in bz_step.hip (bzi_lean_stage)
         const bool full = diagnose && stage == 2;
-        LeanStage LS;
-        bzi_lean_stage(s, U0, G, stage, &LS);
-        const bz_state *sin = &LS.sin, *sout = &LS.sout;
-        const bz_prognostic *u0 = &LS.u0;
-        const double *pa = LS.pa, *pb = LS.pb;
-        double *oa = LS.oa, *ob = LS.ob;
-        // The scalar-pair kernel feeds nothing of the pressure solve: with messages in flight (W > 1) it runs on the context's second
-        // stream beside the source term, the transforms and both all-to-alls, and is joined before the projection kernel.
-        const bool fork = (c->W > 1 || c->self_messages || ctx->side_scalar) && !ctx->tune.comm_no_side_scalar;
-        const int first_part = fork ? 1 : 3;
+        LeanStage L;
+        bzi_lean_stage(s, U0, G, stage, &L);
+        double *oa = L.oa, *ob = L.ob;
         if (c->halo_pending) {
             // the halos of the stage-start state are still travelling on the side stream: interior tile rows first
-            if ((rc = bzi_tendencies_lean(ctx, sin, u0, G, pa, pb, oa, ob, dt, alpha, stage == 0, 1, first_part))) return rc;
+            if ((rc = bzi_lean_tendencies(ctx, L, G, dt, alpha, stage == 0, 1, first_part))) return rc;
             BZ_HIP(hipStreamWaitEvent(ctx->stream, c->ev_side, 0));
             c->halo_pending = false;
-            if ((rc = bzi_tendencies_lean(ctx, sin, u0, G, pa, pb, oa, ob, dt, alpha, stage == 0, 2, first_part))) return rc;
-        } else if ((rc = bzi_tendencies_lean(ctx, sin, u0, G, pa, pb, oa, ob, dt, alpha, stage == 0, 0, first_part))) return rc;
-        if (fork) {
-            BZ_HIP(hipEventRecord(ctx->ev_fork, ctx->stream));
-            BZ_HIP(hipStreamWaitEvent(ctx->side_stream, ctx->ev_fork, 0));
-            hipStream_t keep = ctx->stream;
-            ctx->stream = ctx->side_stream;
-            rc = bzi_tendencies_lean(ctx, sin, u0, G, pa, pb, oa, ob, dt, alpha, stage == 0, 0, 2);
-            ctx->stream = keep;
-            if (rc) return rc;
-            BZ_HIP(hipEventRecord(ctx->ev_join, ctx->side_stream));
-        }
-        if ((rc = dist_projection(ctx, full ? s : sout, G, alpha * dt, !full, oa, ob, oa, ob, fork))) return rc;
+            if ((rc = bzi_lean_tendencies(ctx, L, G, dt, alpha, stage == 0, 2, first_part))) return rc;
+        } else if ((rc = bzi_lean_tendencies(ctx, L, G, dt, alpha, stage == 0, 0, first_part))) return rc;
+        if (fork && (rc = bzi_scalar_pair_fork(ctx, L, G, dt, alpha, stage == 0))) return rc;
+        if ((rc = dist_projection(ctx, full ? s : &L.sout, G, alpha * dt, !full, oa, ob, oa, ob, fork))) return rc;
         // halos of the new state.  After a diagnosed stage 3 rho theta / rho q are back in `s` and the diagnostics are current: exchange
         // them too, so that every field of `s` is what the per-operator sequence leaves
-        double *na = oa, *nb = ob;      // (a diagnosed stage 3 writes in place: oa, ob are the state arrays)
         const bool async = c->overlap && !full && (c->W > 1 || c->self_messages);
         hipStream_t st = async ? c->side : ctx->stream;
         if (async) {
@@ -837,7 +793,7 @@ int bzi_dist_time_step(bz_ctx *ctx, const bz_state *s, const bz_prognostic *U0, 
         }
         {
             ProfileScope ps(ctx, "comm_halo_exchange");
-            if ((rc = state_halo_exchange(ctx, full ? s : sout, na, nb, full, st))) return rc;
+            if ((rc = state_halo_exchange(ctx, full ? s : &L.sout, oa, ob, full, st))) return rc;      // (a diagnosed stage 3 writes in place: oa, ob are the state arrays)
         }
         if (async) {
             BZ_HIP(hipEventRecord(c->ev_side, c->side));
@@ -846,6 +802,18 @@ int bzi_dist_time_step(bz_ctx *ctx, const bz_state *s, const bz_prognostic *U0, 
     }
     bzi_lean_step_done(ctx, diagnose);
     return BZ_OK;
+}
+
+// time_step!(model, dt) on y-slabs: the tier of bzi_anelastic_tier (bz_step.hip; the slab drivers have no fused tier)
+int bzi_dist_time_step(bz_ctx *ctx, const bz_state *s, const bz_prognostic *U0, const bz_prognostic *G, double dt, bool diagnose)
+{
+    ctx->lean_step_last = false;
+    const bz_tier tier = bzi_anelastic_tier(ctx);
+    if (tier == BZ_TIER_LEAN) return dist_time_step_lean(ctx, s, U0, G, dt, diagnose);
+    // these tiers start from the stored diagnostics: rebuild them if undiagnosed lean steps came before
+    const int rcs = ctx->diagnostics_stale ? bz_comm_update_state_and_project(ctx, s, G, 1.0, 0) : BZ_OK;
+    if (rcs) return rcs;
+    return tier == BZ_TIER_FUSED_RK ? dist_time_step_fused_rk(ctx, s, U0, G, dt) : dist_time_step_operators(ctx, s, U0, G, dt);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------

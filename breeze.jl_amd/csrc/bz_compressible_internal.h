@@ -71,7 +71,7 @@ struct AcParams {
     int xcd;                      // forward sweep: 1 = every XCD owns a band of tile rows (see k_ac_column_forward), 0 = launch order
     // Round 6, dry runs inside bz_time_step_compressible: the time-averaged velocities of a stage feed one thing, the moisture (tracer)
     // tendency the NEXT stage's update uses (acoustic_runge_kutta_3.jl:189-192) — which a model whose rho q is identically zero skips
-    // (bz_step.hip: moisture scan; exact zeros either way).  Where this points at the scan's word and the word says "identically zero,
+    // (bz_moisture.hip: moisture scan; exact zeros either way).  Where this points at the scan's word and the word says "identically zero,
     // verified by the scan that opened this call", the substep kernels of stages 1 and 2 neither read nor write the three accumulators
     // (6 of a substep's 32 words) and the stage epilogue does not form the averages; stage 3 accumulates as ever, so after the step the
     // substepper holds the averages the reference leaves.  nullptr: always accumulate (per-operator entry points, slabs, moist models).

@@ -428,7 +428,7 @@ struct bz_ctx {
     int *h_qstate = nullptr;          // pinned
     hipEvent_t ev_q = nullptr;
     bool q_pending = false;
-    int *d_qstate = nullptr;          // moisture scan of the lean seam (bz_step.hip: bzi_scan_moisture): 2 = rho q has a non-zero element (sticky until
+    int *d_qstate = nullptr;          // moisture scan of the lean seam (bz_moisture.hip: bzi_scan_moisture): 2 = rho q has a non-zero element (sticky until
                                       // update_state!), anything else after a scan = identically zero; the lean kernels then skip every access to it
     bool diagnostics_stale = false;   // u, v, w, theta, q, T, phi of `s` are older than the prognostic state (bz_time_steps_anelastic without the last diagnosis)
     bool lean_step_last = false;      // the last step body took the lean tier
@@ -605,6 +605,8 @@ int bzi_scalar_rho3d_generic(bz_ctx *ctx, double *Gc, double *Grho, const double
 void bzi_closure_teardown(bz_ctx *ctx);
 int bzi_apply_closure(bz_ctx *ctx, const bz_state *s, double *Gu, double *Gv, double *Gw, double *Gth, double *Gq, double scale);
 int bzi_kessler_rk3(bz_ctx *ctx, double dt, double alpha, bool first);
+// column part of microphysics_model_update! on the attached species; density / pressure: 3-D parents of a compressible context, nullptr = reference columns
+int bzi_kessler_columns(bz_ctx *ctx, double *theta, double *rho_theta, double *rho_q, const double *density, const double *pressure, double dt);
 int bzi_kessler_update(bz_ctx *ctx, const bz_state *s, const bz_prognostic *G, double dt);
 int bzi_fill_halos_multi(bz_ctx *ctx, double *const *fields, const int *kinds, int n);
 int bzi_poisson_setup(bz_ctx *ctx, const double *h_rho_halo /* Nz+2Hz */);
@@ -621,6 +623,12 @@ int bzi_comm_join_pending(bz_ctx *ctx);
 // than the prognostic state.  With the state at hand they are rebuilt first (bz_update_state, on slab contexts with its halo exchange);
 // without it (s == nullptr) the call fails with BZ_ERR_INVALID and a message instead of answering from stale fields
 int bzi_refresh_diagnostics(bz_ctx *ctx, const bz_state *s, const char *who);
+// ---- the anelastic whole step (bz_step.hip; the slab drivers of bz_comm.hip share all of it) ----
+enum bz_tier { BZ_TIER_LEAN, BZ_TIER_FUSED_RK, BZ_TIER_FUSED, BZ_TIER_OPERATORS };
+bz_tier bzi_anelastic_tier(const bz_ctx *ctx);      // the tier a step of this context takes: the only statement of tier eligibility
+inline constexpr double BZ_SSP_RK3_ALPHA[3] = {1.0, 1.0 / 4.0, 2.0 / 3.0};      // stage weights (ssp_runge_kutta_3.jl:99-101)
+int bzi_zero_wall_faces(bz_ctx *ctx, const bz_prognostic *G, const bz_prognostic *U0 = nullptr);      // wall faces of the predictor rho w stay 0
+int bzi_fused_rk_physics(bz_ctx *ctx, const bz_state *s, const bz_prognostic *G, double dt, double alpha, bool first, bool fold);
 void bzi_lean_step_done(bz_ctx *ctx, bool diagnosed);
 int bzi_scan_moisture(bz_ctx *ctx, const bz_state *s);
 int bzi_scan_moisture_field(bz_ctx *ctx, const double *rho_q);
@@ -666,6 +674,14 @@ struct LeanStage {
 };
 int bzi_tendencies_lean(bz_ctx *ctx, const bz_state *s, const bz_prognostic *U0, const bz_prognostic *G, const double *pa,
                         const double *pb, double *oa, double *ob, double dt, double alpha, bool first, int rows = 0, int which = 3);
+static inline int bzi_lean_tendencies(bz_ctx *ctx, const LeanStage &L, const bz_prognostic *G, double dt, double alpha, bool first,
+                                      int rows = 0, int which = 3)
+{
+    return bzi_tendencies_lean(ctx, &L.sin, &L.u0, G, L.pa, L.pb, L.oa, L.ob, dt, alpha, first, rows, which);
+}
+// the scalar-pair kernel (which = 2) of a lean stage on the side stream, beside the pressure solve; joined before the projection
+int bzi_scalar_pair_fork(bz_ctx *ctx, const LeanStage &L, const bz_prognostic *G, double dt, double alpha, bool first);
+int bzi_scalar_pair_join(bz_ctx *ctx);
 int bzi_tendencies_fused_rk(bz_ctx *ctx, const bz_state *s, const bz_prognostic *U0, const bz_prognostic *G, double dt,
                             double alpha, bool first);
 int bzi_create(bz_ctx **out, const bz_grid *grid, const bz_constants *constants, const bz_reference_state *ref,

@@ -265,20 +265,25 @@ int bzi_kessler_rk3(bz_ctx *ctx, double dt, double alpha, bool first)
     return BZ_OK;
 }
 
-// microphysics_model_update!: the column kernel, then update_state!(model) (dcmip2016_kessler.jl:480-485)
-int bzi_kessler_update(bz_ctx *ctx, const bz_state *s, const bz_prognostic *G, double dt)
+// the column kernel of microphysics_model_update! on the species of the attached model (rank-local on slabs)
+int bzi_kessler_columns(bz_ctx *ctx, double *theta, double *rho_theta, double *rho_q, const double *density, const double *pressure, double dt)
 {
     const bz_kessler_model_fields &K = ctx->kessler;
     bz_kessler_fields F;
-    F.density = nullptr; F.pressure = nullptr;
-    F.potential_temperature = s->theta; F.potential_temperature_density = s->rho_theta;
-    F.moisture_density = s->rho_q; F.cloud_liquid_density = K.cloud_liquid_density; F.rain_density = K.rain_density;
+    F.density = density; F.pressure = pressure;
+    F.potential_temperature = theta; F.potential_temperature_density = rho_theta;
+    F.moisture_density = rho_q; F.cloud_liquid_density = K.cloud_liquid_density; F.rain_density = K.rain_density;
     F.vapor_mass_fraction = K.vapor_mass_fraction; F.cloud_liquid_mass_fraction = K.cloud_liquid_mass_fraction;
     F.rain_mass_fraction = K.rain_mass_fraction; F.rain_terminal_velocity = K.rain_terminal_velocity;
     F.precipitation_rate = K.precipitation_rate;
-    int rc = bz_kessler_microphysics_update(ctx, &ctx->kessler_params, &F, dt, ctx->kessler_pst);
-    if (rc) return rc;
-    return bz_update_state(ctx, s, G, 1);
+    return bz_kessler_microphysics_update(ctx, &ctx->kessler_params, &F, dt, ctx->kessler_pst);
+}
+
+// microphysics_model_update!: the column kernel, then update_state!(model) (dcmip2016_kessler.jl:480-485)
+int bzi_kessler_update(bz_ctx *ctx, const bz_state *s, const bz_prognostic *G, double dt)
+{
+    const int rc = bzi_kessler_columns(ctx, s->theta, s->rho_theta, s->rho_q, nullptr, nullptr, dt);
+    return rc ? rc : bz_update_state(ctx, s, G, 1);
 }
 
 extern "C" int bz_kessler_model_update(bz_ctx *ctx, const bz_state *s, const bz_prognostic *G, double dt)

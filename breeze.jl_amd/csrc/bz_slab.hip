@@ -202,12 +202,9 @@ extern "C" int bz_tendencies_fused_rk(bz_ctx *ctx, const bz_state *s, const bz_p
                                       double dt, double alpha, int first)
 {
     if (!ctx || !s || !U0 || !G) return BZ_ERR_INVALID;
-    const DevGrid &g = ctx->dg;
-    if (first) {      // wall faces of the predictor stay 0
-        BZ_HIP(hipMemsetAsync(G->rho_w + g.Sxy * g.Hz, 0, g.Sxy * sizeof(double), ctx->stream));
-        BZ_HIP(hipMemsetAsync(G->rho_w + g.Sxy * (g.Hz + g.Nz), 0, g.Sxy * sizeof(double), ctx->stream));
-    }
-    int rc = bzi_tendencies_fused_rk(ctx, s, U0, G, dt, alpha, first != 0);
+    int rc = first ? bzi_zero_wall_faces(ctx, G) : BZ_OK;
+    if (rc) return rc;
+    rc = bzi_tendencies_fused_rk(ctx, s, U0, G, dt, alpha, first != 0);
     ctx->G_is_predictor = true;
     return rc;
 }

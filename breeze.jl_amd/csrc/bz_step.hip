@@ -1,7 +1,8 @@
 // bz_step.hip — host-side orchestration of the device-resident anelastic SSP-RK3 step.
 //   update_state!  /root/reference/src/AtmosphereModels/update_atmosphere_model_state.jl:41-68
 //   time_step!     /root/reference/src/TimeSteppers/ssp_runge_kutta_3.jl:209-278
-// Everything is enqueued on ctx->stream; there is no host synchronisation inside a step.
+// Everything is enqueued on ctx->stream; there is no host synchronisation inside a step.  One tier decision (bzi_anelastic_tier), one
+// function per tier (step_lean, step_fused_rk, step_fused, step_operators), and the pieces the slab drivers of bz_comm.hip share.
 #include <cstdlib>
 
 #include "bz_internal.h"
@@ -14,8 +15,7 @@ extern "C" int bz_update_state(bz_ctx *ctx, const bz_state *s, const bz_prognost
     ctx->diagnostics_stale = false;
     if (ctx->d_qstate) BZ_HIP(hipMemsetAsync(ctx->d_qstate, 0, sizeof(int), ctx->stream));      // the moisture may have been set!: unknown (= moist) until the next scan
     bzi_moisture_unknown(ctx);
-    // fill_halo_regions!(prognostic_fields(model))  (:48) — momentum halos are filled inside
-    // bz_compute_velocities (:135-136), the scalars here.
+    // fill_halo_regions!(prognostic_fields(model))  (:48) — momentum halos are filled inside bz_compute_velocities (:135-136), the scalars here.
     double *sf[4] = {s->rho_theta, s->rho_q, ctx->dg.rqcl_field, ctx->dg.rqr_field};
     int sk[4] = {0, 0, 0, 0};
     if ((rc = bzi_fill_halos_multi(ctx, sf, sk, ctx->dg.microphysics == 2 ? 4 : 2))) return rc;
@@ -27,7 +27,77 @@ extern "C" int bz_update_state(bz_ctx *ctx, const bz_state *s, const bz_prognost
     return BZ_OK;
 }
 
-static int anelastic_step_body(bz_ctx *ctx, const bz_state *s, const bz_prognostic *U0, const bz_prognostic *G, double dt, bool diagnose);
+// ---- which tier a step takes -------------------------------------------------------------------------------------------------------
+// The one statement of tier eligibility, for single-device contexts and for y-slab contexts with a communicator (bz_comm.hip).  Where the
+// slab rule differs, the difference is a named condition; DESIGN §4 "which tier runs where" lists them.  (No walls on slabs: bzi_create.)
+bz_tier bzi_anelastic_tier(const bz_ctx *ctx)
+{
+    const DevGrid &g = ctx->dg;
+    const bool slab = ctx->slab_mode;
+    // walls in y ((Periodic, Bounded, Bounded)) ride the lean seam too (WY kernels, wall rows in the projection kernels); the generic
+    // order-7 / 9 kernels of the fused-RK tier are wall-aware, its LDS-tiled order-5 kernels are not
+    const bool walls_lean = g.bounded_y && ctx->walls_lean_ok;
+    const bool order5 = ctx->weno_R == 3 && ctx->scalar_R == 3;
+    const bool theta_model = g.formulation == 0;
+    const bool lean_switches = slab || (ctx->fuse_rk && ctx->lean);                       // slab: BZ_NO_LEAN / BZ_NO_FUSE_RK are not consulted
+    const bool lean_anelastic = slab || !ctx->compressible;                               // slab: the context's model is not looked at
+    const bool lean_forcings = !ctx->has_forcings || (!slab && bzi_lean_forcings_ok(ctx));      // slab: every forcing stack is refused
+    const bool rk_orders = slab ? order5                                                  // slab: order 5 only
+                                : ctx->scalar_R == ctx->weno_R && (ctx->weno_R == 3 || ctx->n_tracers == 0);
+    const bool rk_forcings = slab || !(ctx->has_forcings && ctx->tune.no_fuse_forcing);   // slab: BZ_NO_FUSE_FORCING is not consulted
+    const bool fused_tier = !slab;                                                        // slab: no fused tier, operators instead
+    // lean seam: dry / vapour WENO5 theta model without closure, bulk fluxes, relaxation, tracers, microphysics
+    if ((ctx->fused_ok || walls_lean) && lean_switches && order5 && lean_anelastic && theta_model && g.microphysics == 0 && lean_forcings &&
+        !ctx->has_bulk && !ctx->has_closure && !ctx->has_relaxation && ctx->n_tracers == 0 && !ctx->bounded_mask &&
+        (long long)g.Sxy * (g.Nz + 2 * g.Hz + 1) < (1LL << 32))
+        return BZ_TIER_LEAN;
+    if ((ctx->fused_ok || (walls_lean && ctx->weno_R != 3)) && ctx->fuse_rk && rk_orders && theta_model && g.microphysics != 2 &&
+        !ctx->bounded_mask && !ctx->has_relaxation && rk_forcings)
+        return BZ_TIER_FUSED_RK;
+    return ctx->fused_ok && fused_tier ? BZ_TIER_FUSED : BZ_TIER_OPERATORS;
+}
+
+// ---- pieces shared with the slab drivers (bz_comm.hip) and the per-operator entry points (bz_slab.hip) -------------------------------
+// the wall faces of the predictor rho w in the G slots stay 0 — and, for the lean seam, those of the projected momentum of stages 1-2 (U0)
+int bzi_zero_wall_faces(bz_ctx *ctx, const bz_prognostic *G, const bz_prognostic *U0)
+{
+    const DevGrid &g = ctx->dg;
+    for (const long long face : {g.Sxy * g.Hz, g.Sxy * (g.Hz + g.Nz)})
+        BZ_HIP(hipMemsetAsync(G->rho_w + face, 0, g.Sxy * sizeof(double), ctx->stream));
+    return U0 ? bzi_zero_wall_faces(ctx, U0, nullptr) : BZ_OK;
+}
+
+// The scalar-pair kernel feeds nothing of the pressure solve: it runs on the side stream beside the source term, the transforms and the Thomas
+// solve (issue-bound stencil kernel next to bandwidth-bound streaming kernels); it joins before the projection (z-halo images of rho theta / rho q)
+int bzi_scalar_pair_fork(bz_ctx *ctx, const LeanStage &L, const bz_prognostic *G, double dt, double alpha, bool first)
+{
+    BZ_HIP(hipEventRecord(ctx->ev_fork, ctx->stream));
+    BZ_HIP(hipStreamWaitEvent(ctx->side_stream, ctx->ev_fork, 0));
+    hipStream_t keep = ctx->stream;
+    ctx->stream = ctx->side_stream;
+    const int rc = bzi_lean_tendencies(ctx, L, G, dt, alpha, first, 0, 2);
+    ctx->stream = keep;
+    if (rc) return rc;
+    BZ_HIP(hipEventRecord(ctx->ev_join, ctx->side_stream));
+    return BZ_OK;
+}
+
+int bzi_scalar_pair_join(bz_ctx *ctx) { BZ_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0)); return BZ_OK; }
+
+// The physics beside the fused-RK kernels of a stage: evaluated from the still-intact previous-stage state and added, weighted alpha dt, to what
+// the fused RK update just wrote (G slots, rho theta / rho q in place).  fold: the stack's momentum terms went into the momentum kernels' epilogues
+int bzi_fused_rk_physics(bz_ctx *ctx, const bz_state *s, const bz_prognostic *G, double dt, double alpha, bool first, bool fold)
+{
+    int rc;
+    if (ctx->n_tracers) {       // tracers ride beside the fused kernels: tendency from the previous-stage state, RK in place
+        if ((rc = bzi_tracer_tendencies(ctx, s))) return rc;
+        if ((rc = bzi_tracer_rk3(ctx, dt, alpha, first))) return rc;
+    }
+    if (ctx->has_closure && (rc = bzi_apply_closure(ctx, s, G->rho_u, G->rho_v, G->rho_w, s->rho_theta, s->rho_q, alpha * dt))) return rc;
+    if (ctx->has_forcings && (rc = bzi_apply_forcings(ctx, s, G->rho_u, G->rho_v, s->rho_theta, s->rho_q, alpha * dt, fold))) return rc;
+    if ((ctx->has_forcings || ctx->has_bulk) && (rc = bzi_flux_bc(ctx, s, G->rho_u, G->rho_v, s->rho_theta, s->rho_q, alpha * dt))) return rc;
+    return BZ_OK;
+}
 
 // host-side bookkeeping at the end of a lean step (single-device and slab drivers): where the ping-pong pair sits now
 void bzi_lean_step_done(bz_ctx *ctx, bool diagnosed)
@@ -58,110 +128,179 @@ void bzi_lean_stage(const bz_state *s, const bz_prognostic *U0, const bz_prognos
     L->ob = stage == 0 ? G->rho_q : stage == 1 ? U0->rho_q : s->rho_q;
 }
 
-// ---- moisture scan -------------------------------------------------------------------------------------------------------------------
-// The reference advects rho q^v in every model, dry ones included (update_atmosphere_model_state.jl:333-343).  In a dry run the field
-// is identically zero and stays so: every flux of it is an exact zero, its update is 0 -> 0.  Every step call opens with one pass over
-// rho q (1 word per cell, once per CALL — bz_time_steps_anelastic amortises it over its n steps) that leaves *d_qstate = 1 if every
-// element is zero (2 otherwise); the lean scalar-pair and z-momentum kernels read that word and, where it is 1, skip every load, store and
-// flux of rho q (4.6 of the scalar kernel's 13 words per cell, a fifth of its instructions).  The result carries the same bits either
-// way.  2 is sticky (a moist model is scanned once, later calls return at once) until bz_update_state — what set! ends with — resets it;
-// a dry model is scanned at every call, so a moisture field written behind the library's back is seen.  Contexts with a moisture
-// source (bottom moisture flux, moisture forcing, subsidence of q) or with microphysics never take the shortcut.
-// state[0]: 0 unknown (treated as moist: nothing is skipped), 1 identically zero (verified by the scan that opened this call),
-//           2 moist (sticky until bz_update_state puts 0 back);  state[1]: "some block found a non-zero element" of the scan in flight
-__global__ __launch_bounds__(256) void k_scan_moisture(const double *__restrict__ rq, long long n, int *__restrict__ state)
+// Lean tier.  full: projection + diagnosis into `s` (the last stage of a diagnosed step); else the momentum-only projection
+static int lean_project(bz_ctx *ctx, const bz_state *s, const LeanStage &L, const bz_prognostic *G, double adt, bool full)
 {
-    if (state[0] == 2) return;
-    bool found = false;
-    for (long long t = (long long)blockIdx.x * 256 + threadIdx.x; t < n; t += (long long)gridDim.x * 256) found = found || (rq[t] != 0.0);
-    if (__any(found) && (threadIdx.x & 63) == 0) state[1] = 1;
-}
-__global__ void k_scan_moisture_close(int *__restrict__ state)
-{
-    if (state[0] != 2) state[0] = state[1] ? 2 : 1;
-    state[1] = 0;
-}
-// y-slab contexts: the verdict must be the DOMAIN's, not the slab's (a rank whose slab is dry while its neighbour's is not would drop
-// the moisture that arrives through its halo rows for the rest of the call): every rank contributes "found" (0 / 1, also a
-// rank that already knows it is moist) to a sum over the communicator and closes the scan on the sum
-__global__ void k_scan_moisture_flag(const int *__restrict__ state, double *__restrict__ flag) { flag[0] = (state[0] == 2 || state[1]) ? 1.0 : 0.0; }
-__global__ void k_scan_moisture_close_global(int *__restrict__ state, const double *__restrict__ flag)
-{
-    state[0] = flag[0] != 0.0 ? 2 : 1;
-    state[1] = 0;
+    return full ? bzi_project_diagnose(ctx, s, adt, nullptr, nullptr, G, true, L.oa, L.ob) : bzi_project_lean(ctx, &L.sout, adt, nullptr, nullptr, G, L.oa, L.ob);
 }
 
-static bool moisture_sources(const bz_ctx *ctx)
+// Pressure solve from the predictor in the G slots and the projection of a lean stage, in the context's variant of the solve.
+// forked: the scalar-pair kernel of the stage is on the side stream and joins before the projection.
+static int lean_solve_and_project(bz_ctx *ctx, const bz_state *s, const LeanStage &L, const bz_prognostic *G, double adt, bool full, bool forked)
 {
-    return ctx->tune.no_dry_shortcut || ctx->dg.microphysics != 0 || ctx->has_bulk || ctx->has_relaxation || ctx->field_forcing != nullptr ||
-           (ctx->has_forcings && (ctx->forcing_flux_q != 0.0 || (ctx->forcing_static_mask & 8) || (ctx->forcing_subsidence_mask & 8))) ||
-           (ctx->slab_mode && !ctx->comm);      // slabs driven from the host: the library cannot ask the other ranks, so nothing is skipped
-}
-
-// the word the lean kernels read (nullptr: no shortcut on this context)
-const int *bzi_moisture_state(const bz_ctx *ctx) { return (ctx->d_qstate && !moisture_sources(ctx)) ? ctx->d_qstate : nullptr; }
-
-int bzi_scan_moisture(bz_ctx *ctx, const bz_state *s) { return ctx->compressible ? BZ_OK : bzi_scan_moisture_field(ctx, s->rho_q); }
-
-void bzi_moisture_unknown(bz_ctx *ctx) { ctx->q_host = 0; ctx->q_pending = false; }
-
-int bzi_scan_moisture_field(bz_ctx *ctx, const double *rho_q)
-{
-    if (moisture_sources(ctx)) return BZ_OK;
     const DevGrid &g = ctx->dg;
-    int rc;
-    if (!ctx->d_qstate) {
-        BZ_HIP(hipMalloc(&ctx->d_qstate, 2 * sizeof(int) + 2 * sizeof(double)));      // [state, found] + the flag of the slab all-reduce
-        BZ_HIP(hipMemsetAsync(ctx->d_qstate, 0, 2 * sizeof(int) + 2 * sizeof(double), ctx->stream));
-        BZ_HIP(hipHostMalloc(&ctx->h_qstate, sizeof(int)));
-        BZ_HIP(hipEventCreateWithFlags(&ctx->ev_q, hipEventDisableTiming));
-        ctx->q_host = 0;
-    }
-    // the verdict of the previous call's scan, if it has landed (asynchronous copy, never waited for)
-    if (ctx->q_pending && !ctx->comm && hipEventQuery(ctx->ev_q) == hipSuccess) { ctx->q_host = *ctx->h_qstate; ctx->q_pending = false; }
-    if (ctx->q_host == 2) return BZ_OK;      // moist is sticky on the device (until bz_update_state) and on every rank of a slab communicator alike: nothing to scan
-    // an undiagnosed last stage leaves the halo exchange of rho q on the side stream: the scan reads those rows
-    if (ctx->comm && (rc = bzi_comm_join_pending(ctx))) return rc;
-    const long long n = (long long)g.Sxy * (g.Nz + 2 * g.Hz);
-    {
-    ProfileScope ps(ctx, "moisture_scan");
-    hipLaunchKernelGGL(k_scan_moisture, dim3(ctx->num_cus * 8), dim3(256), 0, ctx->stream, rho_q, n, ctx->d_qstate);
-    if (ctx->comm) {
-        double *flag = (double *)(ctx->d_qstate + 2);
-        hipLaunchKernelGGL(k_scan_moisture_flag, dim3(1), dim3(1), 0, ctx->stream, ctx->d_qstate, flag);
-        BZ_LAUNCH_CHECK();
-        if ((rc = bzi_comm_allreduce_sum(ctx, flag, 1))) return rc;      // a collective: every rank of the communicator scans at every call
-        hipLaunchKernelGGL(k_scan_moisture_close_global, dim3(1), dim3(1), 0, ctx->stream, ctx->d_qstate, flag);
-    } else
-        hipLaunchKernelGGL(k_scan_moisture_close, dim3(1), dim3(1), 0, ctx->stream, ctx->d_qstate);
-    BZ_LAUNCH_CHECK();
-    }
-    if (ctx->graph_capturing) return BZ_OK;      // (never: the scan precedes the recorded region)
-    BZ_HIP(hipMemcpyAsync(ctx->h_qstate, ctx->d_qstate, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    if (ctx->q_host == 0 || ctx->comm) {
-        // first scan since update_state!: read the verdict back before the first tendency launch — one host wait per set! / first step —
-        // so that from here on the host launches the body that applies (separate kernels, separate rocprofv3 rows).
-        // Slab communicators read it back at EVERY call: the asynchronous path below lands at a rank-dependent time, and a rank that has
-        // learnt "moist" stops scanning — its peers would wait for it in the scan's all-reduce.  Read synchronously, the (all-reduced)
-        // verdict is the same on every rank at the same call
-        BZ_HIP(hipStreamSynchronize(ctx->stream));
-        ctx->q_host = *ctx->h_qstate;
-        ctx->q_pending = false;
+    const int ch = ctx->pchunk;
+    int rc = BZ_OK;
+    if (ch) {
+        // chunked pipeline: each level range goes source term -> x transform -> y transform (and, after the vertical solves,
+        // y -> x -> projection) back to back, so the intermediate passes find the range in the Infinity Cache
+        {
+            ProfileScope ps(ctx, "poisson_source_term+fft_forward");
+            ctx->profile_mute++;
+            for (int k0 = 0; k0 < g.Nz && !rc; k0 += ch) {
+                ctx->kr0 = k0; ctx->krn = ch;
+                rc = bzi_poisson_source_fused(ctx, s, adt, nullptr, G);
+                if (!rc) rc = bzi_fft_chunk(ctx, k0, true);
+            }
+            ctx->krn = 0;
+            ctx->profile_mute--;
+        }
+        if (rc) return rc;
+        ProfileScope ps(ctx, "poisson_tridiagonal");
+        if ((rc = bzi_tridiag_launch(ctx, (double *)ctx->d_hat, 1.0 / ((double)g.Nx * (double)g.Ny), g.Ny, 1))) return rc;
+    } else if (ctx->xf) {
+        // hand-written x transforms (bz_xfft_kernels.h): the source term is evaluated inside the forward x pass; y transforms
+        // (contiguous) and vertical solves on the transposed spectrum
+        {
+            ProfileScope ps(ctx, "poisson_source_term+fft_x");
+            if ((rc = bzi_xf_forward(ctx, s, adt, G))) return rc;
+        }
+        if ((rc = bzi_xf_middle(ctx))) return rc;
+        ProfileScope ps(ctx, "poisson_fft_x_inverse");
+        if ((rc = bzi_xf_inverse(ctx))) return rc;
     } else {
-        BZ_HIP(hipEventRecord(ctx->ev_q, ctx->stream));
-        ctx->q_pending = true;
+        if ((rc = bzi_poisson_source_fused(ctx, s, adt, nullptr, G))) return rc;
+        if ((rc = bzi_poisson_spectral(ctx))) return rc;
     }
+    if (forked && (rc = bzi_scalar_pair_join(ctx))) return rc;
+    if (!ch) return lean_project(ctx, s, L, G, adt, full);
+    ProfileScope ps(ctx, !full ? "poisson_fft_inverse+project_momentum" : "poisson_fft_inverse+project_and_diagnose");
+    ctx->profile_mute++;
+    for (int k0 = 0; k0 < g.Nz && !rc; k0 += ch) {
+        if ((rc = bzi_fft_chunk(ctx, k0, false))) break;
+        ctx->kr0 = k0; ctx->krn = ch;
+        rc = lean_project(ctx, s, L, G, adt, full);
+    }
+    ctx->krn = 0;
+    ctx->profile_mute--;
+    return rc;
+}
+
+// Lean seam (bz_tendency5_kernels.h): the tendency kernels read the prognostic fields only and derive u, v, w, theta, q^v, T on the
+// fly (bit-identical to the stored diagnostics), rho theta / rho q ping-pong between their own arrays and the G slots, the projection
+// of stages 1-2 writes momentum only; stage 3 of a diagnosed step runs the full projection + diagnosis kernel, so on return every
+// field of `s` (halos included) is what the per-operator sequence leaves.
+static int step_lean(bz_ctx *ctx, const bz_state *s, const bz_prognostic *U0, const bz_prognostic *G, double dt, bool diagnose)
+{
+    int rc;
+    if ((rc = bzi_zero_wall_faces(ctx, G, U0))) return rc;
+    const bool fork = ctx->side_scalar && !ctx->has_forcings;
+    for (int stage = 0; stage < 3; ++stage) {
+        const double alpha = BZ_SSP_RK3_ALPHA[stage];
+        LeanStage L;
+        bzi_lean_stage(s, U0, G, stage, &L);
+        if ((rc = bzi_lean_tendencies(ctx, L, G, dt, alpha, stage == 0, 0, fork ? 1 : 3))) return rc;
+        if (fork && (rc = bzi_scalar_pair_fork(ctx, L, G, dt, alpha, stage == 0))) return rc;
+        // the bottom fluxes of the stage (bzi_lean_forcings_ok), evaluated from the intact previous-stage momentum and added, weighted alpha dt, to
+        // what the fused RK updates just wrote: the predictor momentum in the G slots and rho theta / rho q in the stage's output buffers (the Coriolis /
+        // profile terms went into the RK epilogues: Lean5::mforce, bz_tendency5.hip; T is no stored field here: the next stage derives it from oa, ob)
+        if (ctx->has_forcings && (rc = bzi_flux_bc(ctx, &L.sin, G->rho_u, G->rho_v, L.oa, L.ob, alpha * dt))) return rc;
+        if ((rc = lean_solve_and_project(ctx, s, L, G, alpha * dt, diagnose && stage == 2, fork))) return rc;
+    }
+    bzi_lean_step_done(ctx, diagnose);
     return BZ_OK;
 }
 
-// the lean whole-step seam applies: dry / vapour WENO5 theta model without closure, bulk fluxes, relaxation, tracers, microphysics
-// (walls in y ((Periodic, Bounded, Bounded)) ride it too: WY kernels, wall rows in the projection kernels)
-static bool anelastic_lean_tier(const bz_ctx *ctx)
+// Fused-RK tier: tendencies and the following RK update in one pass (bz_tendency.hip: bzi_tendencies_fused_rk).  The tendency of stage s is
+// evaluated where the reference applies it (at the start of stage s, from the state left by stage s-1), the predictor momentum goes to the G arrays
+// and is projected from there into the state arrays, rho_theta / rho_q advance in place.  G never makes the round trip through HBM.
+// lsum_in: the level sums the previous step of this call left are fresh (one_anelastic_step).
+static int step_fused_rk(bz_ctx *ctx, const bz_state *s, const bz_prognostic *U0, const bz_prognostic *G, double dt, bool lsum_in)
 {
-    const bool walls_lean = ctx->dg.bounded_y && ctx->walls_lean_ok;
-    return (ctx->fused_ok || walls_lean) && ctx->fuse_rk && ctx->lean && ctx->weno_R == 3 && ctx->scalar_R == 3 && !ctx->compressible && ctx->dg.formulation == 0 && ctx->dg.microphysics == 0 &&
-        (!ctx->has_forcings || bzi_lean_forcings_ok(ctx)) && !ctx->has_bulk && !ctx->has_closure && !ctx->has_relaxation && ctx->n_tracers == 0 && !ctx->bounded_mask &&
-        (long long)ctx->dg.Sxy * (ctx->dg.Nz + 2 * ctx->dg.Hz + 1) < (1LL << 32);
+    int rc;
+    if ((rc = bzi_zero_wall_faces(ctx, G))) return rc;
+    // momentum terms of the forcing stack in the epilogues of the stored-velocity momentum kernels (round 5): the stage's subsidence
+    // profiles are built first (from the stored u, v, theta, q of the stage start, which the tendency kernels do not touch)
+    const bool fold = ctx->has_forcings && ctx->weno_R == 3 && bzi_k6_stored_ok(ctx) && ctx->tiled_tendencies && !ctx->tune.no_fuse_forcing && !ctx->tune.no_fold_forcing;
+    for (int stage = 0; stage < 3; ++stage) {
+        const double alpha = BZ_SSP_RK3_ALPHA[stage];
+        if (stage == 0) ctx->lsum_fresh = lsum_in;
+        if (fold && (rc = bzi_compute_forcings(ctx, s))) return rc;
+        ctx->fold_momentum_forcing = fold;
+        rc = bzi_tendencies_fused_rk(ctx, s, U0, G, dt, alpha, stage == 0);
+        ctx->fold_momentum_forcing = false;
+        if (rc) return rc;
+        if ((rc = bzi_fused_rk_physics(ctx, s, G, dt, alpha, stage == 0, fold))) return rc;
+        if (ctx->dg.bounded_y && (rc = bzi_fill_halo(ctx, G->rho_v, BZ_HALO_YFACE))) return rc;      // wall faces j = 0, Ny of the predictor (the source term reads face Ny)
+        if ((rc = bzi_poisson_from_momentum(ctx, s, alpha * dt, G))) return rc;
+        // pressure_anomaly is a diagnostic nobody reads inside the step: only the last stage scatters it
+        // (the horizontal sums of the u, v, theta, q it stores ride along: the next stage's subsidence profiles, bz_forcing.hip)
+        const bool ride = bzi_level_sums_ride(ctx) && ctx->d_lsum_rows;
+        if ((rc = bzi_project_diagnose(ctx, s, alpha * dt, nullptr, nullptr, G, stage == 2, nullptr, nullptr, ride))) return rc;
+        ctx->lsum_fresh = ride;
+        if ((rc = bzi_tracer_specific(ctx))) return rc;
+        if ((rc = bzi_surface_layer_stage(ctx, s, stage, dt))) return rc;      // update_boundary_conditions! of the stage's update_state!
+    }
+    ctx->lsum_step_last = ctx->lsum_fresh;
+    ctx->G_is_predictor = true;
+    return BZ_OK;
+}
+
+// Fused tier: same arithmetic as the operators, fewer passes over HBM (bz_fused.hip): store_initial_state! rides on the first RK update, the source
+// term uses wrap indexing instead of a halo fill, and the projection, velocity / thermodynamic diagnosis and every halo fill of
+// update_state! are one kernel.
+static int step_fused(bz_ctx *ctx, const bz_state *s, const bz_prognostic *U0, const bz_prognostic *G, double dt)
+{
+    int rc;
+    if (ctx->G_is_predictor && (rc = bz_compute_tendencies(ctx, s, G))) return rc;
+    for (int stage = 0; stage < 3; ++stage) {
+        const double alpha = BZ_SSP_RK3_ALPHA[stage];
+        if ((rc = bz_compute_flux_bc_tendencies(ctx, s, G))) return rc;          // :229,243,257
+        if ((rc = bzi_rk3_fused(ctx, s, U0, G, dt, alpha, stage == 0))) return rc;
+        if (ctx->dg.microphysics == 2 && (rc = bzi_kessler_rk3(ctx, dt, alpha, stage == 0))) return rc;
+        if ((rc = bzi_tracer_rk3(ctx, dt, alpha, stage == 0))) return rc;
+        if ((rc = bzi_poisson_from_momentum(ctx, s, alpha * dt, nullptr))) return rc;
+        if ((rc = bzi_project_diagnose(ctx, s, alpha * dt))) return rc;
+        if ((rc = bzi_tracer_specific(ctx))) return rc;
+        if ((rc = bzi_surface_layer_stage(ctx, s, stage, dt))) return rc;
+        if ((rc = bz_compute_tendencies(ctx, s, G))) return rc;
+    }
+    // microphysics_model_update!(model.microphysics, model) closes the step (ssp_runge_kutta_3.jl:262-263)
+    if (ctx->dg.microphysics == 2 && (rc = bzi_kessler_update(ctx, s, G, dt))) return rc;
+    return BZ_OK;
+}
+
+// Operators tier: the reference's own call order
+static int step_operators(bz_ctx *ctx, const bz_state *s, const bz_prognostic *U0, const bz_prognostic *G, double dt)
+{
+    int rc;
+    if (ctx->G_is_predictor && (rc = bz_compute_tendencies(ctx, s, G))) return rc;
+    if ((rc = bz_store_initial_state(ctx, s, U0))) return rc;               // :223
+    for (int stage = 0; stage < 3; ++stage) {
+        const double alpha = BZ_SSP_RK3_ALPHA[stage];
+        if ((rc = bz_compute_flux_bc_tendencies(ctx, s, G))) return rc;              // :229,243,257
+        if ((rc = bz_ssp_rk3_substep(ctx, s, U0, G, dt, alpha))) return rc;          // :230,244,258
+        if ((rc = bz_compute_pressure_correction(ctx, s, alpha * dt))) return rc;    // :232,246,260
+        if ((rc = bz_make_pressure_correction(ctx, s, alpha * dt))) return rc;       // :233,247,261
+        if ((rc = bz_update_state(ctx, s, G, 1))) return rc;                         // :236,250,270
+        if ((rc = bzi_surface_layer_stage(ctx, s, stage, dt))) return rc;
+    }
+    if (ctx->dg.microphysics == 2 && (rc = bzi_kessler_update(ctx, s, G, dt))) return rc;
+    return BZ_OK;
+}
+
+// One step on a single-device context.  A hipGraph records this body (one_anelastic_step): nothing below allocates or synchronises,
+// and G_is_predictor, lean_step_last, lsum_step_last are what the recording saves after it (bz_graph.hip).
+static int anelastic_step_body(bz_ctx *ctx, bz_tier tier, const bz_state *s, const bz_prognostic *U0, const bz_prognostic *G, double dt, bool diagnose)
+{
+    ctx->lean_step_last = false;
+    ctx->lsum_step_last = false;
+    const bool lsum_in = ctx->lsum_fresh;      // every tier but the fused-RK one leaves no sums behind
+    ctx->lsum_fresh = false;
+    if (tier == BZ_TIER_LEAN) return step_lean(ctx, s, U0, G, dt, diagnose);
+    if (tier == BZ_TIER_FUSED_RK) return step_fused_rk(ctx, s, U0, G, dt, lsum_in);
+    if (tier == BZ_TIER_FUSED) return step_fused(ctx, s, U0, G, dt);
+    return step_operators(ctx, s, U0, G, dt);
 }
 
 static int one_anelastic_step(bz_ctx *ctx, const bz_state *s, const bz_prognostic *U0, const bz_prognostic *G, double dt, bool diagnose)
@@ -172,10 +311,11 @@ static int one_anelastic_step(bz_ctx *ctx, const bz_state *s, const bz_prognosti
                           "or a host-side distributed driver";
         return BZ_ERR_UNSUPPORTED;
     }
+    const bz_tier tier = bzi_anelastic_tier(ctx);
     // the tiers other than the lean seam start from the stored diagnostics: if undiagnosed lean steps came before (the configuration
     // changed in between), rebuild them — here, outside the region a graph records (a rebuild baked into a recorded step would run, and
     // reset the moisture scan's word, on every replay)
-    if (ctx->diagnostics_stale && !anelastic_lean_tier(ctx)) { const int rcs = bz_update_state(ctx, s, G, 0); if (rcs) return rcs; }
+    if (ctx->diagnostics_stale && tier != BZ_TIER_LEAN) { const int rcs = bz_update_state(ctx, s, G, 0); if (rcs) return rcs; }
     // launch-bound grids replay the recorded step (bz_graph.hip); a failed recording has executed nothing and falls through
     // (the host's view of the moisture scan selects the kernels a recording holds; so does the source of the first stage's level sums)
     const int kind = 1 + (diagnose ? 0 : 16) + 32 * ctx->q_host + (ctx->lsum_fresh ? 128 : 0);
@@ -189,11 +329,11 @@ static int one_anelastic_step(bz_ctx *ctx, const bz_state *s, const bz_prognosti
     }
     const bool lsum_in = ctx->lsum_fresh;
     if (capture) {
-        rc = anelastic_step_body(ctx, s, U0, G, dt, diagnose);
+        rc = anelastic_step_body(ctx, tier, s, U0, G, dt, diagnose);
         if ((rc = bzi_graph_end(ctx, key, rc)) != -1) return rc;
         ctx->lsum_fresh = lsum_in;      // nothing ran
     }
-    return anelastic_step_body(ctx, s, U0, G, dt, diagnose);
+    return anelastic_step_body(ctx, tier, s, U0, G, dt, diagnose);
 }
 
 // The level sums of SubsidenceForcing ride on the projection + diagnosis kernel (bz_fused.hip) from one stage to the next INSIDE a call;
@@ -212,8 +352,7 @@ static int surface_layer_first_step(bz_ctx *ctx, const bz_state *s)
     return bz_surface_layer_initialize(ctx, s);
 }
 
-extern "C" int bz_time_step_anelastic(bz_ctx *ctx, const bz_state *s, const bz_prognostic *U0,
-                                      const bz_prognostic *G, double dt)
+extern "C" int bz_time_step_anelastic(bz_ctx *ctx, const bz_state *s, const bz_prognostic *U0, const bz_prognostic *G, double dt)
 {
     if (!ctx || !s || !U0 || !G) return BZ_ERR_INVALID;
     level_sums_open(ctx);
@@ -259,207 +398,3 @@ int bzi_refresh_diagnostics(bz_ctx *ctx, const bz_state *s, const char *who)
 }
 
 extern "C" int bz_diagnostics_stale(const bz_ctx *ctx) { return ctx ? (ctx->diagnostics_stale ? 1 : 0) : BZ_ERR_INVALID; }
-
-static int anelastic_step_body(bz_ctx *ctx, const bz_state *s, const bz_prognostic *U0, const bz_prognostic *G, double dt, bool diagnose)
-{
-    ctx->lean_step_last = false;
-    ctx->lsum_step_last = false;
-    const bool lsum_in = ctx->lsum_fresh;      // every other tier leaves no sums behind
-    ctx->lsum_fresh = false;
-    int rc;
-    const double alphas[3] = {1.0, 1.0 / 4.0, 2.0 / 3.0};                   // :99-101
-    // walls in y ((Periodic, Bounded, Bounded)) ride the lean seam too (WY kernels, wall rows in the projection kernels); every other
-    // configuration with walls steps operator by operator
-    const bool walls_lean = ctx->dg.bounded_y && ctx->walls_lean_ok;
-    const bool lean_tier = anelastic_lean_tier(ctx);
-    // (the other tiers start from the stored diagnostics: one_anelastic_step rebuilt them if undiagnosed lean steps came before)
-    if (lean_tier) {
-        // Lean seam (bz_tendency5_kernels.h): the tendency kernels read the prognostic fields only and derive u, v, w, theta,
-        // q^v, T on the fly (bit-identical to the stored diagnostics), rho theta / rho q ping-pong between their own arrays
-        // and the G slots, the projection of stages 1-2 writes momentum only; stage 3 runs the full projection + diagnosis
-        // kernel, so on return every field of `s` (halos included) is what the per-operator sequence leaves.
-        const DevGrid &g = ctx->dg;
-        BZ_HIP(hipMemsetAsync(G->rho_w + g.Sxy * g.Hz, 0, g.Sxy * sizeof(double), ctx->stream));                 // wall faces of the
-        BZ_HIP(hipMemsetAsync(G->rho_w + g.Sxy * (g.Hz + g.Nz), 0, g.Sxy * sizeof(double), ctx->stream));        // predictor stay 0,
-        BZ_HIP(hipMemsetAsync(U0->rho_w + g.Sxy * g.Hz, 0, g.Sxy * sizeof(double), ctx->stream));                // and so do those of the
-        BZ_HIP(hipMemsetAsync(U0->rho_w + g.Sxy * (g.Hz + g.Nz), 0, g.Sxy * sizeof(double), ctx->stream));       // projected momentum of stages 1-2
-        for (int stage = 0; stage < 3; ++stage) {
-            const double alpha = alphas[stage];
-            const bool full = diagnose && stage == 2;      // projection + diagnosis (else: momentum-only projection)
-            LeanStage LS;
-            bzi_lean_stage(s, U0, G, stage, &LS);
-            const bz_state *sin = &LS.sin, *sout = &LS.sout;
-            const bz_prognostic *u0 = &LS.u0;
-            const double *pa = LS.pa, *pb = LS.pb;
-            double *oa = LS.oa, *ob = LS.ob;
-            if (ctx->side_scalar && !ctx->has_forcings) {
-                // the scalar-pair kernel feeds nothing of the pressure solve: it runs on the side stream beside the source term,
-                // the transforms and the Thomas solve (issue-bound stencil kernel next to bandwidth-bound streaming kernels)
-                if ((rc = bzi_tendencies_lean(ctx, sin, u0, G, pa, pb, oa, ob, dt, alpha, stage == 0, 0, 1))) return rc;
-                BZ_HIP(hipEventRecord(ctx->ev_fork, ctx->stream));
-                BZ_HIP(hipStreamWaitEvent(ctx->side_stream, ctx->ev_fork, 0));
-                hipStream_t keep = ctx->stream;
-                ctx->stream = ctx->side_stream;
-                rc = bzi_tendencies_lean(ctx, sin, u0, G, pa, pb, oa, ob, dt, alpha, stage == 0, 0, 2);
-                ctx->stream = keep;
-                if (rc) return rc;
-                BZ_HIP(hipEventRecord(ctx->ev_join, ctx->side_stream));
-            } else if ((rc = bzi_tendencies_lean(ctx, sin, u0, G, pa, pb, oa, ob, dt, alpha, stage == 0))) return rc;
-            if (ctx->has_forcings) {
-                // the bottom fluxes of the stage (bzi_lean_forcings_ok), evaluated from the intact previous-stage momentum and added,
-                // weighted alpha dt, to what the fused RK updates just wrote: the predictor momentum in the G slots and rho theta /
-                // rho q in the stage's output buffers — as the fused-RK tier below does
-                // (the Coriolis / profile terms went into the RK epilogues of the momentum kernels: Lean5::mforce, bz_tendency5.hip)
-                if ((rc = bzi_flux_bc(ctx, sin, G->rho_u, G->rho_v, oa, ob, alpha * dt))) return rc;
-                // (T is no stored field inside the lean seam any more: the z-momentum kernel of the next stage derives it from oa, ob)
-            }
-            if (ctx->pchunk) {
-                // chunked pipeline: each level range goes source term -> x transform -> y transform (and, after the vertical solves,
-                // y -> x -> projection) back to back, so the intermediate passes find the range in the Infinity Cache
-                const int ch = ctx->pchunk;
-                rc = 0;
-                {
-                    ProfileScope ps(ctx, "poisson_source_term+fft_forward");
-                    ctx->profile_mute++;
-                    for (int k0 = 0; k0 < g.Nz && !rc; k0 += ch) {
-                        ctx->kr0 = k0; ctx->krn = ch;
-                        rc = bzi_poisson_source_fused(ctx, s, alpha * dt, nullptr, G);
-                        if (!rc) rc = bzi_fft_chunk(ctx, k0, true);
-                    }
-                    ctx->krn = 0;
-                    ctx->profile_mute--;
-                }
-                if (rc) return rc;
-                {
-                    ProfileScope ps(ctx, "poisson_tridiagonal");
-                    if ((rc = bzi_tridiag_launch(ctx, (double *)ctx->d_hat, 1.0 / ((double)g.Nx * (double)g.Ny), g.Ny, 1))) return rc;
-                }
-                if (ctx->side_scalar && !ctx->has_forcings) BZ_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
-                {
-                    ProfileScope ps(ctx, !full ? "poisson_fft_inverse+project_momentum" : "poisson_fft_inverse+project_and_diagnose");
-                    ctx->profile_mute++;
-                    for (int k0 = 0; k0 < g.Nz && !rc; k0 += ch) {
-                        rc = bzi_fft_chunk(ctx, k0, false);
-                        ctx->kr0 = k0; ctx->krn = ch;
-                        if (rc) break;
-                        if (!full) rc = bzi_project_lean(ctx, sout, alpha * dt, nullptr, nullptr, G, oa, ob);
-                        else rc = bzi_project_diagnose(ctx, s, alpha * dt, nullptr, nullptr, G, true, oa, ob);
-                    }
-                    ctx->krn = 0;
-                    ctx->profile_mute--;
-                }
-                if (rc) return rc;
-                continue;
-            }
-            if (ctx->xf && !ctx->pchunk) {
-                // hand-written x transforms (bz_xfft_kernels.h): the source term is evaluated inside the forward x pass; y transforms
-                // (contiguous) and vertical solves on the transposed spectrum
-                {
-                    ProfileScope ps(ctx, "poisson_source_term+fft_x");
-                    if ((rc = bzi_xf_forward(ctx, s, alpha * dt, G))) return rc;
-                }
-                if ((rc = bzi_xf_middle(ctx))) return rc;
-                {
-                    ProfileScope ps(ctx, "poisson_fft_x_inverse");
-                    if ((rc = bzi_xf_inverse(ctx))) return rc;
-                }
-                // the scalar-pair kernel of the side stream joins here: the projection kernels write the z-halo images of rho theta / rho q
-                if (ctx->side_scalar && !ctx->has_forcings) BZ_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
-                if (!full) rc = bzi_project_lean(ctx, sout, alpha * dt, nullptr, nullptr, G, oa, ob);
-                else rc = bzi_project_diagnose(ctx, s, alpha * dt, nullptr, nullptr, G, true, oa, ob);
-                if (rc) return rc;
-                continue;
-            }
-            if ((rc = bzi_poisson_source_fused(ctx, s, alpha * dt, nullptr, G))) return rc;
-            if ((rc = bzi_poisson_spectral(ctx))) return rc;
-            if (ctx->side_scalar && !ctx->has_forcings) BZ_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
-            if (!full) rc = bzi_project_lean(ctx, sout, alpha * dt, nullptr, nullptr, G, oa, ob);
-            else rc = bzi_project_diagnose(ctx, s, alpha * dt, nullptr, nullptr, G, true, oa, ob);
-            if (rc) return rc;
-        }
-        bzi_lean_step_done(ctx, diagnose);
-        return BZ_OK;
-    }
-    // (walls in y: the generic order-7 / 9 kernels are wall-aware, the LDS-tiled order-5 kernels of this tier are not)
-    if ((ctx->fused_ok || (walls_lean && ctx->weno_R != 3)) && ctx->fuse_rk && ctx->scalar_R == ctx->weno_R && (ctx->weno_R == 3 || ctx->n_tracers == 0) && ctx->dg.formulation == 0 &&
-        ctx->dg.microphysics != 2 && !ctx->bounded_mask && !ctx->has_relaxation && !(ctx->has_forcings && ctx->tune.no_fuse_forcing)) {
-        // Tendencies and the following RK update in one pass (bz_tendency.hip: bzi_tendencies_fused_rk): the
-        // tendency of stage s is evaluated where the reference applies it (at the start of stage s, from the state
-        // left by stage s-1), the predictor momentum goes to the G arrays and is projected from there into the
-        // state arrays, rho_theta / rho_q advance in place.  G never makes the round trip through HBM.
-        const DevGrid &g = ctx->dg;
-        BZ_HIP(hipMemsetAsync(G->rho_w + g.Sxy * g.Hz, 0, g.Sxy * sizeof(double), ctx->stream));                 // wall faces of the
-        BZ_HIP(hipMemsetAsync(G->rho_w + g.Sxy * (g.Hz + g.Nz), 0, g.Sxy * sizeof(double), ctx->stream));        // predictor stay 0
-        for (int stage = 0; stage < 3; ++stage) {
-            const double alpha = alphas[stage];
-            // momentum terms of the forcing stack in the epilogues of the stored-velocity momentum kernels (round 5): the stage's subsidence
-            // profiles are built first (from the stored u, v, theta, q of the stage start, which the tendency kernels do not touch)
-            const bool fold = ctx->has_forcings && ctx->weno_R == 3 && bzi_k6_stored_ok(ctx) && ctx->tiled_tendencies && !ctx->tune.no_fuse_forcing && !ctx->tune.no_fold_forcing;
-            if (stage == 0) ctx->lsum_fresh = lsum_in;
-            if (fold && (rc = bzi_compute_forcings(ctx, s))) return rc;
-            ctx->fold_momentum_forcing = fold;
-            rc = bzi_tendencies_fused_rk(ctx, s, U0, G, dt, alpha, stage == 0);
-            ctx->fold_momentum_forcing = false;
-            if (rc) return rc;
-            if (ctx->n_tracers) {       // tracers ride beside the fused kernels: tendency from the previous-stage state, RK in place
-                if ((rc = bzi_tracer_tendencies(ctx, s))) return rc;
-                if ((rc = bzi_tracer_rk3(ctx, dt, alpha, stage == 0))) return rc;
-            }
-            if (ctx->has_closure &&
-                (rc = bzi_apply_closure(ctx, s, G->rho_u, G->rho_v, G->rho_w, s->rho_theta, s->rho_q, alpha * dt))) return rc;
-            if (ctx->has_forcings) {
-                // forcing, Coriolis and bottom fluxes of the stage, evaluated from the still-intact previous-stage state and
-                // added to what the fused RK update just wrote, weighted alpha dt
-                if ((rc = bzi_apply_forcings(ctx, s, G->rho_u, G->rho_v, s->rho_theta, s->rho_q, alpha * dt, fold))) return rc;
-            }
-            if ((ctx->has_forcings || ctx->has_bulk) &&
-                (rc = bzi_flux_bc(ctx, s, G->rho_u, G->rho_v, s->rho_theta, s->rho_q, alpha * dt))) return rc;
-            if (g.bounded_y && (rc = bzi_fill_halo(ctx, G->rho_v, BZ_HALO_YFACE))) return rc;      // wall faces j = 0, Ny of the predictor (the source term reads face Ny)
-            if ((rc = bzi_poisson_from_momentum(ctx, s, alpha * dt, G))) return rc;
-            // pressure_anomaly is a diagnostic nobody reads inside the step: only the last stage scatters it
-            // (the horizontal sums of the u, v, theta, q it stores ride along: the next stage's subsidence profiles, bz_forcing.hip)
-            const bool ride = bzi_level_sums_ride(ctx) && ctx->d_lsum_rows;
-            if ((rc = bzi_project_diagnose(ctx, s, alpha * dt, nullptr, nullptr, G, stage == 2, nullptr, nullptr, ride))) return rc;
-            ctx->lsum_fresh = ride;
-            if ((rc = bzi_tracer_specific(ctx))) return rc;
-            if ((rc = bzi_surface_layer_stage(ctx, s, stage, dt))) return rc;      // update_boundary_conditions! of the stage's update_state!
-        }
-        ctx->lsum_step_last = ctx->lsum_fresh;
-        ctx->G_is_predictor = true;
-        return BZ_OK;
-    }
-    if (ctx->fused_ok) {
-        if (ctx->G_is_predictor && (rc = bz_compute_tendencies(ctx, s, G))) return rc;
-        // Same arithmetic, fewer passes over HBM (bz_fused.hip): store_initial_state! rides on the first
-        // RK update, the source term uses wrap indexing instead of a halo fill, and the projection,
-        // velocity / thermodynamic diagnosis and every halo fill of update_state! are one kernel.
-        for (int stage = 0; stage < 3; ++stage) {
-            const double alpha = alphas[stage];
-            if ((rc = bz_compute_flux_bc_tendencies(ctx, s, G))) return rc;          // :229,243,257
-            if ((rc = bzi_rk3_fused(ctx, s, U0, G, dt, alpha, stage == 0))) return rc;
-            if (ctx->dg.microphysics == 2 && (rc = bzi_kessler_rk3(ctx, dt, alpha, stage == 0))) return rc;
-            if ((rc = bzi_tracer_rk3(ctx, dt, alpha, stage == 0))) return rc;
-            if ((rc = bzi_poisson_from_momentum(ctx, s, alpha * dt, nullptr))) return rc;
-            if ((rc = bzi_project_diagnose(ctx, s, alpha * dt))) return rc;
-            if ((rc = bzi_tracer_specific(ctx))) return rc;
-            if ((rc = bzi_surface_layer_stage(ctx, s, stage, dt))) return rc;
-            if ((rc = bz_compute_tendencies(ctx, s, G))) return rc;
-        }
-        // microphysics_model_update!(model.microphysics, model) closes the step (ssp_runge_kutta_3.jl:262-263)
-        if (ctx->dg.microphysics == 2 && (rc = bzi_kessler_update(ctx, s, G, dt))) return rc;
-        return BZ_OK;
-    }
-    if (ctx->G_is_predictor && (rc = bz_compute_tendencies(ctx, s, G))) return rc;
-    if ((rc = bz_store_initial_state(ctx, s, U0))) return rc;               // :223
-    for (int stage = 0; stage < 3; ++stage) {
-        const double alpha = alphas[stage];
-        if ((rc = bz_compute_flux_bc_tendencies(ctx, s, G))) return rc;              // :229,243,257
-        if ((rc = bz_ssp_rk3_substep(ctx, s, U0, G, dt, alpha))) return rc;          // :230,244,258
-        if ((rc = bz_compute_pressure_correction(ctx, s, alpha * dt))) return rc;    // :232,246,260
-        if ((rc = bz_make_pressure_correction(ctx, s, alpha * dt))) return rc;       // :233,247,261
-        if ((rc = bz_update_state(ctx, s, G, 1))) return rc;                         // :236,250,270
-        if ((rc = bzi_surface_layer_stage(ctx, s, stage, dt))) return rc;
-    }
-    if (ctx->dg.microphysics == 2 && (rc = bzi_kessler_update(ctx, s, G, dt))) return rc;
-    return BZ_OK;
-}

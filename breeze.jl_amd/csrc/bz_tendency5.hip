@@ -123,7 +123,7 @@ static int lean_launch(bz_ctx *ctx, const bz_state *s, const bz_prognostic *U0, 
     L.pi_dry = ColPtr(ctx->d_pi_dry + g.Hz);
     L.lev = (const LevRow5 *)ctx->d_lev_rows + g.Hz;
     L.qstate = bzi_moisture_state(ctx);
-    const int qh = L.qstate ? ctx->q_host : 2;      // the host's view of the scan's verdict (bz_step.hip); no word: the general bodies only
+    const int qh = L.qstate ? ctx->q_host : 2;      // the host's view of the scan's verdict (bz_moisture.hip); no word: the general bodies only
     L.mforce = 0; L.cor_f = 0.0; L.Fu = ColPtr(nullptr); L.Fv = ColPtr(nullptr); L.Su = ColPtr(nullptr); L.Sv = ColPtr(nullptr);
     if (ctx->has_forcings && bzi_lean_forcings_ok(ctx)) {      // the stack's momentum terms ride the RK epilogues of k6_u / k6_v
         const int m = ctx->forcing_static_mask;

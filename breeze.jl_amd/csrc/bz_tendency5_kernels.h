@@ -134,7 +134,7 @@ struct Lean5 {
     // compressible model, where rho is a 3-D field and nothing can be derived from a column constant): vel = u | v | w of the component,
     // bT / bq = the buoyancy inputs of the z-momentum kernel (T and q; pressure and total density in the compressible form)
     const double *vel, *bT, *bq;
-    const int *qstate;               // moisture scan (bz_step.hip: bzi_scan_moisture): *qstate == 1 <=> rho q is identically zero; nullptr: not known
+    const int *qstate;               // moisture scan (bz_moisture.hip: bzi_scan_moisture): *qstate == 1 <=> rho q is identically zero; nullptr: not known
     int xcd;                         // 1: XCD-contiguous block order (grid size divisible by 8)
     int by0, bys;                    // tile row of block row b is by0 + b * bys (sub-launches of the slab driver: interior rows
                                      // while the y-halo exchange is in flight, then the two edge rows)
@@ -224,7 +224,7 @@ __device__ __forceinline__ double bz_symm4y(double qm2, double qm1, double q0, d
 // shuffle + the batched out-of-wave flux, z stencils in register rings.
 // ---------------------------------------------------------------------------------------------------------------------
 // DRYQ: the second scalar is identically zero in the whole field (Lean5::qstate, set by the scan that opens every step call:
-// bz_step.hip: bzi_scan_moisture) — rho q of a dry run, which the reference advects all the same
+// bz_moisture.hip: bzi_scan_moisture) — rho q of a dry run, which the reference advects all the same
 // (update_atmosphere_model_state.jl:333-343).  Every flux of it is an exact zero and its update is 0 -> 0, so the instantiation
 // neither loads nor stores anything of q: 4.6 of the kernel's 13 words per cell.  Identical bits: the arrays stay zero.
 template <int TY, bool WY, bool DRYQ>

@@ -185,7 +185,7 @@ struct FluxBuf {
     // stores (1 - alpha) u0 + alpha (uold + dt G); uold = the prognostic field the tendency belongs to (E.mode 0: store G)
     RKEpilogue E;
     const double *uold;
-    // fused-RK moisture launch only: the moisture scan's word (bz_step.hip: bzi_scan_moisture); where rho q is identically zero its
+    // fused-RK moisture launch only: the moisture scan's word (bz_moisture.hip: bzi_scan_moisture); where rho q is identically zero its
     // update is 0 -> 0 and both passes of the launch return at once (nothing is read or written; U0 of rho q is then never read either)
     const int *skip_if_dry;
 };

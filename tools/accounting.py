@@ -97,7 +97,7 @@ COMPULSORY_WORDS = {
     "kessler_species_tendencies": 6,
     "store_initial_state": 12,
 }
-# Dry runs (rho q identically zero, found by the moisture scan that opens every step call — bz_step.hip: bzi_scan_moisture): the two lean
+# Dry runs (rho q identically zero, found by the moisture scan that opens every step call — bz_moisture.hip: bzi_scan_moisture): the two lean
 # kernels that would touch rho q skip it altogether, so their compulsory array lists shrink; bench.py prices a run in these when its
 # profile shows the scan and the workload set no moisture (and reports the moist variant of the same workload beside it)
 COMPULSORY_WORDS_DRY = {
