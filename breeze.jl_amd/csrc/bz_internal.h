@@ -363,6 +363,14 @@ void bzi_read_tuning(bz_tuning &t);
             return BZ_ERR_UNSUPPORTED;                                                                                       \
         }                                                                                                                    \
     } while (0)
+// the entry points of the anelastic step (momentum, pressure solve) on a context with PrescribedDynamics
+#define BZ_REJECT_KINEMATIC(ctx, who)                                                                                        \
+    do {                                                                                                                     \
+        if ((ctx) && (ctx)->kinematic) {                                                                                     \
+            (ctx)->last_error = who ": the context has PrescribedDynamics (no momentum, no pressure solve); use bz_time_steps_kinematic"; \
+            return BZ_ERR_UNSUPPORTED;                                                                                       \
+        }                                                                                                                    \
+    } while (0)
 #define BZ_HALO_XFACE 8      // the same for x faces (rho u, u) on a Bounded x
 #define BZ_HALO_YFACE 4      // halo kind bit: the field sits on y faces (rho v, v): wall faces instead of a no-flux row on a Bounded y
 struct bz_ctx;
@@ -506,6 +514,13 @@ struct bz_ctx {
     // advection = (; rho_q = WENO(order = 5, bounds = (lo, hi))) (bz_set_bounds_preserving_advection, bz_bounded.hip)
     int bounded_mask = 0;             // 1 moisture, 2 microphysical species, 4 tracers
     double bounded_lo = 0.0, bounded_hi = 1.0;
+    // dynamics = PrescribedDynamics(reference_state) (bz_set_prescribed_dynamics, bz_kinematic.hip): given velocities, only the scalars advance
+    bool kinematic = false;
+    bool kin_correction = false;      // scalar tendencies carry + c div_rhoU
+    double *d_kin_div = nullptr;      // D = div_rhoU at cell centres (parent-shaped), formed while the correction is on
+    uint64_t velocity_epoch = 0;      // bumped by every bz_set_prescribed_dynamics call (the host's set path): the velocities may have changed
+    uint64_t kin_div_epoch = 0;       // velocity epoch and velocity arrays D was last formed from
+    const double *kin_div_u = nullptr, *kin_div_v = nullptr, *kin_div_w = nullptr;
     struct BzComm *comm = nullptr;    // y-slab communicator (bz_comm_init_rccl / bz_comm_init_local, bz_comm.hip)
     // profiling
     bool profiling = false;
@@ -623,6 +638,9 @@ int bzi_comm_join_pending(bz_ctx *ctx);
 // than the prognostic state.  With the state at hand they are rebuilt first (bz_update_state, on slab contexts with its halo exchange);
 // without it (s == nullptr) the call fails with BZ_ERR_INVALID and a message instead of answering from stale fields
 int bzi_refresh_diagnostics(bz_ctx *ctx, const bz_state *s, const char *who);
+// ---- the kinematic driver (bz_kinematic.hip) ----
+int bzi_kinematic_update_state(bz_ctx *ctx, const bz_state *s, const bz_prognostic *G, int compute_tendencies);
+void bzi_kinematic_teardown(bz_ctx *ctx);
 // ---- the anelastic whole step (bz_step.hip; the slab drivers of bz_comm.hip share all of it) ----
 enum bz_tier { BZ_TIER_LEAN, BZ_TIER_FUSED_RK, BZ_TIER_FUSED, BZ_TIER_OPERATORS };
 bz_tier bzi_anelastic_tier(const bz_ctx *ctx);      // the tier a step of this context takes: the only statement of tier eligibility

@@ -836,6 +836,7 @@ int bzi_poisson_solve(bz_ctx *ctx, const bz_state *s, double dt)
 extern "C" int bz_compute_pressure_correction(bz_ctx *ctx, const bz_state *s, double dt)
 {
     if (!ctx || !s) return BZ_ERR_INVALID;
+    BZ_REJECT_KINEMATIC(ctx, "bz_compute_pressure_correction");
     if (ctx->slab_mode) {
         ctx->last_error = "bz_compute_pressure_correction: y-slab contexts solve through bz_poisson_source_term / "
                           "bz_spectral_tridiagonal_solve / bz_project_and_diagnose";

@@ -23,6 +23,7 @@ extern "C" int bz_ssp_rk3_substep_fused(bz_ctx *ctx, const bz_state *s, const bz
                                         const bz_prognostic *G, double dt, double alpha, int first)
 {
     if (!ctx || !s || !U0 || !G) return BZ_ERR_INVALID;
+    BZ_REJECT_KINEMATIC(ctx, "bz_ssp_rk3_substep_fused");
     if (ctx->G_is_predictor) {
         int rc = bz_compute_tendencies(ctx, s, G);
         if (rc) return rc;
@@ -202,6 +203,7 @@ extern "C" int bz_tendencies_fused_rk(bz_ctx *ctx, const bz_state *s, const bz_p
                                       double dt, double alpha, int first)
 {
     if (!ctx || !s || !U0 || !G) return BZ_ERR_INVALID;
+    BZ_REJECT_KINEMATIC(ctx, "bz_tendencies_fused_rk");
     int rc = first ? bzi_zero_wall_faces(ctx, G) : BZ_OK;
     if (rc) return rc;
     rc = bzi_tendencies_fused_rk(ctx, s, U0, G, dt, alpha, first != 0);

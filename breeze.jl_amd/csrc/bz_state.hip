@@ -139,6 +139,7 @@ static inline dim3 cell_grid(const DevGrid &g, int nz) { return dim3((g.Nx + TX 
 extern "C" int bz_compute_velocities(bz_ctx *ctx, const bz_state *s)
 {
     if (!ctx || !s) return BZ_ERR_INVALID;
+    BZ_REJECT_KINEMATIC(ctx, "bz_compute_velocities");
     const DevGrid &g = ctx->dg;
     // halos of momentum first (update_atmosphere_model_state.jl:135-136)
     double *mf[3] = {s->rho_u, s->rho_v, s->rho_w};
@@ -176,6 +177,7 @@ extern "C" int bz_compute_auxiliary_thermodynamic_variables(bz_ctx *ctx, const b
 extern "C" int bz_store_initial_state(bz_ctx *ctx, const bz_state *s, const bz_prognostic *U0)
 {
     if (!ctx || !s || !U0) return BZ_ERR_INVALID;
+    BZ_REJECT_KINEMATIC(ctx, "bz_store_initial_state");
     const DevGrid &g = ctx->dg;
     ProfileScope ps(ctx, "store_initial_state");
     long long nc = g.Sxy * (g.Nz + 2 * g.Hz), nw = g.Sxy * (g.Nz + 1 + 2 * g.Hz);
@@ -197,6 +199,7 @@ extern "C" int bz_ssp_rk3_substep(bz_ctx *ctx, const bz_state *s, const bz_progn
                                   const bz_prognostic *G, double dt, double alpha)
 {
     if (!ctx || !s || !U0 || !G) return BZ_ERR_INVALID;
+    BZ_REJECT_KINEMATIC(ctx, "bz_ssp_rk3_substep");
     if (ctx->G_is_predictor) {      // a fused whole step left predictor momentum in G: rebuild the tendencies first
         int rc = bz_compute_tendencies(ctx, s, G);
         if (rc) return rc;
@@ -220,6 +223,7 @@ extern "C" int bz_ssp_rk3_substep(bz_ctx *ctx, const bz_state *s, const bz_progn
 extern "C" int bz_make_pressure_correction(bz_ctx *ctx, const bz_state *s, double dt)
 {
     if (!ctx || !s) return BZ_ERR_INVALID;
+    BZ_REJECT_KINEMATIC(ctx, "bz_make_pressure_correction");
     const DevGrid &g = ctx->dg;
     ProfileScope ps(ctx, "make_pressure_correction");
     hipLaunchKernelGGL(k_pressure_correct, cell_grid(g, g.Nz), dim3(TX, TY), 0, ctx->stream, g, s->rho_u,
@@ -231,6 +235,7 @@ extern "C" int bz_make_pressure_correction(bz_ctx *ctx, const bz_state *s, doubl
 extern "C" int bz_max_abs_divergence(bz_ctx *ctx, const bz_state *s, double *out)
 {
     if (!ctx || !s || !out) return BZ_ERR_INVALID;
+    BZ_REJECT_KINEMATIC(ctx, "bz_max_abs_divergence");
     const DevGrid &g = ctx->dg;
     double *mf[3] = {s->rho_u, s->rho_v, s->rho_w};
     int mk[3] = {BZ_HALO_XFACE, BZ_HALO_YFACE, 1};

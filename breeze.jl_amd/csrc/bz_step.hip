@@ -10,6 +10,7 @@
 extern "C" int bz_update_state(bz_ctx *ctx, const bz_state *s, const bz_prognostic *G, int compute_tendencies)
 {
     if (!ctx || !s || (compute_tendencies && !G)) return BZ_ERR_INVALID;
+    if (ctx->kinematic) return bzi_kinematic_update_state(ctx, s, G, compute_tendencies);      // compute_velocities! is a no-op there (bz_kinematic.hip)
     int rc;
     if (ctx->comm && (rc = bzi_comm_join_pending(ctx))) return rc;      // an undiagnosed last stage leaves its halo exchange on the side stream
     ctx->diagnostics_stale = false;
@@ -355,6 +356,7 @@ static int surface_layer_first_step(bz_ctx *ctx, const bz_state *s)
 extern "C" int bz_time_step_anelastic(bz_ctx *ctx, const bz_state *s, const bz_prognostic *U0, const bz_prognostic *G, double dt)
 {
     if (!ctx || !s || !U0 || !G) return BZ_ERR_INVALID;
+    BZ_REJECT_KINEMATIC(ctx, "bz_time_step_anelastic");
     level_sums_open(ctx);
     int rc = bzi_scan_moisture(ctx, s);
     if (!rc) rc = surface_layer_first_step(ctx, s);
@@ -375,6 +377,7 @@ extern "C" int bz_time_steps_anelastic(bz_ctx *ctx, const bz_state *s, const bz_
                                        int diagnose_last)
 {
     if (!ctx || !s || !U0 || !G || n < 0) return BZ_ERR_INVALID;
+    BZ_REJECT_KINEMATIC(ctx, "bz_time_steps_anelastic");
     level_sums_open(ctx);
     if (n > 0) { const int rc = bzi_scan_moisture(ctx, s); if (rc) return rc; }
     if (n > 0) { const int rc = surface_layer_first_step(ctx, s); if (rc) return rc; }

@@ -494,6 +494,7 @@ static int compute_tendencies_by_operator(bz_ctx *ctx, const bz_state *s, const 
 extern "C" int bz_compute_tendencies(bz_ctx *ctx, const bz_state *s, const bz_prognostic *G)
 {
     if (!ctx || !s || !G) return BZ_ERR_INVALID;
+    BZ_REJECT_KINEMATIC(ctx, "bz_compute_tendencies");
     { const int rcs = bzi_refresh_diagnostics(ctx, s, "bz_compute_tendencies"); if (rcs) return rcs; }
     ctx->G_is_predictor = false;
     if (ctx->scalar_R != ctx->weno_R || ctx->weno_R == 3) return compute_tendencies_by_operator(ctx, s, G);

@@ -329,6 +329,9 @@ class LibrarySlabAtmosphereModel(AtmosphereModel):
                  standard_pressure=1e5, thermodynamic_constants=None, device=None, **kw):
         import torch
         G = global_grid
+        from .model import PrescribedDynamics
+        if isinstance(kw.get("dynamics"), PrescribedDynamics):
+            raise NotImplementedError("AtmosphereModel(dynamics = PrescribedDynamics(...)): y-slab (distributed) models are not implemented")
         if G.topology != (Periodic, Periodic, Bounded):
             raise NotImplementedError("slab decomposition implements topology (Periodic, Periodic, Bounded)")
         if G.Ny % world:

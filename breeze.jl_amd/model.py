@@ -134,6 +134,72 @@ class AnelasticDynamics:
         self.pressure_anomaly = None   # materialised by AtmosphereModel
 
 
+class PrescribedDynamics:
+    """PrescribedDynamics(reference_state; divergence_correction=false) (src/KinematicDriver/prescribed_dynamics.jl:27-84): the kinematic
+    driver.  Density and pressure are the reference state's, the velocities are ordinary fields set with `model.set(u=..., v=..., w=...)`,
+    and only the scalars (ρθ, moisture, tracers) advance; there is no momentum and no pressure solver.  With `divergence_correction` every
+    scalar tendency carries `+ c ∇·(ρU)` (kinematic_driver_time_stepping.jl:66-73), for velocity fields that are not anelastically
+    non-divergent."""
+
+    def __init__(self, reference_state, divergence_correction=False):
+        self.reference_state = reference_state
+        self.divergence_correction = bool(divergence_correction)
+        self.pressure_anomaly = None
+
+
+class PrescribedVelocityFields:
+    """PrescribedVelocityFields(u=f(x, y, z, t), ...) of the reference (functions of time): named so that the constructor can refuse it."""
+
+    def __init__(self, u=None, v=None, w=None, parameters=None):
+        self.u, self.v, self.w, self.parameters = u, v, w, parameters
+
+
+def _check_kinematic_options(model_type, grid, dynamics, advection, formulation, closure, microphysics, forcing, boundary_conditions, velocities,
+                             coriolis):
+    """What AtmosphereModel(dynamics = PrescribedDynamics(...)) runs: (Periodic, Periodic | Flat, Bounded), Float64, WENO(order = 5), the
+    potential-temperature formulation, microphysics nothing or warm-phase saturation adjustment, tracers, one GPU.  Everything else of the
+    reference's kinematic driver says so here, by name."""
+    from .microphysics import SaturationAdjustment
+
+    def no(what):
+        raise NotImplementedError(f"AtmosphereModel(dynamics = PrescribedDynamics(...)): {what} not implemented")
+    if not isinstance(dynamics.reference_state, ReferenceState):
+        no("prognostic density (PrescribedDynamics(ρ_field)) is")
+    if model_type is not AtmosphereModel:
+        no("y-slab (distributed) models are")
+    if grid.topology not in ((Periodic, Periodic, Bounded), (Periodic, Flat, Bounded)):
+        no(f"topology {grid.topology} is")
+    if grid.ftype != 8:
+        no("Float32 grids are")
+    schemes = list(advection.values()) if isinstance(advection, dict) else [advection]
+    for s in schemes:
+        if s is None or isinstance(s, Centered):
+            no("Centered advection is (pass advection = WENO(order = 5)); it is")
+        if not isinstance(s, WENO):
+            no(f"advection scheme {type(s).__name__} is")
+        if s.bounds is not None:
+            no("bounds-preserving advection (WENO(bounds = ...)) is")
+        if s.order != 5:
+            no(f"WENO(order = {s.order}) is")
+        if s.ft2_hypothesis:
+            no("WENO(ft2_hypothesis != 0) is")
+    if str(formulation).lstrip(":") != "LiquidIcePotentialTemperature":
+        no(f"the {str(formulation).lstrip(':')} formulation is")
+    if microphysics is not None and not isinstance(microphysics, SaturationAdjustment):
+        no(f"microphysics {type(microphysics).__name__} (Kessler) is")
+    if closure is not None:
+        no("a closure is")
+    if forcing is not None or coriolis is not None:
+        no("forcing (Forcing, Relaxation sponges, subsidence, Coriolis) is")
+    if boundary_conditions is not None:
+        w = boundary_conditions.get("w") if isinstance(boundary_conditions, dict) else None
+        if w is not None:
+            no("a NormalFlowBoundaryCondition (or any boundary condition) on w is")
+        no("flux and value boundary conditions are")
+    if velocities is not None:
+        no("PrescribedVelocityFields (velocities as functions of time) is")
+
+
 class Clock:
     def __init__(self):
         self.time, self.iteration, self.last_Δt = 0.0, 0, float("inf")
@@ -218,11 +284,18 @@ class AtmosphereModel:
     def __init__(self, grid, dynamics=None, advection=None, thermodynamic_constants=None,
                  formulation="LiquidIcePotentialTemperature", timestepper="SSPRungeKutta3",
                  closure=None, coriolis=None, microphysics=None, forcing=None, boundary_conditions=None,
-                 tracers=(), device="cuda:0", momentum_advection=None, scalar_advection=None):
+                 tracers=(), device="cuda:0", momentum_advection=None, scalar_advection=None, velocities=None):
         import torch
         if not isinstance(grid, RectilinearGrid):
             raise TypeError("grid must be a RectilinearGrid")
         advection = _merge_advection(advection, momentum_advection, scalar_advection)
+        # dynamics = PrescribedDynamics(reference_state): the kinematic driver (csrc/bz_kinematic.hip)
+        self._kinematic = kin = isinstance(dynamics, PrescribedDynamics)
+        if kin:
+            _check_kinematic_options(type(self), grid, dynamics, advection, formulation, closure, microphysics, forcing, boundary_conditions,
+                                     velocities, coriolis)
+        elif velocities is not None:
+            raise ValueError("`velocities` belongs to AtmosphereModel(dynamics = PrescribedDynamics(...))")
         bounded_x = grid.topology == (Bounded, Flat, Bounded)          # walls in x of a 2-D model: examples/cloudy_thermal_bubble.jl
         flat_y = grid.topology == (Periodic, Flat, Bounded) or bounded_x
         bounded_y = grid.topology == (Periodic, Bounded, Bounded)      # walls in y: the reference benchmark driver's PBB option
@@ -315,7 +388,7 @@ class AtmosphereModel:
             return Field(grid, _LOC[loc], self.device)
 
         # materialize_momentum_and_velocities, formulation, moisture, diagnostics
-        self.momentum = {"ρu": fld("fcc"), "ρv": fld("cfc"), "ρw": fld("ccf")}
+        self.momentum = {} if kin else {"ρu": fld("fcc"), "ρv": fld("cfc"), "ρw": fld("ccf")}      # a kinematic model has no prognostic momentum
         self.velocities = {"u": fld("fcc"), "v": fld("cfc"), "w": fld("ccf")}
         # :StaticEnergy keeps rho_e / e in the thermodynamic slots (energy_density, specific_energy)
         self.potential_temperature_density = fld("ccc")
@@ -324,9 +397,13 @@ class AtmosphereModel:
         self.moisture_density = fld("ccc")
         self.specific_moisture = fld("ccc")
         self.temperature = fld("ccc")
-        dynamics.pressure_anomaly = fld("ccc")
+        dynamics.pressure_anomaly = None if kin else fld("ccc")
+        # the context owns the Fourier-tridiagonal solver of an anelastic model; a kinematic model has none
+        self.pressure_solver = None if kin else "FourierTridiagonalPoissonSolver"
         import weakref
-        for _f in (*self.velocities.values(), self.potential_temperature, self.specific_moisture, self.temperature, dynamics.pressure_anomaly):
+        # (the velocities of a kinematic model are the user's, not diagnostics: reading them never rebuilds anything)
+        for _f in ((self.potential_temperature, self.specific_moisture, self.temperature) if kin else
+                   (*self.velocities.values(), self.potential_temperature, self.specific_moisture, self.temperature, dynamics.pressure_anomaly)):
             _f._owner = weakref.ref(self)
         self.microphysical_fields = {}
         if self._kessler:      # materialize_microphysical_fields(::DCMIP2016KM) (dcmip2016_kessler.jl:255-290)
@@ -365,6 +442,8 @@ class AtmosphereModel:
             raise _lib.BreezeHIPError(f"bz_create failed with code {rc}")
         self._check(lib.bz_set_stream(self._ctx, C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)),
                     "bz_set_stream")
+        if kin:
+            self._check(lib.bz_set_prescribed_dynamics(self._ctx, 1 if dynamics.divergence_correction else 0), "bz_set_prescribed_dynamics")
         if formulation == "StaticEnergy":
             self._check(lib.bz_set_formulation(self._ctx, 1), "bz_set_formulation")
         if self._scalar_order != advection.order:      # momentum_advection and scalar_advection of different orders
@@ -445,16 +524,18 @@ class AtmosphereModel:
         self._state = self._make_state()
         self._U0 = self._make_prog(self.U0)
         self._G = self._make_prog(self.G)
-        # initialize_model_thermodynamics!: θ = θ₀  (anelastic_time_stepping.jl:15-19)
-        set_(self, θ=ref.potential_temperature)
+        # initialize_model_thermodynamics!: θ = θ₀  (anelastic_time_stepping.jl:15-19); nothing for a kinematic model
+        # (kinematic_driver_time_stepping.jl:16)
+        if not kin:
+            set_(self, θ=ref.potential_temperature)
 
     # -- plumbing ------------------------------------------------------------
     def _check(self, rc, what):
         _lib.check(self._lib, self._ctx, rc, what)
 
     def prognostic_fields(self):
-        out = {"ρu": self.momentum["ρu"], "ρv": self.momentum["ρv"], "ρw": self.momentum["ρw"],
-               "ρθ": self.potential_temperature_density, "ρq": self.moisture_density}
+        out = dict(self.momentum)
+        out.update({"ρθ": self.potential_temperature_density, "ρq": self.moisture_density})
         if getattr(self, "_kessler", False):
             out["ρqᶜˡ"], out["ρqʳ"] = self.microphysical_fields["ρqᶜˡ"], self.microphysical_fields["ρqʳ"]
         out.update(getattr(self, "tracers", {}))
@@ -462,17 +543,21 @@ class AtmosphereModel:
 
     def _make_state(self):
         s = _lib.bz_state()
-        s.rho_u, s.rho_v, s.rho_w = (self.momentum[k].ptr() for k in ("ρu", "ρv", "ρw"))
+        if self.momentum:
+            s.rho_u, s.rho_v, s.rho_w = (self.momentum[k].ptr() for k in ("ρu", "ρv", "ρw"))
         s.rho_theta, s.rho_q = self.potential_temperature_density.ptr(), self.moisture_density.ptr()
         s.u, s.v, s.w = (self.velocities[k].ptr() for k in ("u", "v", "w"))
         s.theta, s.q, s.T = self.potential_temperature.ptr(), self.specific_moisture.ptr(), self.temperature.ptr()
-        s.phi = self.dynamics.pressure_anomaly.ptr()
+        if self.dynamics.pressure_anomaly is not None:
+            s.phi = self.dynamics.pressure_anomaly.ptr()
         return s
 
     @staticmethod
     def _make_prog(d):
         p = _lib.bz_prognostic()
-        p.rho_u, p.rho_v, p.rho_w, p.rho_theta, p.rho_q = (d[k].ptr() for k in ("ρu", "ρv", "ρw", "ρθ", "ρq"))
+        if "ρu" in d:
+            p.rho_u, p.rho_v, p.rho_w = (d[k].ptr() for k in ("ρu", "ρv", "ρw"))
+        p.rho_theta, p.rho_q = d["ρθ"].ptr(), d["ρq"].ptr()
         return p
 
     def __del__(self):
@@ -542,6 +627,8 @@ class AtmosphereModel:
     # -- profiling -----------------------------------------------------------
     def graph_enable(self, on=True):
         """hipGraph replay of whole steps (csrc/bz_graph.hip); opt-in, bit-identical to launched steps."""
+        if self._kinematic and on:
+            raise NotImplementedError("AtmosphereModel(dynamics = PrescribedDynamics(...)): hipGraph replay is not implemented")
         self._check(self._lib.bz_graph_enable(self._ctx, 1 if on else 0), "bz_graph_enable")
 
     def graph_info(self):
@@ -567,6 +654,8 @@ class AtmosphereModel:
         return out
 
     def max_abs_divergence(self):
+        if self._kinematic:
+            raise ValueError("a kinematic model has no momentum")
         out = self._T.real()
         self._check(self._lib.bz_max_abs_divergence(self._ctx, C.byref(self._state), C.byref(out)),
                     "bz_max_abs_divergence")
@@ -650,6 +739,8 @@ def enforce_mass_conservation_(model):
 def set_(model, enforce_mass_conservation=True, **kw):
     """set!(model; kw...): θ / ρθ, u v w / ρu ρv ρw, qᵗ / ρqᵗ from numbers, arrays or f(x, y, z)."""
     import torch
+    if getattr(model, "_kinematic", False):
+        return _set_kinematic(model, **kw)
     g = model.grid
     ref = model.dynamics.reference_state
     Hz, Nz = g.Hz, g.Nz
@@ -752,10 +843,81 @@ def set_(model, enforce_mass_conservation=True, **kw):
         enforce_mass_conservation_(model)
 
 
+def _set_kinematic(model, **kw):
+    """set!(model; kw...) of a kinematic model: θ / ρθ, qᵗ / ρqᵗ, the tracers by name (their density fields, set_atmosphere_model.jl:236-238)
+    and the velocities u, v, w (kinematic_driver_time_stepping.jl:28-42).  Momentum cannot be set; nothing is projected."""
+    import torch
+    g = model.grid
+    ref = model.dynamics.reference_state
+    Hz, Nz = g.Hz, g.Nz
+    ρc = torch.from_numpy(ref.density[Hz:Hz + Nz].copy()).to(model.device)[:, None, None]
+    velocities_set = False
+    for name, value in sorted(kw.items(), key=lambda kv: 0 if _ALIASES.get(kv[0]) in ("q", "ρq") else 1):
+        tracer = str(name).lstrip(":")
+        if tracer in model.tracers or (tracer.startswith("ρ") and tracer[1:] in model.tracers):
+            model.tracers[tracer if tracer in model.tracers else tracer[1:]].set_interior(value)
+            continue
+        key = _ALIASES.get(name)
+        if key in ("ρu", "ρv", "ρw"):
+            raise ValueError(f"Cannot set momentum component '{name}' of a KinematicModel.")
+        if key in ("u", "v", "w"):
+            model.velocities[key].set_interior(value)
+            velocities_set = True
+        elif key == "θ":
+            model.potential_temperature.set_interior(value)
+            model.potential_temperature_density.interior.copy_(ρc * model.potential_temperature.interior)
+        elif key == "ρθ":
+            model.potential_temperature_density.set_interior(value)
+        elif key == "q":
+            model.specific_moisture.set_interior(value)
+            model.moisture_density.interior.copy_(ρc * model.specific_moisture.interior)
+        elif key == "ρq":
+            model.moisture_density.set_interior(value)
+        elif key in ("T", "ℋ", "e", "ρe", "qcl", "qr"):
+            raise NotImplementedError(f"set!(model; {name}) is not implemented for AtmosphereModel(dynamics = PrescribedDynamics(...))")
+        else:
+            raise ValueError(f"Cannot set! {name} in AtmosphereModel because {name} is neither a prognostic "
+                             "variable, a settable thermodynamic variable, nor a settable diagnostic variable!")
+    if velocities_set:
+        # default boundary conditions: the faces k = 1 and k = Nz + 1 of w are impenetrable — zeros, as the halo fill of a wall-normal face
+        # field leaves them; u, v, w get their periodic images.  Then the library is told that the velocities changed (∇·(ρU) is re-formed)
+        w = model.velocities["w"].parent
+        w[Hz].zero_()
+        w[Hz + Nz].zero_()
+        fill_halo_regions_(model, model.velocities["u"], kind=2 | 8)
+        fill_halo_regions_(model, model.velocities["v"], kind=2 | 4)
+        fill_halo_regions_(model, model.velocities["w"], kind=1)
+        model._check(model._lib.bz_set_prescribed_dynamics(model._ctx, 1 if model.dynamics.divergence_correction else 0),
+                     "bz_set_prescribed_dynamics")
+    update_state_(model, compute_tendencies=False)
+
+
+def compute_kinematic_tendencies_(model):
+    """Gⁿ of every scalar of a kinematic model, G = −∇·(ρU c) [+ c ∇·(ρU)], from the fields of the last update_state!."""
+    model._check(model._lib.bz_compute_kinematic_tendencies(model._ctx, C.byref(model._state), C.byref(model._G)),
+                 "bz_compute_kinematic_tendencies")
+
+
+def _kinematic_time_steps(model, Δt, n, diagnose_last=True):
+    """n × time_step!(model, Δt) of a kinematic model (ssp_runge_kutta_3.jl:209-278 with the projection calls doing nothing)."""
+    n = int(n)
+    if n <= 0:
+        return
+    if model.clock.iteration == 0:       # maybe_prepare_first_time_step!
+        update_state_(model, compute_tendencies=False)      # (the stage kernel evaluates the tendencies itself)
+    model._check(model._lib.bz_time_steps_kinematic(model._ctx, C.byref(model._state), C.byref(model._U0), C.byref(model._G),
+                                                    float(Δt), n, 1 if diagnose_last else 0), "bz_time_steps_kinematic")
+    model.clock.time += n * Δt
+    model.clock.last_Δt = float(Δt)
+    model.clock.iteration += n
+
+
 def time_step_(model, Δt, whole_step=True):
     """time_step!(model, Δt) with SSP-RK3.  whole_step=True uses the single-call device-resident seam
     (bz_time_step_anelastic); False replays the reference's call sequence through the per-operator
     entry points (same kernels, used by the parity tests)."""
+    if getattr(model, "_kinematic", False):
+        return _kinematic_time_steps(model, Δt, 1)
     if model.clock.iteration == 0:       # maybe_prepare_first_time_step!
         update_state_(model, compute_tendencies=True)
     fv = getattr(model, "filtered_velocities", None)
@@ -784,6 +946,8 @@ def time_step_(model, Δt, whole_step=True):
 
 def many_time_steps_(model, Δt, n, diagnose_last=True):
     """many_time_steps!(model, Δt, n) of the reference's benchmark driver through the multi-step seam."""
+    if getattr(model, "_kinematic", False):
+        return _kinematic_time_steps(model, Δt, n, diagnose_last)
     n = int(n)
     if n <= 0:
         return

@@ -210,6 +210,36 @@ int bz_time_steps_anelastic(bz_ctx *ctx, const bz_state *s, const bz_prognostic 
                             const bz_prognostic *G, double dt, int n, int diagnose_last);
 int bz_diagnostics_stale(const bz_ctx *ctx);
 
+/* ---- Kinematic driver: AtmosphereModel(grid; dynamics = PrescribedDynamics(reference_state; divergence_correction)) ----------------
+ * (src/KinematicDriver/prescribed_dynamics.jl:27-84, kinematic_driver_time_stepping.jl:16-73).  The velocities s->u, s->v, s->w are GIVEN:
+ * ordinary halo-filled fields the host writes (periodic images in x, y; w as stored on the wall faces k = 0 and k = Nz — the host keeps
+ * zeros there for impenetrable walls), never written by the library.  Density and pressure are the reference state's; there is no
+ * momentum (s->rho_u, rho_v, rho_w, phi and their U0 / G slots may be NULL) and no pressure solve.  Every scalar c of {theta, moisture,
+ * tracers} advances with
+ *     G = -div_rhoUc(c) [+ c div_rhoU],   div_rhoU = 1/V [dx(Ax Ix(rho) u) + dy(Ay Iy(rho) v) + dz(Az Iz(rho) w)]
+ * (dynamics_kernel_functions.jl:155-156; the second term with divergence_correction != 0: a uniform c then stays uniform in a divergent
+ * flow), all scalars of a Runge-Kutta stage in one launch.
+ * bz_set_prescribed_dynamics marks an anelastic single-device context ((Periodic, Periodic | Flat, Bounded)) kinematic; compressible,
+ * y-slab and walled contexts return BZ_ERR_UNSUPPORTED.  EVERY call also declares that the velocity fields may have changed (the
+ * host's set path calls it again): the library re-forms div_rhoU before its next use.
+ * On a kinematic context bz_update_state skips the velocity computation (update_state! with compute_velocities! = nothing) and, with
+ * compute_tendencies != 0, ends with bz_compute_kinematic_tendencies; the momentum / projection entry points (bz_time_step(s)_anelastic,
+ * bz_compute_tendencies, bz_compute_velocities, bz_ssp_rk3_substep, bz_store_initial_state, bz_compute_pressure_correction,
+ * bz_make_pressure_correction, bz_tendencies_fused_rk, bz_ssp_rk3_substep_fused, bz_max_abs_divergence) return BZ_ERR_UNSUPPORTED with
+ * bz_last_error set, and so do the two entry points below on a context that is not kinematic.
+ * Implemented: WENO(order = 5), the potential-temperature formulation, microphysics nothing or warm-phase saturation adjustment, user
+ * tracers; anything else attached to the context (closure, forcings, sponges, bulk fluxes, bounds-preserving advection, Kessler, graph
+ * replay) makes the two entry points return BZ_ERR_UNSUPPORTED naming it. */
+int bz_set_prescribed_dynamics(bz_ctx *ctx, int divergence_correction);
+/* G->rho_theta, G->rho_q and the tracers' G arrays from the stored specific fields (stale diagnostics are rebuilt first). */
+int bz_compute_kinematic_tendencies(bz_ctx *ctx, const bz_state *s, const bz_prognostic *G);
+/* n x time_step!(model, dt): per stage the substep of every rho c (stage 1 also stores U0), then update_state!.  The caller has run
+ * bz_update_state once after the last set!.  diagnose_last as in bz_time_steps_anelastic: with 0 the update_state! after the very last
+ * stage is skipped, the prognostic scalars are current, theta / q / T / the specific tracers are stale (bz_diagnostics_stale) until
+ * bz_update_state(ctx, s, G, 0) — which a following call of this function runs by itself.  The G arrays are not written. */
+int bz_time_steps_kinematic(bz_ctx *ctx, const bz_state *s, const bz_prognostic *U0, const bz_prognostic *G, double dt, int n,
+                            int diagnose_last);
+
 /* ---- y-slab decomposition: one process per GPU --------------------------------------------------
  * The reference re-exports Oceananigans' Distributed architecture (src/Breeze.jl:172,183,209) and has no
  * distributed code of its own; these entry points are the rank-local kernels of this repo's decomposition.
