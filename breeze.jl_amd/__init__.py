@@ -33,4 +33,5 @@ from . import diagnostics  # noqa: F401,E402
 from .diagnostics import (Average, DewpointTemperature, EquivalentPotentialTemperature, LiquidIcePotentialTemperature,  # noqa: F401,E402
                           PotentialTemperature, RelativeHumidity, SaturationSpecificHumidity, StabilityEquivalentPotentialTemperature,
                           StaticEnergy, VirtualPotentialTemperature, compute_diagnostics, horizontal_average)
+from .diagnostics import at, compute_averages, partial_z  # noqa: F401,E402
 from .diagnostics import AzimuthalMean, RadialVelocity, TangentialVelocity, azimuthal_mean  # noqa: F401,E402

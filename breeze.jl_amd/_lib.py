@@ -195,6 +195,19 @@ BZ_DIAG_DENSITY_WEIGHTED = 0x100
 BZ_MAX_DIAGNOSTICS = 24
 
 
+# bz_horizontal_moments of include/breeze_hip.h
+BZ_MAX_MOMENT_FIELDS, BZ_MAX_MOMENTS, BZ_MAX_MOMENT_FACTORS = 8, 24, 3
+
+
+class bz_moment_field(C.Structure):
+    _fields_ = [("data", C.c_void_p), ("face_x", C.c_int32), ("face_y", C.c_int32), ("face_z", C.c_int32)]
+
+
+class bz_moment(C.Structure):
+    _fields_ = [("n_factors", C.c_int32), ("field", C.c_int32 * BZ_MAX_MOMENT_FACTORS), ("power", C.c_int32 * BZ_MAX_MOMENT_FACTORS),
+                ("dz", C.c_int32), ("at_center", C.c_int32)]
+
+
 class bz_exner_reference_state(C.Structure):
     _fields_ = [("standard_pressure", C.c_double), ("pressure", _dp), ("density", _dp)]
 
@@ -305,6 +318,8 @@ SYMBOLS = {
     "bz_compute_diagnostics": (C.c_int, [_ctx, _sp, C.POINTER(bz_diagnostic_inputs), C.c_int32, C.POINTER(C.c_int32),
                                          C.POINTER(C.c_void_p)]),
     "bz_horizontal_average": (C.c_int, [_ctx, C.c_void_p, C.c_int, _dp]),
+    "bz_horizontal_moments": (C.c_int, [_ctx, C.c_int32, C.POINTER(bz_moment_field), C.c_int32, C.POINTER(bz_moment), _dp,
+                                        C.POINTER(C.c_int32)]),
     "bz_set_horizontal_nodes": (C.c_int, [_ctx, _dp, _dp]),
     "bz_azimuthal_mean": (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_int32, _dp,
                                     C.POINTER(C.c_int64)]),

@@ -405,6 +405,7 @@ extern "C" void bz_destroy(bz_ctx *ctx)
     bzi_closure_teardown(ctx);
     bzi_diagnostics_teardown(ctx);
     bzi_azimuthal_teardown(ctx);
+    bzi_moments_teardown(ctx);
     bzi_kinematic_teardown(ctx);
     if (ctx->d_scalar) hipFree(ctx->d_scalar);
     if (ctx->d_gflux) hipFree(ctx->d_gflux);

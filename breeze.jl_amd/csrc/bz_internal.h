@@ -419,6 +419,7 @@ struct bz_ctx {
     double *d_lower = nullptr;        // Nz
     double *d_scalar = nullptr;       // small scratch (mean, reductions)
     double *d_havg = nullptr;         // bz_horizontal_average: partial sums per (level, slice) and the profile, allocated by the first call (bz_diagnostics.hip)
+    double *d_moments = nullptr;      // bz_horizontal_moments: partial sums per (moment, level, slice) and the profiles, allocated by the first call (bz_moments.hip)
     struct AzPlan *az = nullptr;      // bz_azimuthal_mean / bz_polar_winds: x^c, y^c on the device, the cached ring plan and scratch (bz_azimuthal.hip)
     // y-slab decomposition (bz_create_slab): this rank owns Ny rows of Ny*y_nranks and the kx block
     // [kx0, kx0+nkx) of the zero-padded half spectrum; the horizontal transforms are done by the caller.
@@ -606,6 +607,7 @@ int bzi_surface_layer_stage(bz_ctx *ctx, const bz_state *s, int stage, double dt
 void bzi_forcing_teardown(bz_ctx *ctx);
 void bzi_diagnostics_teardown(bz_ctx *ctx);
 void bzi_azimuthal_teardown(bz_ctx *ctx);
+void bzi_moments_teardown(bz_ctx *ctx);
 int bzi_tracer_specific(bz_ctx *ctx);
 int bzi_tracer_rk3(bz_ctx *ctx, double dt, double alpha, bool first);
 int bzi_tracer_store_initial_state(bz_ctx *ctx);

@@ -6,6 +6,11 @@ microphysics_diagnostics.jl) — behind bz_compute_diagnostics / bz_horizontal_a
     θᵛ, θᵉ = compute_diagnostics(model, [VirtualPotentialTemperature(model), EquivalentPotentialTemperature(model)])   # one launch
     profile = Average(RelativeHumidity(model), dims=(1, 2)).compute()      # numpy, Nz values
 
+    u, v, w = model.velocities.values(); θ = model.potential_temperature; CCC = (Center, Center, Center)
+    profiles = compute_averages(model, {"uw": Average(at(CCC, u * w)), "w³": Average(at(CCC, w ** 3)), "θw": Average(θ * w),
+                                        "u²w": Average(at(CCC, u ** 2 * w)), "∂z_u": Average(at(CCC, partial_z(u)))})
+                                                                # one fused bz_horizontal_moments call: every field is read once
+
     vθ = TangentialVelocity(model, center=(0, 0)).compute()     # (−y uᶜ + x vᶜ)/r at cell centres
     v̄θ = azimuthal_mean(vθ, radius=150e3, Nr=30)               # .data (Nr, Nz), .counts, .r, .z
     θ̄ = azimuthal_mean(LiquidIcePotentialTemperature(model), radius=150e3, Nr=30)      # same geometry: the ring plan is reused
@@ -19,7 +24,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .grids import Center
+from .grids import Center, Face
 from .model import Field, fill_halo_regions_
 
 _SPECIFIC_OR_DENSITY = ("specific", "density")
@@ -32,8 +37,24 @@ def _flavor(flavor, valid):
     return flavor
 
 
-class _Operation:
+class _Arithmetic:
+    """`a * b`, `a ** p` on fields, pointwise operations and expressions: each returns a small expression object for Average(...)."""
+
+    def __mul__(self, other):
+        return _Product(self, other)
+
+    def __pow__(self, p):
+        return _Power(self, p)
+
+    def __add__(self, other):
+        return _Sum(self, other)
+
+    __sub__ = __radd__ = __rsub__ = __add__
+
+
+class _Operation(_Arithmetic):
     """A KernelFunctionOperation at (Center, Center, Center) of one model."""
+    loc = (Center, Center, Center)
     kind = None
     needs_saturation_pressure = False
     uses_model_pressure = False      # the potential temperatures: dynamics_pressure_for_potential_temperature
@@ -210,23 +231,284 @@ def horizontal_average(model, field):
     return prof
 
 
+# ---- Average of products, powers and ∂z (csrc/bz_moments.hip: bz_horizontal_moments) ----------------------------------------------------
+# Oceananigans' BinaryOperation, ^, ∂z and @at as the reference's examples use them in their profile lists
+# (examples/neutral_atmospheric_boundary_layer.jl:203-221): trees of small objects that Average lowers onto one bz_moment descriptor
+class _Expression(_Arithmetic):
+    def shape(self):
+        raise NotImplementedError
+
+    def __repr__(self):
+        return self.shape()
+
+
+def _shape(x):
+    if isinstance(x, _Expression):
+        return x.shape()
+    if isinstance(x, _Operation):
+        return type(x).__name__
+    if isinstance(x, Field):
+        return "field"
+    return type(x).__name__
+
+
+class _Product(_Expression):
+    def __init__(self, a, b):
+        self.a, self.b = a, b
+
+    def shape(self):
+        right = _shape(self.b)
+        return f"{_shape(self.a)} * " + (f"({right})" if isinstance(self.b, (_Product, _Sum)) else right)
+
+
+class _Power(_Expression):
+    def __init__(self, a, p):
+        self.a, self.p = a, p
+
+    def shape(self):
+        base = _shape(self.a)
+        return (f"({base})" if isinstance(self.a, _Expression) else base) + f" ** {self.p}"
+
+
+class _Sum(_Expression):
+    def __init__(self, a, b):
+        self.a, self.b = a, b
+
+    def shape(self):
+        return f"{_shape(self.a)} + {_shape(self.b)}"
+
+
+class _Dz(_Expression):
+    def __init__(self, a):
+        self.a = a
+
+    def shape(self):
+        return f"∂z({_shape(self.a)})"
+
+
+class _At(_Expression):
+    def __init__(self, loc, a):
+        self.loc, self.a = tuple(loc), a
+
+    def shape(self):
+        return f"at(({', '.join(getattr(l, '__name__', repr(l)) for l in self.loc)}), {_shape(self.a)})"
+
+
+def partial_z(f):
+    """∂z(f) of one field or pointwise operation: (f[k] − f[k−1]) / Δzᵃᵃᶠ[k] at the z location opposite to f's."""
+    return _Dz(f)
+
+
+def at(loc, expr):
+    """@at(loc, expr): the expression interpolated to `loc`; (Center, Center, Center) is implemented."""
+    return _At(loc, expr)
+
+
+def _is_leaf(x):
+    return isinstance(x, (Field, _Operation))
+
+
+class Moment:
+    """One bz_moment before its fields are numbered: `factors` [(leaf, power), ...], `dz`, `at_center`."""
+
+    def __init__(self, factors, dz=False, at_center=False):
+        self.factors, self.dz, self.at_center = factors, bool(dz), bool(at_center)
+
+    @property
+    def leaves(self):
+        return [f for f, _ in self.factors]
+
+    def needs_halos(self):
+        """True if any neighbour of a point is read: ∂z, @at of a face location, or factors at different locations."""
+        first = self.factors[0][0].loc
+        return self.dz or (self.at_center and any(l is Face for l in first)) or any(tuple(f.loc) != tuple(first) for f in self.leaves)
+
+    def descriptor(self, index):
+        """The bz_moment with fields numbered by `index` (id(leaf) -> position in fields[])."""
+        M = _lib.bz_moment()
+        M.n_factors = len(self.factors)
+        for q, (f, p) in enumerate(self.factors):
+            M.field[q], M.power[q] = index[id(f)], p
+        M.dz, M.at_center = int(self.dz), int(self.at_center)
+        return M
+
+    def key(self):
+        """(((face_x, face_y, face_z), power), ...), dz, at_center: what the descriptor says, without pointers"""
+        return (tuple((tuple(int(l is Face) for l in f.loc), p) for f, p in self.factors), self.dz, self.at_center)
+
+
+def lower(expr):
+    """The Moment of an accepted expression: a left-associated product of up to three leaves, each optionally raised to a power 1..3, or a
+    single ∂z(leaf), optionally under at((Center, Center, Center), ·).  Anything else raises NotImplementedError naming the shape."""
+    def refuse(why):
+        raise NotImplementedError(f"Average: {why}: {_shape(expr)} (implemented: leaf ** p * leaf ** p * leaf ** p multiplied left to right "
+                                  f"with powers 1..3, or ∂z(leaf), optionally under at((Center, Center, Center), ...))")
+
+    at_center = False
+    body = expr
+    if isinstance(body, _At):
+        if body.loc != (Center, Center, Center):
+            refuse("at(loc, ...) is implemented for (Center, Center, Center)")
+        at_center, body = True, body.a
+
+    def factor(x):
+        if _is_leaf(x):
+            return (x, 1)
+        if isinstance(x, _Power) and _is_leaf(x.a):
+            if not isinstance(x.p, (int, np.integer)) or isinstance(x.p, bool) or not 1 <= x.p <= 3:
+                refuse("a power must be an integer 1..3")
+            return (x.a, int(x.p))
+        if isinstance(x, _Power):
+            refuse("a power of an expression is not implemented")
+        if isinstance(x, _Product):
+            refuse("a product is multiplied left to right, (a * b) * c; a product as the right factor is not implemented")
+        if isinstance(x, _Sum):
+            refuse("sums are not implemented")
+        if isinstance(x, _Dz):
+            refuse("∂z inside a product is not implemented")
+        if isinstance(x, _At):
+            refuse("at(...) is implemented as the outermost operation")
+        refuse(f"{type(x).__name__} is not a field or a diagnostic operation")
+
+    if isinstance(body, _Dz):
+        if not _is_leaf(body.a):
+            refuse("∂z takes one field or diagnostic operation")
+        return Moment([(body.a, 1)], dz=True, at_center=at_center)
+    factors = []
+    while isinstance(body, _Product):
+        factors.insert(0, factor(body.b))
+        body = body.a
+    factors.insert(0, factor(body))
+    if len(factors) > _lib.BZ_MAX_MOMENT_FACTORS:
+        refuse(f"at most {_lib.BZ_MAX_MOMENT_FACTORS} factors")
+    return Moment(factors, at_center=at_center)
+
+
+def _dims(dims, model):
+    """dims = (1, 2); dims = 1 on a Flat y, where it is the same average (the reference's x-z examples)"""
+    d = (dims,) if isinstance(dims, (int, np.integer)) else tuple(dims)
+    if d == (1, 2):
+        return d
+    topology = getattr(getattr(model, "grid", None), "topology", None)
+    if d == (1,) and topology is not None and topology[1] == "Flat":
+        return d
+    raise NotImplementedError("Average: dims = (1, 2) is implemented, and dims = 1 on a Flat y")
+
+
+def _refuse_slab(model, what):
+    if _is_slab(model):
+        raise NotImplementedError(f"{what}: not implemented on y-slab models (the average needs an all-reduce over the ranks)")
+
+
 class Average:
-    """Average(field_or_operation, dims=(1, 2)): the horizontal mean per level.  `model` is needed for a bare Field."""
+    """Average(field_or_operation_or_expression, dims=(1, 2)): the horizontal mean per level.  `model` is needed if no leaf knows it."""
 
     def __init__(self, operand, dims=(1, 2), model=None):
-        if tuple(dims) != (1, 2):
-            raise NotImplementedError("Average: dims = (1, 2) is implemented")
-        self.operand, self.dims = operand, (1, 2)
-        self.model = operand.model if isinstance(operand, _Operation) else model
-        if self.model is None:
-            owner = getattr(operand, "_owner", None)
-            self.model = owner() if owner is not None else None
-        if self.model is None:
+        self.operand = operand
+        self.moment = lower(operand) if isinstance(operand, _Expression) else None
+        if model is None:
+            for leaf in (self.moment.leaves if self.moment else [operand]):
+                model = leaf.model if isinstance(leaf, _Operation) else None
+                if model is None:
+                    owner = getattr(leaf, "_owner", None)
+                    model = owner() if owner is not None else None
+                if model is not None:
+                    break
+        if model is None:
             raise ValueError("Average(field): pass model=... for a field that does not know its model")
+        self.model = model
+        self.dims = _dims(dims, model)
 
     def compute(self):
+        if self.moment is not None:
+            return compute_averages(self.model, {"": self})[""]
         field = self.operand.compute() if isinstance(self.operand, _Operation) else self.operand
         return horizontal_average(self.model, field)
+
+
+def _maintained_fields(model):
+    """ids of the Fields the model itself holds (state, diagnostics, dynamics, microphysics, tracers): update_state! keeps their halos"""
+    found = set()
+    for holder in (model, getattr(model, "dynamics", None)):
+        for value in vars(holder).values() if holder is not None else ():
+            for f in (value.values() if isinstance(value, dict) else (value,)):
+                if isinstance(f, Field):
+                    found.add(id(f))
+    return found
+
+
+def _plan_calls(moments, max_fields=None, max_moments=None):
+    """Greedy packing of moments (in order) into calls of at most max_moments moments over at most max_fields distinct leaves: a list of
+    (leaves, [positions])."""
+    max_fields = _lib.BZ_MAX_MOMENT_FIELDS if max_fields is None else max_fields
+    max_moments = _lib.BZ_MAX_MOMENTS if max_moments is None else max_moments
+    calls = []
+    for pos, M in enumerate(moments):
+        ids = {id(f): f for f in M.leaves}
+        for leaves, members in calls:
+            new = [f for i, f in ids.items() if i not in {id(x) for x in leaves}]
+            if len(members) < max_moments and len(leaves) + len(new) <= max_fields:
+                leaves.extend(new)
+                members.append(pos)
+                break
+        else:
+            calls.append((list(ids.values()), [pos]))
+    return calls
+
+
+def compute_averages(model, averages):
+    """Evaluate {name: Average(...)} of one model in as few fused bz_horizontal_moments calls as its limits allow (every distinct field of
+    a call is read once); returns {name: numpy profile}.  Pointwise operations among the leaves are computed first, in one
+    compute_diagnostics launch; halos of leaves the model does not maintain are filled where a moment reads neighbours."""
+    _refuse_slab(model, "compute_averages")
+    names = list(averages)
+    moments = []
+    for name in names:
+        A = averages[name]
+        if not isinstance(A, Average):
+            raise TypeError(f"{name!r}: {A!r} is not an Average")
+        if A.model is not model:
+            raise ValueError("every Average must belong to `model`")
+        M = A.moment
+        moments.append(Moment(list(M.factors), M.dz, M.at_center) if M is not None else Moment([(A.operand, 1)]))
+    if not moments:
+        return {}
+    # pointwise operations -> centre fields, one launch for all of them
+    ops = {}
+    for M in moments:
+        for f in M.leaves:
+            if isinstance(f, _Operation):
+                ops.setdefault(id(f), f)
+    done = dict(zip(ops, compute_diagnostics(model, list(ops.values())))) if ops else {}
+    for M in moments:
+        M.factors = [(done.get(id(f), f), p) for f, p in M.factors]
+    filled = {id(f) for f in done.values()} | _maintained_fields(model)
+    real = model.temperature.dtype
+    for M in moments:
+        for f in M.leaves:
+            if not isinstance(f, Field) or f.grid is not model.grid or f.dtype != real:
+                raise ValueError("Average: every leaf must be a Field of the model's grid and float type")
+            if hasattr(f, "_fresh"):
+                f._fresh()      # a stale diagnostic field of the model is rebuilt first
+            if M.needs_halos() and id(f) not in filled:
+                fill_halo_regions_(model, f)      # not one of the fields the model maintains: its halos may be anything
+                filled.add(id(f))
+    T, Nz = model._T, model.grid.Nz
+    out = {}
+    for leaves, members in _plan_calls(moments):
+        index = {id(f): n for n, f in enumerate(leaves)}
+        fields = (_lib.bz_moment_field * len(leaves))()
+        for n, f in enumerate(leaves):
+            fields[n].data = f.ptr()
+            fields[n].face_x, fields[n].face_y, fields[n].face_z = (int(l is Face) for l in f.loc)
+        descs = (_lib.bz_moment * len(members))(*[moments[pos].descriptor(index) for pos in members])
+        prof = np.zeros((len(members), Nz + 1), dtype=T.np_real)
+        nlev = (C.c_int32 * len(members))()
+        model._check(model._lib.bz_horizontal_moments(model._ctx, len(leaves), fields, len(members), descs,
+                                                      prof.ctypes.data_as(C.POINTER(T.real)), nlev), "bz_horizontal_moments")
+        for row, pos in enumerate(members):
+            out[names[pos]] = prof[row, :nlev[row]].copy()
+    return {name: out[name] for name in names}
 
 
 # ---- azimuthal means and polar winds (csrc/bz_azimuthal.hip; src/AtmosphereModels/Diagnostics/azimuthal_mean.jl) ---------------------

@@ -225,6 +225,21 @@ class Field:
     def ptr(self):
         return self.parent.data_ptr()
 
+    # u * w, w ** 3, ... are expressions for Average(...) (diagnostics.py); nothing is evaluated here
+    def __mul__(self, other):
+        from .diagnostics import _Product
+        return _Product(self, other)
+
+    def __pow__(self, p):
+        from .diagnostics import _Power
+        return _Power(self, p)
+
+    def __add__(self, other):
+        from .diagnostics import _Sum
+        return _Sum(self, other)
+
+    __sub__ = __radd__ = __rsub__ = __add__
+
     def set_interior(self, value):
         import torch
         g = self.grid

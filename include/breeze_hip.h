@@ -819,6 +819,50 @@ int bz_compute_diagnostics(bz_ctx *ctx, const bz_state *s, const bz_diagnostic_i
  * bz_create_compressible_slab) return BZ_ERR_UNSUPPORTED. */
 int bz_horizontal_average(bz_ctx *ctx, const double *field, int z_face, double *profile);
 
+/* ---- turbulence statistics: Average(expression, dims = (1, 2)) of products, powers and vertical derivatives (csrc/bz_moments.hip) ----
+ * The profiles the reference's LES examples average every step inside an AveragedTimeInterval window
+ * (examples/neutral_atmospheric_boundary_layer.jl:203-221: u^2, u*w, θ*w, u^2*w, w^3, νₑ^3, ∂z(u), ... under @at((Center, Center, Center), ·);
+ * rico.jl:281-282; tropical_cyclone_world.jl:244-249), all of one list from ONE pass over the fields they are functions of.
+ * The semantics are those of Oceananigans' BinaryOperation, ^, ∂z and @at as the example's comments describe them.  Oceananigans is not
+ * vendored with the reference, so this is a READING of it, not a checked parity:
+ *   location   The location L of a moment is that of its first factor; with `dz` its z location is flipped.  On a Flat y there is no y
+ *              location (face_y is ignored) and no y interpolation.
+ *   value      At a point of L:  f0^p0 · ℑ_L(f1^p1) · ℑ_L(f2^p2), multiplied left to right.  A power is repeated multiplication and is
+ *              applied BEFORE the interpolation, as in a * (b^p).  ℑ_L is the two-point mean (a + b) / 2 in every direction in which
+ *              the factor's location differs from L, composed with x outermost and z innermost: centre -> face at index i uses the
+ *              centres i - 1 and i, face -> centre at i the faces i and i + 1.
+ *   dz         ∂z of the single factor (n_factors == 1, power == 1): centre -> face k is (f[k] - f[k-1]) / Δzᵃᵃᶠ[k], face -> centre k is
+ *              (f[k+1] - f[k]) / Δzᵃᵃᶜ[k], with the grid's own spacings (true divisions).
+ *   at_center  The field of values at L is interpolated to (Center, Center, Center) with the same ℑ rules before it is averaged.
+ *   profile    profiles[m (Nz + 1) + k], k < nlev[m]: the sum over the Nx × Ny interior points of level k divided by Nx Ny, in the
+ *              context's float type.  nlev[m] = Nz + 1 if L is a z face and at_center == 0, else Nz; the remaining entries of a row are 0.
+ * Halo reads: at most ONE halo cell in each direction, corners included (the ℑxy of u*v; the z halo under the bottom and above the top
+ * face for θ*w and ∂z).  The caller provides filled halos; cells further out are never read.  Contexts need Hx, Hy (unless Flat), Hz >= 1.
+ * Deterministic: fixed summation order (that of bz_horizontal_average: a plain field gives the same bits as that call), no floating-point
+ * atomics; the bits of a moment's profile depend neither on the other moments of the call nor on their order.  Runs on the context's
+ * stream, makes one device -> host copy and synchronises once.  The kernel knows no model: anelastic, compressible, Flat-y and Float32
+ * contexts alike.  The caller rebuilds stale diagnostics first if a field is one of them (bz_diagnostics_stale).
+ * BZ_ERR_UNSUPPORTED: y-slab contexts; on contexts with walls in x or y any moment with a field or L at a horizontal face (moments of
+ * horizontally centred fields run: nothing there is wall-specific).  BZ_ERR_INVALID: counts outside the limits below, a null array, a face
+ * flag other than 0 / 1, a field index out of range, a power outside 1 .. 3, dz with more than one factor or a power.  bz_last_error names
+ * the argument; nothing is launched. */
+#define BZ_MAX_MOMENT_FIELDS 8
+#define BZ_MAX_MOMENTS 24
+#define BZ_MAX_MOMENT_FACTORS 3
+typedef struct bz_moment_field {
+    const double *data;      /* DEVICE parent array */
+    int32_t face_x, face_y, face_z;      /* 0: Center, 1: Face */
+} bz_moment_field;
+typedef struct bz_moment {
+    int32_t n_factors;                          /* 1 .. 3 */
+    int32_t field[BZ_MAX_MOMENT_FACTORS];       /* index into fields[] */
+    int32_t power[BZ_MAX_MOMENT_FACTORS];       /* 1 .. 3 */
+    int32_t dz;                                 /* 1: ∂z of the single factor */
+    int32_t at_center;                          /* 1: interpolate the result to (Center, Center, Center) before averaging */
+} bz_moment;
+int bz_horizontal_moments(bz_ctx *ctx, int32_t n_fields, const bz_moment_field *fields, int32_t n_moments, const bz_moment *moments,
+                          double *profiles /* HOST, n_moments rows of Nz + 1 */, int32_t *nlev /* HOST, n_moments */);
+
 /* ---- azimuthal means and polar winds (csrc/bz_azimuthal.hip; src/AtmosphereModels/Diagnostics/azimuthal_mean.jl of the reference) ---- */
 /* The cell-centre coordinates of the grid, x^c[0 .. Nx) and y^c[0 .. Ny) (HOST arrays, copied; xnodes / ynodes of the caller's grid at
  * Center).  bz_grid carries spacings only, and the ring membership of a sample must be formed from the very coordinates the caller's grid

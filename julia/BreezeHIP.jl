@@ -595,6 +595,33 @@ function horizontal_average!(profile::Vector{Float64}, ctx, field::Ptr{Cvoid}, z
     return profile
 end
 
+# ---- turbulence statistics: Average(expression, dims = (1, 2)) of products, powers and ∂z (bz_horizontal_moments) ----
+const BZ_MAX_MOMENT_FIELDS, BZ_MAX_MOMENTS, BZ_MAX_MOMENT_FACTORS = 8, 24, 3
+"A field of a moment list: the device parent array and its location (0: Center, 1: Face)."
+struct BzMomentField
+    data::Ptr{Cvoid}
+    face_x::Int32; face_y::Int32; face_z::Int32
+end
+"One moment: f[field[1]]^power[1] * ℑ(f[field[2]]^power[2]) * ℑ(f[field[3]]^power[3]) (0-based field indices), or ∂z of the single factor; at_center: @at((Center, Center, Center), ·)."
+struct BzMoment
+    n_factors::Int32
+    field::NTuple{3, Int32}
+    power::NTuple{3, Int32}
+    dz::Int32
+    at_center::Int32
+end
+
+"""
+horizontal_moments!(profiles, nlev, ctx, fields, moments): every profile of the list from one pass over the fields;
+`profiles` is (Nz + 1) × length(moments) (a column per moment, nlev[m] valid levels), host memory.
+"""
+function horizontal_moments!(profiles::Matrix{Float64}, nlev::Vector{Int32}, ctx, fields::Vector{BzMomentField}, moments::Vector{BzMoment})
+    check(ccall((:bz_horizontal_moments, libbreeze_hip), Cint,
+                (Ptr{Cvoid}, Int32, Ptr{BzMomentField}, Int32, Ptr{BzMoment}, Ptr{Cdouble}, Ptr{Int32}),
+                ctx, length(fields), fields, length(moments), moments, profiles, nlev), "bz_horizontal_moments", ctx)
+    return profiles
+end
+
 "Hand the grid's own cell-centre coordinates (xnodes / ynodes at Center, host vectors) to the context: needed once before azimuthal_mean / polar_winds!."
 function set_horizontal_nodes!(ctx, xc::Vector{Float64}, yc::Vector{Float64})
     check(ccall((:bz_set_horizontal_nodes, libbreeze_hip), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}), ctx, xc, yc),
