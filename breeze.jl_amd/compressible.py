@@ -301,8 +301,10 @@ class CompressibleAtmosphereModel:
         if not isinstance(grid, RectilinearGrid):
             raise TypeError("grid must be a RectilinearGrid")
         # (Periodic, Flat, Bounded): the 2-D x-z cases of examples/acoustic_wave.jl:51 and inertia_gravity_wave.jl:70
-        # a Bounded x and / or y (3-D): the acoustic substep loop with its lateral boundaries (refresh_linearization_, acoustic_rk3_substep_loop_);
-        # set / time_step / update_state_ of such a model are not built (the library returns BZ_ERR_UNSUPPORTED)
+        # a Bounded x and / or y (3-D): the acoustic substep loop with its lateral boundaries (refresh_linearization_, acoustic_rk3_substep_loop_).
+        # (Periodic, Bounded, Bounded) with impenetrable south and north walls also runs the whole model — set, update_state_, the slow
+        # tendencies and time_step (the reference's validation/cartesian_baroclinic_wave); on a Bounded x, or with an active open side, those
+        # are not built (the library returns BZ_ERR_UNSUPPORTED)
         self.lateral_walls = Bounded in grid.topology[:2]
         if self.lateral_walls and (Flat in grid.topology or type(self) is not CompressibleAtmosphereModel):
             raise NotImplementedError("Bounded x / y of the compressible model: 3-D grids on one device")
@@ -474,6 +476,7 @@ class CompressibleAtmosphereModel:
                      for b, k, d in ((bu, "west", 0), (bu, "east", 0), (bv, "south", 1), (bv, "north", 1))]
             self._check(lib.bz_set_acoustic_lateral_boundaries(self._ctx, *(int(x) for x in sides), td.open_boundary_relaxation),
                         "bz_set_acoustic_lateral_boundaries")
+            self._open_sides = tuple(k for k, on in zip(("west", "east", "south", "north"), sides) if on)
         # seed_pressure! (compressible_dynamics.jl:254-258)
         if ref is not None:
             Hz, Nz = grid.Hz, grid.Nz
@@ -599,11 +602,33 @@ def store_initial_state_(model):
         model.U0[k].parent.copy_(f.parent)
 
 
+def _require_whole_model_on_walls(model, what):
+    """What a model on lateral walls runs beyond its acoustic loop: (Periodic, Bounded, Bounded) with impenetrable south and north walls,
+    WENO(order = 5), dry or vapour-carrying.  Everything else fails by name (the library's rejections say the same)."""
+    if not getattr(model, "lateral_walls", False):
+        return
+    if model.grid.topology[0] == Bounded:
+        raise NotImplementedError(f"{what}: a compressible model on a Bounded x runs the acoustic substep loop only (fill its fields directly)")
+    if getattr(model, "_open_sides", ()):
+        raise NotImplementedError(f"{what}: a Bounded y with an active open boundary (NormalFlowBoundaryCondition on ρv, sides "
+                                  f"{', '.join(model._open_sides)}) runs the acoustic substep loop only")
+    if not isinstance(model.advection, WENO):
+        raise NotImplementedError(f"{what}: Centered(order = 2) is not built on a Bounded y (WENO(order = 5) is)")
+    if model.advection.bounds is not None:
+        raise NotImplementedError(f"{what}: bounds-preserving WENO (bounds = ...) is not built on a Bounded y")
+    if model.advection.order != 5:
+        raise NotImplementedError(f"{what}: WENO(order = {model.advection.order}) is not built on a Bounded y (WENO(order = 5) is)")
+    if getattr(model, "_kessler", False):
+        raise NotImplementedError(f"{what}: DCMIP2016KesslerMicrophysics is not built on a Bounded y")
+    if getattr(model, "_sa", False):
+        raise NotImplementedError(f"{what}: SaturationAdjustment is not built on a Bounded y")
+
+
 def set_(model, **kw):
     """set!(model; ρ, θ, u, v, w, qᵗ): total density first, moisture, then establish_densities!, θ and velocities
-    (set_atmosphere_model.jl:198-362; compressible_time_stepping.jl:105-150)."""
-    if getattr(model, "lateral_walls", False):
-        raise NotImplementedError("set!: a compressible model on a Bounded x / y runs the acoustic substep loop only (fill its fields directly)")
+    (set_atmosphere_model.jl:198-362; compressible_time_stepping.jl:105-150).  Walls in y: v given as a function is evaluated on the
+    faces 0 … Ny-1, ρv takes the face-mean density through the no-flux halo row, and update_state! leaves exact zeros on the wall faces."""
+    _require_whole_model_on_walls(model, "set!")
     d = model.dynamics
     g = model.grid
     keys = {}
@@ -660,8 +685,7 @@ def time_step_(model, Δt, whole_step=True):
     """time_step!(model::CompressibleAcousticModel, Δt) (acoustic_runge_kutta_3.jl:264-319) without callbacks.
     whole_step=True keeps the step behind one C call; False issues the operator sequence of the reference."""
     Δt = float(Δt)
-    if getattr(model, "lateral_walls", False):
-        raise NotImplementedError("time_step!: a compressible model on a Bounded x / y runs the acoustic substep loop only")
+    _require_whole_model_on_walls(model, "time_step!")
     if model.clock.iteration == 0:                         # maybe_prepare_first_time_step!
         seed_time_averaged_velocities_(model)
         update_state_(model, compute_tendencies=True)

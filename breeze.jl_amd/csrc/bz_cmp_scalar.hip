@@ -12,7 +12,26 @@
 // ---------------------------------------------------------------------------------------------------------------------
 #include "bz_weno.h"
 
+// Walls in y (topology (Periodic, Bounded, Bounded)): the WY instantiations of the ragged and of the LDS-tiled kernel reconstruct the scalar in
+// y with the buffer that fits at the face's row — WENO5 at faces 3 .. Ny-3, WENO3 at faces 2 and Ny-2, first-order upwind at faces 1 and
+// Ny-1 and at the wall faces 0 and Ny, whose flux is the exact zero of their v — the rule of the per-operator kernels (bz_tendency.hip: by_face).
+// A wavefront is one row: the buffer is wave-uniform and sits in a scalar register.  The density at a y face is the same two-point mean, read
+// through the no-flux halo row; G_rho takes rho v of face Ny from the first upper halo row (a zero).  WY = false compiles to the code it replaced.
+template <bool WY>
+__device__ __forceinline__ int by_face_c(const DevGrid &g, int j)
+{
+    if constexpr (WY) return __builtin_amdgcn_readfirstlane(bz_buffer_face(j, g.Ny));
+    else return 3;
+}
+template <bool WY>
+__device__ __forceinline__ double bz_up5y_c(double m3, double m2, double m1, double p0, double p1, double p2, bool left, int B)
+{
+    if constexpr (WY) return bz_upB(m3, m2, m1, p0, p1, p2, left, B);
+    else return bz_up5(m3, m2, m1, p0, p1, p2, left);
+}
+
 #define CTY 4
+template <bool WY>
 __global__ __launch_bounds__(64 * CTY) void k_scalar_tendency_rho3d(DevGrid g, double *__restrict__ Gc, double *__restrict__ Grho,
                                                                    const double *__restrict__ rho, const double *__restrict__ u,
                                                                    const double *__restrict__ v, const double *__restrict__ w,
@@ -27,6 +46,7 @@ __global__ __launch_bounds__(64 * CTY) void k_scalar_tendency_rho3d(DevGrid g, d
     const int k1 = min(k0 + kchunk, g.Nz);
     const long long sy = g.Sx, sz = g.Sxy;
     long long n = g.idx(i, j, k0);
+    const int Bylo = by_face_c<WY>(g, j), Byhi = by_face_c<WY>(g, j + 1);
     // moisture launch of a dry model (the moisture scan's word, bz_moisture.hip: bzi_scan_moisture): the advected field is identically zero,
     // every flux an exact zero — the tendency is written as such without reading anything
     if (zero_if_dry && __builtin_amdgcn_readfirstlane(*zero_if_dry) == 1) {
@@ -60,8 +80,8 @@ __global__ __launch_bounds__(64 * CTY) void k_scalar_tendency_rho3d(DevGrid g, d
         if (!g.flat_y) {
             const double ym3 = c[n - 3 * sy], ym2 = c[n - 2 * sy], ym1 = c[n - sy], yp1 = c[n + sy], yp2 = c[n + 2 * sy], yp3 = c[n + 3 * sy];
             const double v0 = v[n], v1 = v[n + sy];
-            Fy_lo = ((r0 + rho[n - sy]) / 2.0) * ((Ay * v0) * bz_up5(ym3, ym2, ym1, z0, yp1, yp2, v0 > 0.0));
-            Fy_hi = ((rho[n + sy] + r0) / 2.0) * ((Ay * v1) * bz_up5(ym2, ym1, z0, yp1, yp2, yp3, v1 > 0.0));
+            Fy_lo = ((r0 + rho[n - sy]) / 2.0) * ((Ay * v0) * bz_up5y_c<WY>(ym3, ym2, ym1, z0, yp1, yp2, v0 > 0.0, Bylo));
+            Fy_hi = ((rho[n + sy] + r0) / 2.0) * ((Ay * v1) * bz_up5y_c<WY>(ym2, ym1, z0, yp1, yp2, yp3, v1 > 0.0, Byhi));
         }
         Gc[n] = -(g.Vinv_c[k] * ((Fx_hi - Fx_lo) + (Fy_hi - Fy_lo) + (Fz_hi - Fz_lo)));
         if (Grho) {
@@ -205,7 +225,7 @@ __global__ __launch_bounds__(64 * CTY) void k_scalar_tendency_rho3d_x(DevGrid g,
 #ifndef SLT
 #define SLT 8
 #endif
-template <bool GRHO>
+template <bool GRHO, bool WY = false>
 __global__ __launch_bounds__(64 * SLT, 2) void k_scalar_rho3d_lds(DevGrid g, double *__restrict__ Gc, double *__restrict__ Grho,
                                                                 const double *__restrict__ rho, const double *__restrict__ u,
                                                                 const double *__restrict__ v, const double *__restrict__ w,
@@ -276,6 +296,7 @@ __global__ __launch_bounds__(64 * SLT, 2) void k_scalar_rho3d_lds(DevGrid g, dou
     double u0 = u[n], v0 = v[n], wt = w[n + sz];
     double grw_lo = GRHO ? rw[n] : 0.0;
     const long long nvt = g.idx(i, j0 + TY, k0);      // v of the row outside the tile (wave 0)
+    const int Byj = by_face_c<WY>(g, j), Byt = by_face_c<WY>(g, j0 + TY);      // walls in y: the buffers of the own low face and of the face above the tile
     double vT = (ty == 0) ? v[nvt] : 0.0;
     // tiles of level k0
     C[0][ty + 3][tc] = z0;
@@ -315,11 +336,11 @@ __global__ __launch_bounds__(64 * SLT, 2) void k_scalar_rho3d_lds(DevGrid g, dou
         const double *cr = Ck[ty + 3] + tc;
         const double fx = ((r0 + Rk[ty + 1][tx]) / 2.0) * ((Ax * u0) * bz_up5(cr[-3], cr[-2], cr[-1], z0, cr[1], cr[2], u0 > 0.0));
         // ---- y: low face of the own cell; wave 0 also takes the row outside the tile ----
-        const double fy = ((r0 + Rk[ty][tx + 1]) / 2.0) * ((Ay * v0) * bz_up5(Ck[ty][tc], Ck[ty + 1][tc], Ck[ty + 2][tc], z0, Ck[ty + 4][tc], Ck[ty + 5][tc], v0 > 0.0));
+        const double fy = ((r0 + Rk[ty][tx + 1]) / 2.0) * ((Ay * v0) * bz_up5y_c<WY>(Ck[ty][tc], Ck[ty + 1][tc], Ck[ty + 2][tc], z0, Ck[ty + 4][tc], Ck[ty + 5][tc], v0 > 0.0, Byj));
         FY[buf][ty][tx] = fy;
         if (ty == 0)
             FY[buf][TY][tx] = ((Rk[TY + 1][tx + 1] + Rk[TY][tx + 1]) / 2.0) *
-                              ((Ay * vT) * bz_up5(Ck[TY][tc], Ck[TY + 1][tc], Ck[TY + 2][tc], Ck[TY + 3][tc], Ck[TY + 4][tc], Ck[TY + 5][tc], vT > 0.0));
+                              ((Ay * vT) * bz_up5y_c<WY>(Ck[TY][tc], Ck[TY + 1][tc], Ck[TY + 2][tc], Ck[TY + 3][tc], Ck[TY + 4][tc], Ck[TY + 5][tc], vT > 0.0, Byt));
         // ---- stage level k + 1 ----
         C[buf ^ 1][ty + 3][tc] = zp1;
         R[buf ^ 1][ty + 1][tx + 1] = r_hi;
@@ -359,13 +380,15 @@ static int launch_scalar_rho3d(bz_ctx *ctx, const char *name, double *Gc, double
     const DevGrid &g = ctx->dg;
     ProfileScope ps(ctx, name);
     if (ctx->weno_R != 3) return bzi_scalar_rho3d_generic(ctx, Gc, Grho, rho, u, v, w, c, ru, rv, rw);
-    if (!ctx->tune.no_rho3d_exchange && ctx->tune.scalar_lds && !g.flat_y && !g.bounded_x && !g.bounded_y && g.Nx % 64 == 0 && g.Ny % SLT == 0 && g.Hx >= 3 &&
+    // walls in y: the WY instantiations of the tiled and of the ragged kernel (the exchange kernel between them is periodic only)
+    if (!ctx->tune.no_rho3d_exchange && ctx->tune.scalar_lds && !g.flat_y && !g.bounded_x && g.Nx % 64 == 0 && g.Ny % SLT == 0 && g.Hx >= 3 &&
         g.Hy >= 3 && g.Hz >= 3) {
         int kc = 64;
         while (kc > 8 && (long long)(g.Nx / 64) * (g.Ny / SLT) * ((g.Nz + kc - 1) / kc) < 2048) kc >>= 1;
         dim3 block(64, SLT), grid(g.Nx / 64, g.Ny / SLT, (g.Nz + kc - 1) / kc);
-        if (Grho) hipLaunchKernelGGL(k_scalar_rho3d_lds<true>, grid, block, 0, ctx->stream, g, Gc, Grho, rho, u, v, w, c, ru, rv, rw, zero_if_dry, kc);
-        else hipLaunchKernelGGL(k_scalar_rho3d_lds<false>, grid, block, 0, ctx->stream, g, Gc, Grho, rho, u, v, w, c, ru, rv, rw, zero_if_dry, kc);
+        bz_bools([&](auto grho, auto wy) {
+            hipLaunchKernelGGL((k_scalar_rho3d_lds<grho(), wy()>), grid, block, 0, ctx->stream, g, Gc, Grho, rho, u, v, w, c, ru, rv, rw, zero_if_dry, kc);
+        }, Grho != nullptr, g.bounded_y != 0);
         BZ_LAUNCH_CHECK();
         return BZ_OK;
     }
@@ -379,7 +402,8 @@ static int launch_scalar_rho3d(bz_ctx *ctx, const char *name, double *Gc, double
     }
     const int kc = pick_kchunk_c(g, g.Nz);
     dim3 block(64, CTY), grid((g.Nx + 63) / 64, (g.Ny + CTY - 1) / CTY, (g.Nz + kc - 1) / kc);
-    hipLaunchKernelGGL(k_scalar_tendency_rho3d, grid, block, 0, ctx->stream, g, Gc, Grho, rho, u, v, w, c, ru, rv, rw, kc, zero_if_dry);
+    if (g.bounded_y) hipLaunchKernelGGL(k_scalar_tendency_rho3d<true>, grid, block, 0, ctx->stream, g, Gc, Grho, rho, u, v, w, c, ru, rv, rw, kc, zero_if_dry);
+    else hipLaunchKernelGGL(k_scalar_tendency_rho3d<false>, grid, block, 0, ctx->stream, g, Gc, Grho, rho, u, v, w, c, ru, rv, rw, kc, zero_if_dry);
     BZ_LAUNCH_CHECK();
     return BZ_OK;
 }
@@ -388,6 +412,7 @@ extern "C" int bz_compute_slow_tendencies(bz_ctx *ctx, const bz_compressible_sta
 {
     BZ_REQUIRE_COMPRESSIBLE();
     BZ_REJECT_WALLS("bz_compute_slow_tendencies");
+    BZ_REJECT_Y_WALL_OPTIONS("bz_compute_slow_tendencies");
     if (!valid_state(s) || !valid_prog(G)) return BZ_ERR_INVALID;
     bz_state a;
     std::memset(&a, 0, sizeof(a));
@@ -399,7 +424,9 @@ extern "C" int bz_compute_slow_tendencies(bz_ctx *ctx, const bz_compressible_sta
     int rc;
     if (ctx->weno_R != 3) {      // WENO(order = 7 / 9): generic kernels (bz_tendency_generic.hip)
         if ((rc = bzi_momentum_advection_generic(ctx, &a, &Ga))) return rc;
-    } else if (ctx->dg.flat_y) {
+    } else if (ctx->dg.flat_y || ctx->dg.bounded_y) {
+        // walls in y: the per-operator kernels carry the row-wise buffers (bz_tendency.hip: by_face, by_center, symm_y); the wall row j = 0 of
+        // G_rho_v is not written (the acoustic loop holds that face at zero)
         if ((rc = bzi_momentum_advection_gen1(ctx, &a, &Ga))) return rc;
     } else {
         rc = bzi_u_tendency_lds(ctx, &a, &Ga);
@@ -422,6 +449,7 @@ extern "C" int bz_compute_moisture_tendency(bz_ctx *ctx, const bz_compressible_s
 {
     BZ_REQUIRE_COMPRESSIBLE();
     BZ_REJECT_WALLS("bz_compute_moisture_tendency");
+    BZ_REJECT_Y_WALL_OPTIONS("bz_compute_moisture_tendency");
     if (!valid_state(s) || !valid_prog(G) || !valid_sub(sub)) return BZ_ERR_INVALID;
     // (WENO order 5 kernels; the generic order 7 / 9 path evaluates the field whatever it holds)
     int rc = launch_scalar_rho3d(ctx, "moisture_tendency", G->rho_q, nullptr, s->rho, sub->time_averaged_u, sub->time_averaged_v,

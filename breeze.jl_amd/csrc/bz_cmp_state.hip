@@ -15,30 +15,39 @@
 // MP = 1: SaturationAdjustment(WarmPhaseEquilibrium) on the density-based state — rho q is the total moisture, q^v / q^l are
 // diagnosed by bz_ds_adjust at the cell's own total density and the temperature is the same Newton inversion with the latent
 // term (compressible_time_stepping.jl:191-250; saturation_adjustment.jl:236-301)
-template <bool FULL, bool LIN, int MP = 0>
+// WY: walls in y (topology (Periodic, Bounded, Bounded), dry or vapour-carrying models).  The halo writes follow the conventions of
+// DESIGN section 6 "Walls in y" instead of periodic images: a field that is a centre in y gets the no-flux copy of rows 0 and Ny - 1 in its
+// first halo rows (oy = one row down / up for those two rows), rho v and v get exact zeros on their wall faces 0 and Ny (face Ny is the first
+// upper halo row).  Row 0 reads no y neighbour: its face density is the no-flux mean (rho_d itself) and its v the wall's zero — the halo row
+// below it is written by this launch.  x stays periodic, z is unchanged.  WY = false compiles to the code it replaced.
+template <bool FULL, bool LIN, int MP = 0, bool WY = false>
 __global__ __launch_bounds__(256) void k_cmp_diagnose(DevGrid g, DiagFields F, double abstol, int maxiter)
 {
     constexpr bool KES = (MP == 2), SA = (MP == 1);
+    static_assert(!WY || (MP == 0 && !LIN), "walls in y: no microphysics; the linearisation is refreshed by its own kernel (halo rows)");
     const int i = blockIdx.x * 256 + threadIdx.x, j = blockIdx.y, k = blockIdx.z;
     if (i >= g.Nx) return;
     const long long sz = g.Sxy;
     const WrapIdx W = wrap_of(g, i, j);
-    const long long ox = W.ox, oy = W.oy;
+    const bool south = WY && j == 0, north = WY && j == g.Ny - 1;
+    const long long ox = W.ox, oy = !WY ? W.oy : south ? -(long long)g.Sx : north ? (long long)g.Sx : 0;
     const long long n = g.idx(i, j, k);
     const bool bot = (k == 0), top = (k == g.Nz - 1);
 
     const double rd = F.rho_d[n];
     const double rdx = (rd + F.rho_d[n + W.im]) / 2.0;
-    const double rdy = (rd + F.rho_d[n + W.jm]) / 2.0;
-    const double ru = F.ru[n], rv = F.rv[n];
-    const double u = ru / rdx, v = rv / rdy;
+    const double rdy = south ? rd : (rd + F.rho_d[n + W.jm]) / 2.0;
+    const double ru = F.ru[n], rv = south ? 0.0 : F.rv[n];
+    const double u = ru / rdx, v = south ? 0.0 : rv / rdy;
     const double rth = F.rth[n];
     st_img_only(F.rho_d, n, rd, ox, oy);
     st_img_only(F.ru, n, ru, ox, oy);
-    st_img_only(F.rv, n, rv, ox, oy);
+    if constexpr (WY) st_yface_w(g, F.rv, n, rv, ox, south, north);
+    else st_img_only(F.rv, n, rv, ox, oy);
     st_img_only(F.rth, n, rth, ox, oy);
     st_img(F.u, n, u, ox, oy);
-    st_img(F.v, n, v, ox, oy);
+    if constexpr (WY) st_yface_w(g, F.v, n, v, ox, true, north);
+    else st_img(F.v, n, v, ox, oy);
     if (!bot) {
         const double rw = F.rw[n];
         const double rdz = (rd + F.rho_d[n - sz]) / 2.0;
@@ -120,10 +129,12 @@ __global__ __launch_bounds__(256) void k_cmp_diagnose(DevGrid g, DiagFields F, d
         const long long h = bot ? -sz : sz;
         st_img(F.rho_d, n + h, rd, ox, oy);
         st_img(F.ru, n + h, ru, ox, oy);
-        st_img(F.rv, n + h, rv, ox, oy);
+        if constexpr (WY) st_yface_w(g, F.rv, n + h, rv, ox, true, north);
+        else st_img(F.rv, n + h, rv, ox, oy);
         st_img(F.rth, n + h, rth, ox, oy);
         st_img(F.u, n + h, u, ox, oy);
-        st_img(F.v, n + h, v, ox, oy);
+        if constexpr (WY) st_yface_w(g, F.v, n + h, v, ox, true, north);
+        else st_img(F.v, n + h, v, ox, oy);
         if (FULL) {
             st_img(F.rq, n + h, rq, ox, oy);
             st_img(F.rho, n + h, r, ox, oy);
@@ -293,11 +304,17 @@ int bzi_compressible_update_state(bz_ctx *ctx, const bz_compressible_state *s, c
         dim3 grid((g.Nx + 255) / 256, g.Ny, g.Nz), block(256);
         const double na = ctx->se.newton_abstol;
         const int nm = ctx->se.newton_maxiter;
-        bz_bools([&](auto lin) {
+        if (g.bounded_y) hipLaunchKernelGGL((k_cmp_diagnose<true, false, 0, true>), grid, block, 0, ctx->stream, g, F, na, nm);
+        else bz_bools([&](auto lin) {
             constexpr bool LIN = lin();
             bz_static_int<3>(g.microphysics, [&](auto mp) { hipLaunchKernelGGL((k_cmp_diagnose<true, LIN, mp()>), grid, block, 0, ctx->stream, g, F, na, nm); });
         }, with_linearization);
         BZ_LAUNCH_CHECK();
+    }
+    // walls in y: the linearisation of the next stage by its own kernel, which also forms the zero-gradient halo rows the substeps read
+    if (g.bounded_y && with_linearization) {
+        const int rc = bz_refresh_linearization(ctx, s, sub);
+        if (rc) return rc;
     }
     if (compute_tendencies) return bz_compute_moisture_tendency(ctx, s, G, sub);
     return BZ_OK;
@@ -309,7 +326,8 @@ int bzi_compressible_velocities(bz_ctx *ctx, const bz_compressible_state *s, con
     const DevGrid &g = ctx->dg;
     ProfileScope ps(ctx, "acoustic_velocities");
     DiagFields D = diag_fields(ctx, s, sub);
-    hipLaunchKernelGGL((k_cmp_diagnose<false, false>), dim3((g.Nx + 255) / 256, g.Ny, g.Nz), dim3(256), 0, ctx->stream, g, D, 0.0, 0);
+    if (g.bounded_y) hipLaunchKernelGGL((k_cmp_diagnose<false, false, 0, true>), dim3((g.Nx + 255) / 256, g.Ny, g.Nz), dim3(256), 0, ctx->stream, g, D, 0.0, 0);
+    else hipLaunchKernelGGL((k_cmp_diagnose<false, false>), dim3((g.Nx + 255) / 256, g.Ny, g.Nz), dim3(256), 0, ctx->stream, g, D, 0.0, 0);
     BZ_LAUNCH_CHECK();
     return BZ_OK;
 }
@@ -319,6 +337,7 @@ extern "C" int bz_compressible_update_state(bz_ctx *ctx, const bz_compressible_s
 {
     BZ_REQUIRE_COMPRESSIBLE();
     BZ_REJECT_WALLS("bz_compressible_update_state");
+    BZ_REJECT_Y_WALL_OPTIONS("bz_compressible_update_state");
     if (!valid_state(s)) return BZ_ERR_INVALID;
     if (compute_tendencies && (!valid_prog(G) || !valid_sub(sub))) return BZ_ERR_INVALID;
     if (!ctx->fused_ok) { ctx->last_error = "compressible path needs Nx >= 2Hx and Ny >= 2Hy"; return BZ_ERR_UNSUPPORTED; }

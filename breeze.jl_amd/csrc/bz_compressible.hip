@@ -58,6 +58,18 @@ static int bzi_acoustic_substep_loop(bz_ctx *ctx, const bz_compressible_state *s
     return bzi_acoustic_stage_end(ctx, s, U0, G, sub, dt, beta, moist, velocities);
 }
 
+// Walls in y: what acoustic_rk3_substep_loop! does after the loop's last kernel and bz_acoustic_substep_loop leaves to its caller there
+// (acoustic_substepping.jl:1560-1587).  The fills of rho_d, rho theta, rho u, rho v, rho w with the model's conditions, compute_velocities! and
+// the fills of u, v, w are one launch of k_cmp_diagnose<.., WY> (bzi_compressible_velocities, or the full update_state! that follows a stage
+// of a whole step); left are the fills of the time-averaged velocities: no-flux rows for <u> and <w>, wall faces 0 and Ny for the y-face
+// field <v> (the moisture tendency reads <v> of face Ny in the first upper halo row).
+static int fill_walled_averages(bz_ctx *ctx, const bz_acoustic_substepper *sub)
+{
+    double *f[3] = {sub->time_averaged_u, sub->time_averaged_v, sub->time_averaged_w};
+    const int kinds[3] = {0, BZ_HALO_YFACE, 1};
+    return bzi_fill_halos_multi(ctx, f, kinds, 3);
+}
+
 extern "C" int bz_acoustic_substep_loop(bz_ctx *ctx, const bz_compressible_state *s, const bz_compressible_prognostic *U0,
                                         const bz_compressible_prognostic *G, const bz_acoustic_substepper *sub, double dt,
                                         double beta)
@@ -77,6 +89,7 @@ extern "C" int bz_acoustic_rk3_substep(bz_ctx *ctx, const bz_compressible_state 
 {
     BZ_REQUIRE_COMPRESSIBLE();
     BZ_REJECT_WALLS("bz_acoustic_rk3_substep");
+    BZ_REJECT_Y_WALL_OPTIONS("bz_acoustic_rk3_substep");
     int rc = check_loop_args(ctx, s, U0, G, sub);
     if (rc) return rc;
     if ((rc = require_no_slab(ctx, "bz_acoustic_rk3_substep"))) return rc;
@@ -84,7 +97,9 @@ extern "C" int bz_acoustic_rk3_substep(bz_ctx *ctx, const bz_compressible_state 
     if (rc) return rc;
     rc = bz_compute_slow_tendencies(ctx, s, G);
     if (rc) return rc;
-    return bzi_acoustic_substep_loop(ctx, s, U0, G, sub, dt, beta, true, true);
+    rc = bzi_acoustic_substep_loop(ctx, s, U0, G, sub, dt, beta, true, true);
+    if (rc || !ctx->dg.bounded_y) return rc;
+    return fill_walled_averages(ctx, sub);
 }
 
 // buffer rotation of the whole-step seam: the z-halo levels of the six prognostic fields (the step's kernels write the first one of the centre
@@ -184,6 +199,7 @@ static int compressible_step_body(bz_ctx *ctx, const bz_compressible_state *s, c
         if (!fuse_end) {
             rc = bzi_acoustic_substep_loop(ctx, s, U0, G, sub, dt, betas[st], true, false);
             if (rc) return rc;
+            if (g.bounded_y && (rc = fill_walled_averages(ctx, sub))) return rc;      // walls in y take this unfused path (bzi_acoustic_stage_end_fusable)
             // update_state! (+ prepare_acoustic_cache! of the next stage: same inputs, folded into the diagnosis kernel)
             rc = bzi_compressible_update_state(ctx, s, G, sub, true, st < 2);
             if (rc) return rc;
@@ -213,6 +229,7 @@ extern "C" int bz_time_step_compressible(bz_ctx *ctx, const bz_compressible_stat
 {
     BZ_REQUIRE_COMPRESSIBLE();
     BZ_REJECT_WALLS("bz_time_step_compressible");
+    BZ_REJECT_Y_WALL_OPTIONS("bz_time_step_compressible");
     int rc = check_loop_args(ctx, s, U0, G, sub);
     if (rc) return rc;
     if ((rc = bzi_scan_moisture_field(ctx, s->rho_q))) return rc;      // dry models: the moisture tendency kernels write exact zeros without reading

@@ -215,14 +215,29 @@ static bool valid_sub(const bz_acoustic_substepper *a)
            a->previous_density_potential_temperature_perturbation && a->time_averaged_u && a->time_averaged_v &&
            a->time_averaged_w && a->slow_vertical_momentum_tendency && a->vertical_solver_source_term;
 }
-// Contexts with a Bounded x or y run the acoustic loop (bz_refresh_linearization, bz_acoustic_substep_loop, bz_acoustic_stage_begin /
-// _substep / _stage_end); the rest of the compressible model on lateral walls — wall-aware slow tendencies, update_state! with the model's
-// boundary conditions — is not built
+// Contexts with a Bounded x run the acoustic loop only (bz_refresh_linearization, bz_acoustic_substep_loop, bz_acoustic_stage_begin /
+// _substep / _stage_end); the rest of the compressible model — wall-aware slow tendencies, update_state! with the model's boundary
+// conditions — is built for walls in y alone ((Periodic, Bounded, Bounded), impenetrable sides: BZ_REJECT_Y_WALL_OPTIONS)
 #define BZ_REJECT_WALLS(what)                                                                                                          \
     do {                                                                                                                               \
-        if (ctx->dg.bounded_x || ctx->dg.bounded_y) {                                                                                  \
+        if (ctx->dg.bounded_x) {                                                                                                       \
             ctx->last_error = what ": not implemented on a Bounded x or y (compressible contexts with lateral walls run the acoustic substep loop only)"; \
             return BZ_ERR_UNSUPPORTED;                                                                                                 \
+        }                                                                                                                              \
+    } while (0)
+// what whole steps on walls in y do not carry: an active open side (the loop alone relaxes it), WENO orders 7 / 9, microphysics
+#define BZ_REJECT_Y_WALL_OPTIONS(what)                                                                                                 \
+    do {                                                                                                                               \
+        if (ctx->dg.bounded_y) {                                                                                                       \
+            const char *why_ = (ctx->ac_open[2] || ctx->ac_open[3]) ? "an active open boundary (NormalFlowBoundaryCondition on rho v)"  \
+                               : ctx->weno_R != 3                    ? "WENO(order = 7 | 9)"                                              \
+                               : ctx->dg.microphysics == 2           ? "DCMIP2016KesslerMicrophysics"                                     \
+                               : ctx->dg.microphysics == 1           ? "SaturationAdjustment"                                             \
+                                                                     : nullptr;                                                          \
+            if (why_) {                                                                                                                \
+                ctx->last_error = std::string(what ": not implemented on a Bounded y with ") + why_;                                   \
+                return BZ_ERR_UNSUPPORTED;                                                                                             \
+            }                                                                                                                          \
         }                                                                                                                              \
     } while (0)
 #define BZ_REQUIRE_COMPRESSIBLE()                                                      \
@@ -265,6 +280,20 @@ static DiagFields diag_fields(bz_ctx *ctx, const bz_compressible_state *s, const
 }
 
 static bool ac_walls(const bz_ctx *ctx) { return ctx->dg.bounded_x || ctx->dg.bounded_y; }
+
+// Walls in y, a y-face field (rho v, v): the x image; the south wall face (row 0) stored as the zero it is; next to the north wall also the
+// wall face j = Ny, which lives in the first upper halo row ("Walls in y")
+#ifdef __HIPCC__
+__device__ __forceinline__ void st_yface_w(const DevGrid &g, double *__restrict__ f, long long n, double v, long long ox, bool store, bool north)
+{
+    if (store) f[n] = v;
+    if (ox) f[n + ox] = v;
+    if (north) {
+        f[n + g.Sx] = 0.0;
+        if (ox) f[n + g.Sx + ox] = 0.0;
+    }
+}
+#endif
 
 // ---- functions that cross the units ---------------------------------------------------------------------------------
 // bz_cmp_state.hip: update_state! [+ the moisture tendencies] [+ the linearisation of the next stage]; the velocities-only tail of

@@ -474,9 +474,12 @@ int bz_acoustic_direct_damping(bz_ctx *ctx, const bz_compressible_state *s, cons
 /* Lateral boundaries of the acoustic substep loop (acoustic_substepping.jl:1300-1395: apply_open_boundary_relaxation!,
  * enforce_wall_impenetrability!), compressible contexts on a grid with a Bounded x and / or y — (Bounded, Periodic, Bounded),
  * (Periodic, Bounded, Bounded), (Bounded, Bounded, Bounded); single device.  Such a context runs bz_refresh_linearization,
- * bz_acoustic_substep_loop and the three-piece stage interface; bz_compressible_update_state, bz_compute_slow_tendencies,
- * bz_compute_moisture_tendency, bz_acoustic_rk3_substep and bz_time_step_compressible return BZ_ERR_UNSUPPORTED on it (bz_last_error names
- * the function that was called).
+ * bz_acoustic_substep_loop and the three-piece stage interface.  With a Bounded x, bz_compressible_update_state,
+ * bz_compute_slow_tendencies, bz_compute_moisture_tendency, bz_acoustic_rk3_substep and bz_time_step_compressible return BZ_ERR_UNSUPPORTED
+ * (bz_last_error names the function that was called).  (Periodic, Bounded, Bounded) runs them too — whole steps between impenetrable south
+ * and north walls, WENO(order = 5), no microphysics: rho v and v carry exact zeros on their wall faces j = 0 and j = Ny (face Ny is the
+ * first upper halo row), every field that is a centre in y the no-flux copy in its first halo rows, and the wall row j = 0 of the slow
+ * rho v tendency is not written; with an active open side, WENO 7 / 9 or microphysics they return BZ_ERR_UNSUPPORTED naming the option.
  * The substepper's own fields take the zero-gradient halo of their default boundary conditions from the library; the model's fields
  * (rho_d, rho_theta, p, the slow tendencies) are read with the one halo row / column the caller's boundary conditions filled.
  * *_open != 0: that side carries an active open (normal-flow) boundary condition on the wall-normal momentum — the outermost cells of rho',
