@@ -26,6 +26,9 @@ from .microphysics import (DCMIP2016KesslerMicrophysics, KesslerMicrophysicalFie
 from .forcings import (BulkDrag, BulkSensibleHeatFlux, BulkVaporFlux, FPlane, FieldBoundaryConditions, FluxBoundaryCondition, Forcing, FrictionVelocityDrag,  # noqa: F401,E402
                        GaussianMask, GeostrophicForcing, Relaxation, SmagorinskyLilly, SubsidenceForcing, geostrophic_forcings)
 from .model import compute_closure_fields_, compute_flux_bc_tendencies_  # noqa: F401,E402
+from .model import implicit_step_  # noqa: F401,E402
+from .closures import (ExplicitTimeDiscretization, HorizontalScalarDiffusivity, ScalarDiffusivity, VerticalScalarDiffusivity,  # noqa: F401,E402
+                       VerticallyImplicitTimeDiscretization)
 from .forcings import (FilteredSurfaceVelocities, FittedStabilityFunction, PolynomialCoefficient, RichardsonNumberMapping,  # noqa: F401,E402
                        StabilityFunctionParameters)
 from . import benchmarks  # noqa: F401,E402

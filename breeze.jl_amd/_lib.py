@@ -105,6 +105,10 @@ class bz_smagorinsky_lilly(C.Structure):
     _fields_ = [("smagorinsky_coefficient", C.c_double), ("reduction_factor", C.c_double), ("prandtl_number", C.c_double)]
 
 
+class bz_scalar_diffusivity(C.Structure):
+    _fields_ = [("formulation", C.c_int32), ("time_discretization", C.c_int32), ("nu", C.c_double), ("kappa", C.c_double)]
+
+
 class bz_column_forcings(C.Structure):
     _fields_ = [("u_forcing", _dp), ("v_forcing", _dp), ("theta_forcing", _dp), ("moisture_forcing", _dp),
                 ("energy_forcing", _dp), ("subsidence_vertical_velocity", _dp),
@@ -294,6 +298,8 @@ SYMBOLS = {
     "bz_comm_compressible_update_state": (C.c_int, [_ctx, _csp, _cpp, _asp, C.c_int]),
     "bz_set_tracers": (C.c_int, [_ctx, C.c_int32, C.POINTER(bz_tracer_fields)]),
     "bz_set_closure": (C.c_int, [_ctx, C.POINTER(bz_smagorinsky_lilly), C.c_void_p]),
+    "bz_set_scalar_diffusivity": (C.c_int, [_ctx, C.POINTER(bz_scalar_diffusivity), C.c_void_p, C.c_void_p]),
+    "bz_implicit_step": (C.c_int, [_ctx, _sp, C.c_double]),
     "bz_set_bounds_preserving_advection": (C.c_int, [_ctx, C.POINTER(bz_bounds_preserving_advection)]),
     "bz_compute_closure_fields": (C.c_int, [_ctx, _sp]),
     "bz_set_bulk_surface_fluxes": (C.c_int, [_ctx, C.POINTER(bz_bulk_surface_fluxes)]),

@@ -514,6 +514,10 @@ extern "C" int bz_set_closure(bz_ctx *ctx, const bz_smagorinsky_lilly *closure, 
     if (!ctx) return BZ_ERR_INVALID;
     if (!closure) { ctx->has_closure = false; ctx->closure_nu = nullptr; return BZ_OK; }
     if (!eddy_viscosity) return BZ_ERR_INVALID;
+    if (ctx->has_diffusivity) {
+        ctx->last_error = "bz_set_closure: a ScalarDiffusivity closure is attached (bz_set_scalar_diffusivity): one closure per context";
+        return BZ_ERR_UNSUPPORTED;
+    }
     if (ctx->compressible || ctx->dg.formulation != 0 || ctx->dg.microphysics == 2) {      // y-slab contexts: through the library-owned distributed step (bz_comm.hip)
         ctx->last_error = "bz_set_closure: SmagorinskyLilly is implemented for the anelastic "
                           "potential-temperature model (microphysics nothing or SaturationAdjustment)";
@@ -544,6 +548,7 @@ static ClosureFields closure_fields(bz_ctx *ctx, const bz_state *s)
 extern "C" int bz_compute_closure_fields(bz_ctx *ctx, const bz_state *s)
 {
     if (!ctx || !s) return BZ_ERR_INVALID;
+    if (ctx->has_diffusivity) return bzi_diffusivity_halos(ctx);      // these closures have no closure fields: only the halos of a field-valued K
     if (!ctx->has_closure) return BZ_OK;
     { const int rcs = bzi_refresh_diagnostics(ctx, s, "bz_compute_closure_fields"); if (rcs) return rcs; }
     const DevGrid &g = ctx->dg;

@@ -403,6 +403,7 @@ extern "C" void bz_destroy(bz_ctx *ctx)
     if (ctx->d_columns) hipFree(ctx->d_columns);
     bzi_forcing_teardown(ctx);
     bzi_closure_teardown(ctx);
+    bzi_diffusivity_teardown(ctx);
     bzi_diagnostics_teardown(ctx);
     bzi_azimuthal_teardown(ctx);
     bzi_moments_teardown(ctx);

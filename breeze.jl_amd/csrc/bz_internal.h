@@ -510,6 +510,13 @@ struct bz_ctx {
     bz_smagorinsky_lilly closure;
     double *closure_nu = nullptr;     // model.closure_fields.nu_e (caller-owned centre field)
     double *d_closure_ipi = nullptr;  // (pst/p_r[k])^(Rd/cpd), k = -1 .. Nz
+    // closure = ScalarDiffusivity / VerticalScalarDiffusivity (bz_set_scalar_diffusivity, bz_diffusivity.hip)
+    bool has_diffusivity = false;
+    bz_scalar_diffusivity diffusivity;
+    double *diff_nu = nullptr, *diff_kappa = nullptr;      // field-valued nu / kappa (caller-owned centre fields); nullptr: the number
+    double *d_diff_table = nullptr;   // constant K: [lower, c', 1 / pivot] per field class and level (k_implicit_table)
+    double *d_diff_scratch = nullptr; // field K: c' of the solve, one parent-shaped array per field of the launch
+    int diff_scratch_fields = 0;
     double *up2_user = nullptr, *vp2_user = nullptr;   // caller-owned replacements of d_up2 / d_vp2 (bz_set_acoustic_scratch)
     alignas(8) unsigned char ac_stage_storage[160] = {0};   // AcStage of the stage in flight (bz_compressible_internal.h)
     // advection = (; rho_q = WENO(order = 5, bounds = (lo, hi))) (bz_set_bounds_preserving_advection, bz_bounded.hip)
@@ -621,6 +628,12 @@ int bzi_scalar_rho3d_generic(bz_ctx *ctx, double *Gc, double *Grho, const double
                              const double *c, const double *ru, const double *rv, const double *rw);
 void bzi_closure_teardown(bz_ctx *ctx);
 int bzi_apply_closure(bz_ctx *ctx, const bz_state *s, double *Gu, double *Gv, double *Gw, double *Gth, double *Gq, double scale);
+// ---- ScalarDiffusivity closures (bz_diffusivity.hip) ----
+void bzi_diffusivity_teardown(bz_ctx *ctx);
+int bzi_diffusivity_halos(bz_ctx *ctx);      // halos of a field-valued nu / kappa
+int bzi_apply_diffusivity(bz_ctx *ctx, const bz_state *s, double *Gu, double *Gv, double *Gw, double *Gth, double *Gq, double scale);
+// implicit_step! of every prognostic field: momentum and the two scalar densities from the arguments, species and tracers from the context
+int bzi_implicit_step(bz_ctx *ctx, double *ru, double *rv, double *rw, double *rth, double *rq, double dtau);
 int bzi_kessler_rk3(bz_ctx *ctx, double dt, double alpha, bool first);
 // column part of microphysics_model_update! on the attached species; density / pressure: 3-D parents of a compressible context, nullptr = reference columns
 int bzi_kessler_columns(bz_ctx *ctx, double *theta, double *rho_theta, double *rho_q, const double *density, const double *pressure, double dt);

@@ -146,7 +146,7 @@ static int kin_configuration(bz_ctx *ctx, const char *who)
     if (ctx->weno_R != 3 || ctx->scalar_R != 3) what = "WENO(order = 5) is implemented";
     else if (g.formulation != 0) what = "the StaticEnergy formulation is not implemented";
     else if (g.microphysics == 2) what = "Kessler microphysics is not implemented";
-    else if (ctx->has_closure) what = "closures are not implemented";
+    else if (ctx->has_closure || ctx->has_diffusivity) what = "closures are not implemented";
     else if (ctx->has_forcings || ctx->has_relaxation || ctx->field_forcing) what = "forcings and sponges are not implemented";
     else if (ctx->has_bulk) what = "flux boundary conditions are not implemented";
     else if (ctx->bounded_mask) what = "bounds-preserving advection is not implemented";

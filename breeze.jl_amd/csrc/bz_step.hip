@@ -47,9 +47,9 @@ bz_tier bzi_anelastic_tier(const bz_ctx *ctx)
                                 : ctx->scalar_R == ctx->weno_R && (ctx->weno_R == 3 || ctx->n_tracers == 0);
     const bool rk_forcings = slab || !(ctx->has_forcings && ctx->tune.no_fuse_forcing);   // slab: BZ_NO_FUSE_FORCING is not consulted
     const bool fused_tier = !slab;                                                        // slab: no fused tier, operators instead
-    // lean seam: dry / vapour WENO5 theta model without closure, bulk fluxes, relaxation, tracers, microphysics
+    // lean seam: dry / vapour WENO5 theta model without closure (SmagorinskyLilly or a ScalarDiffusivity), bulk fluxes, relaxation, tracers, microphysics
     if ((ctx->fused_ok || walls_lean) && lean_switches && order5 && lean_anelastic && theta_model && g.microphysics == 0 && lean_forcings &&
-        !ctx->has_bulk && !ctx->has_closure && !ctx->has_relaxation && ctx->n_tracers == 0 && !ctx->bounded_mask &&
+        !ctx->has_bulk && !ctx->has_closure && !ctx->has_diffusivity && !ctx->has_relaxation && ctx->n_tracers == 0 && !ctx->bounded_mask &&
         (long long)g.Sxy * (g.Nz + 2 * g.Hz + 1) < (1LL << 32))
         return BZ_TIER_LEAN;
     if ((ctx->fused_ok || (walls_lean && ctx->weno_R != 3)) && ctx->fuse_rk && rk_orders && theta_model && g.microphysics != 2 &&
@@ -95,6 +95,7 @@ int bzi_fused_rk_physics(bz_ctx *ctx, const bz_state *s, const bz_prognostic *G,
         if ((rc = bzi_tracer_rk3(ctx, dt, alpha, first))) return rc;
     }
     if (ctx->has_closure && (rc = bzi_apply_closure(ctx, s, G->rho_u, G->rho_v, G->rho_w, s->rho_theta, s->rho_q, alpha * dt))) return rc;
+    if (ctx->has_diffusivity && (rc = bzi_apply_diffusivity(ctx, s, G->rho_u, G->rho_v, G->rho_w, s->rho_theta, s->rho_q, alpha * dt))) return rc;
     if (ctx->has_forcings && (rc = bzi_apply_forcings(ctx, s, G->rho_u, G->rho_v, s->rho_theta, s->rho_q, alpha * dt, fold))) return rc;
     if ((ctx->has_forcings || ctx->has_bulk) && (rc = bzi_flux_bc(ctx, s, G->rho_u, G->rho_v, s->rho_theta, s->rho_q, alpha * dt))) return rc;
     return BZ_OK;
@@ -232,6 +233,8 @@ static int step_fused_rk(bz_ctx *ctx, const bz_state *s, const bz_prognostic *U0
         ctx->fold_momentum_forcing = false;
         if (rc) return rc;
         if ((rc = bzi_fused_rk_physics(ctx, s, G, dt, alpha, stage == 0, fold))) return rc;
+        // implicit_step! of the stage (:124-161): the predictor momentum in the G slots, the scalars in place
+        if ((rc = bzi_implicit_step(ctx, G->rho_u, G->rho_v, G->rho_w, s->rho_theta, s->rho_q, alpha * dt))) return rc;
         if (ctx->dg.bounded_y && (rc = bzi_fill_halo(ctx, G->rho_v, BZ_HALO_YFACE))) return rc;      // wall faces j = 0, Ny of the predictor (the source term reads face Ny)
         if ((rc = bzi_poisson_from_momentum(ctx, s, alpha * dt, G))) return rc;
         // pressure_anomaly is a diagnostic nobody reads inside the step: only the last stage scatters it
@@ -260,6 +263,7 @@ static int step_fused(bz_ctx *ctx, const bz_state *s, const bz_prognostic *U0, c
         if ((rc = bzi_rk3_fused(ctx, s, U0, G, dt, alpha, stage == 0))) return rc;
         if (ctx->dg.microphysics == 2 && (rc = bzi_kessler_rk3(ctx, dt, alpha, stage == 0))) return rc;
         if ((rc = bzi_tracer_rk3(ctx, dt, alpha, stage == 0))) return rc;
+        if ((rc = bz_implicit_step(ctx, s, alpha * dt))) return rc;
         if ((rc = bzi_poisson_from_momentum(ctx, s, alpha * dt, nullptr))) return rc;
         if ((rc = bzi_project_diagnose(ctx, s, alpha * dt))) return rc;
         if ((rc = bzi_tracer_specific(ctx))) return rc;
@@ -281,6 +285,7 @@ static int step_operators(bz_ctx *ctx, const bz_state *s, const bz_prognostic *U
         const double alpha = BZ_SSP_RK3_ALPHA[stage];
         if ((rc = bz_compute_flux_bc_tendencies(ctx, s, G))) return rc;              // :229,243,257
         if ((rc = bz_ssp_rk3_substep(ctx, s, U0, G, dt, alpha))) return rc;          // :230,244,258
+        if ((rc = bz_implicit_step(ctx, s, alpha * dt))) return rc;                  // :124-161 (a no-op without a vertically implicit closure)
         if ((rc = bz_compute_pressure_correction(ctx, s, alpha * dt))) return rc;    // :232,246,260
         if ((rc = bz_make_pressure_correction(ctx, s, alpha * dt))) return rc;       // :233,247,261
         if ((rc = bz_update_state(ctx, s, G, 1))) return rc;                         // :236,250,270

@@ -433,6 +433,7 @@ static int finish_tendencies(bz_ctx *ctx, const bz_state *s, const bz_prognostic
     }
     if (ctx->bounded_mask && (rc = bzi_bounded_tendencies(ctx, s, G))) return rc;
     if (ctx->has_closure && (rc = bzi_apply_closure(ctx, s, G->rho_u, G->rho_v, G->rho_w, G->rho_theta, G->rho_q, 1.0))) return rc;
+    if (ctx->has_diffusivity && (rc = bzi_apply_diffusivity(ctx, s, G->rho_u, G->rho_v, G->rho_w, G->rho_theta, G->rho_q, 1.0))) return rc;
     if (ctx->has_forcings && (rc = bzi_apply_forcings(ctx, s, G->rho_u, G->rho_v, G->rho_theta, G->rho_q, 1.0))) return rc;
     if ((rc = bzi_apply_relaxation(ctx, s, G))) return rc;
     BZ_LAUNCH_CHECK();

@@ -20,6 +20,10 @@ class SmagorinskyLilly:
     """SmagorinskyLilly(; C = 0.16, Cb = 1.0, Pr = 1.0) (Oceananigans.TurbulenceClosures, re-exported src/Breeze.jl:186,220)."""
 
     def __init__(self, C=0.16, Cb=1.0, Pr=1.0):
+        from .closures import ExplicitTimeDiscretization, VerticallyImplicitTimeDiscretization
+        if isinstance(C, (ExplicitTimeDiscretization, VerticallyImplicitTimeDiscretization)) or C in (ExplicitTimeDiscretization, VerticallyImplicitTimeDiscretization):
+            # SmagorinskyLilly(VerticallyImplicitTimeDiscretization()): Oceananigans' optional positional argument
+            raise NotImplementedError("SmagorinskyLilly(time_discretization): only the explicit discretisation is implemented")
         self.C, self.Cb, self.Pr = float(C), float(Cb), float(Pr)
 
 

@@ -340,8 +340,17 @@ class AtmosphereModel:
         if timestepper not in ("SSPRungeKutta3", ":SSPRungeKutta3"):
             raise NotImplementedError("only SSPRungeKutta3 is implemented")
         from .forcings import SmagorinskyLilly
-        if closure is not None and not isinstance(closure, SmagorinskyLilly):
-            raise NotImplementedError("closure: SmagorinskyLilly() is implemented")
+        from .closures import ScalarDiffusivity
+        if isinstance(closure, (tuple, list)):
+            raise NotImplementedError("closure: one closure is implemented (no closure tuples)")
+        if closure is not None and not isinstance(closure, (SmagorinskyLilly, ScalarDiffusivity)):
+            raise NotImplementedError("closure: SmagorinskyLilly(), ScalarDiffusivity(...) and VerticalScalarDiffusivity(...) are implemented")
+        self._diffusivity = isinstance(closure, ScalarDiffusivity)
+        if self._diffusivity and any("Slab" in k.__name__ for k in type(self).__mro__):      # the y-slab models of distributed.py
+            raise NotImplementedError("closure = ScalarDiffusivity / VerticalScalarDiffusivity: not implemented on y-slab (distributed) models")
+        if self._diffusivity and (bounded_x or bounded_y):
+            raise NotImplementedError("closure = ScalarDiffusivity / VerticalScalarDiffusivity: not implemented between walls in x or y "
+                                      "(Bounded x / Bounded y)")
         self.closure = closure
         self.coriolis, self.forcing, self.boundary_conditions = coriolis, forcing, boundary_conditions
         from .microphysics import DCMIP2016KesslerMicrophysics, SaturationAdjustment, TetensFormula
@@ -499,7 +508,19 @@ class AtmosphereModel:
                 raise ValueError("bounds-preserving tracer advection without tracers")
             bs = T.bz_bounds_preserving_advection(ba["lower"], ba["upper"], ba["moisture"], ba["microphysical_species"], ba["tracers"], 0)
             self._check(lib.bz_set_bounds_preserving_advection(self._ctx, C.byref(bs)), "bz_set_bounds_preserving_advection")
-        if closure is not None:      # build_closure_fields: nu_e (atmosphere_model.jl:276)
+        if self._diffusivity:      # no closure fields: nu and kappa are numbers or the user's own centre fields
+            Kf = {}
+            for name, value in (("ν", closure.ν), ("κ", closure.κ)):
+                if isinstance(value, Field):
+                    if value.grid is not grid or value.parent.device != self.device or value.parent.dtype != self.momentum["ρu"].parent.dtype:
+                        raise ValueError(f"closure {name}: the field must live on the model's grid, device and float type")
+                    Kf[name] = value
+            sd = T.bz_scalar_diffusivity(closure.formulation, 1 if closure.vertically_implicit else 0,
+                                         0.0 if "ν" in Kf else closure.ν, 0.0 if "κ" in Kf else closure.κ)
+            self._diffusivity_fields = Kf      # keeps the arrays the context reads alive
+            self._check(lib.bz_set_scalar_diffusivity(self._ctx, C.byref(sd), C.c_void_p(Kf["ν"].ptr() if "ν" in Kf else None),
+                                                      C.c_void_p(Kf["κ"].ptr() if "κ" in Kf else None)), "bz_set_scalar_diffusivity")
+        elif closure is not None:      # build_closure_fields: nu_e (atmosphere_model.jl:276)
             if self._kessler or formulation != "LiquidIcePotentialTemperature":
                 raise NotImplementedError("SmagorinskyLilly is implemented for the potential-temperature formulation without Kessler")
             self.closure_fields = {"νₑ": fld("ccc")}
@@ -707,6 +728,12 @@ def compute_scalar_tendency_(model, c, Gc):
 def compute_closure_fields_(model):
     """compute_closure_fields!(model.closure_fields, model.closure, model) (update_atmosphere_model_state.jl:218)."""
     model._check(model._lib.bz_compute_closure_fields(model._ctx, C.byref(model._state)), "bz_compute_closure_fields")
+
+
+def implicit_step_(model, Δt):
+    """implicit_step!(field, implicit_solver, closure, ..., Δt) of every prognostic field (ssp_runge_kutta_3.jl:124-161): a no-op
+    without a vertically implicit closure."""
+    model._check(model._lib.bz_implicit_step(model._ctx, C.byref(model._state), float(Δt)), "bz_implicit_step")
 
 
 def compute_flux_bc_tendencies_(model):
@@ -946,6 +973,7 @@ def time_step_(model, Δt, whole_step=True):
         for stage, α in enumerate((1.0, 1.0 / 4.0, 2.0 / 3.0), start=1):
             compute_flux_bc_tendencies_(model)
             ssp_rk3_substep_(model, Δt, α)
+            implicit_step_(model, α * Δt)      # ssp_runge_kutta_3.jl:124-161 (a no-op without a vertically implicit closure)
             compute_pressure_correction_(model, α * Δt)
             make_pressure_correction_(model, α * Δt)
             update_state_(model, compute_tendencies=True)

@@ -753,6 +753,49 @@ typedef struct bz_smagorinsky_lilly {
 int bz_set_closure(bz_ctx *ctx, const bz_smagorinsky_lilly *closure, double *eddy_viscosity);   /* NULL detaches */
 int bz_compute_closure_fields(bz_ctx *ctx, const bz_state *s);
 
+/* ---- closure = ScalarDiffusivity(...) / VerticalScalarDiffusivity(...), explicit or vertically implicit (csrc/bz_diffusivity.hip) ----
+ * Breeze's part is followed line by line: dynamic fluxes = rho_r at the flux location x Oceananigans' kinematic flux, with the
+ * closure's time discretisation passed into every flux (src/TurbulenceClosures/TurbulenceClosures.jl:48-101), and
+ * implicit_step!(field, solver, closure, ..., alpha dt) after the RK update of every prognostic field
+ * (src/TimeSteppers/ssp_runge_kutta_3.jl:124-161; order inside a stage :229-236: flux-BC tendencies, RK update, implicit step,
+ * pressure correction, update_state!).  Oceananigans (0.110.14) is not vendored: what follows is the reading — PARITY UNPINNED, pinned
+ * only by closed forms and the reference's own known answers (test/vertical_diffusion.jl, test/turbulence_closures.jl:14-50;
+ * tests/scalar_diffusivity_reference.py restates it on the CPU).
+ *   formulation 0 (isotropic): the SmagorinskyLilly fluxes with the given nu in place of nu_e and an independent kappa: stresses
+ *     -2 nu Sigma_ij with nu averaged to ccc / ffc / fcf / cff, scalar fluxes -kappa grad c with kappa averaged to the face.
+ *   formulation 1 (vertical): only tau_uz = -nu_fcf dz u, tau_vz = -nu_cff dz v, tau_wz = -nu_ccc dz w, J_z = -kappa_ccf dz c.
+ *   time_discretization 1 (vertically implicit): the explicit tendency drops what the solve covers — vertical formulation: all four
+ *     z fluxes; isotropic: tau_uz -> -nu_fcf dx w, tau_vz -> -nu_cff dy w (the cross terms stay explicit), tau_wz -> 0, J_z -> 0,
+ *     horizontal fluxes unchanged.  The fluxes on the boundary faces k = 1 and Nz + 1 stay explicit in Oceananigans; they vanish
+ *     under the default no-flux / impenetrable conditions (the only ones here), so there is no code for them.
+ *   implicit step: (I - dtau dz K dz) phi = phi* on the density-weighted prognostic field itself (rho u, rho v, rho w, rho theta or
+ *     rho e, the moisture density, Kessler species, tracer densities); no density in the operator — the reference's own asymmetry
+ *     (test/turbulence_closures.jl:38-50 accepts rtol 1e-5 for a uniform e).  Rows of z-centre fields, k = 1 .. Nz, K^f = K at the
+ *     z face of the field's own column (nu_fcf, nu_cff, kappa_ccf): upper(k) = -dtau K^f[k+1] / (dz^c[k] dz^f[k+1]) (0 at Nz),
+ *     lower(k) = -dtau K^f[k] / (dz^c[k] dz^f[k]) (0 at 1), diag = 1 - upper - lower.  Rows of rho w, faces k = 2 .. Nz, nu at
+ *     centres: upper(k) = -dtau nu[k] / (dz^f[k] dz^c[k]), lower(k) = -dtau nu[k-1] / (dz^f[k] dz^c[k-1]), diag = 1 - upper - lower;
+ *     the wall value w = 0 enters rows 2 and Nz through the diagonal only; faces 1 and Nz + 1 are never written
+ *     (src/AtmosphereModels/implicit_vertical_advection.jl:202-214,270-292 documents the same z-Face convention).  K = 0 gives
+ *     identity rows; a closure whose nu (kappa) is the number 0 skips the momentum (the scalars) altogether.
+ * nu_field / kappa_field: centre field parents with the model's halos (caller-owned; NULL: the number in the struct).  The library
+ * fills their halos — periodic in x and y, zero gradient in z — before every use (bz_compute_closure_fields, bz_compute_tendencies,
+ * bz_implicit_step), because the user may have rewritten them.  Mutually exclusive with bz_set_closure: the second attach returns
+ * BZ_ERR_UNSUPPORTED.  Single-device anelastic contexts, periodic in x and y (or Flat y); y-slab, walled, compressible and
+ * kinematic contexts return BZ_ERR_UNSUPPORTED naming the option.  With one attached bz_compute_tendencies subtracts the explicit
+ * divergences where it subtracts SmagorinskyLilly's, and bz_time_step(s)_anelastic run the implicit step of every stage (never on
+ * the lean tier).  NULL detaches. */
+typedef struct bz_scalar_diffusivity {
+    int32_t formulation;           /* 0: ScalarDiffusivity (isotropic), 1: VerticalScalarDiffusivity */
+    int32_t time_discretization;   /* 0: ExplicitTimeDiscretization, 1: VerticallyImplicitTimeDiscretization */
+    double nu;                     /* used where nu_field == NULL */
+    double kappa;                  /* used where kappa_field == NULL (every scalar) */
+} bz_scalar_diffusivity;
+int bz_set_scalar_diffusivity(bz_ctx *ctx, const bz_scalar_diffusivity *c, double *nu_field, double *kappa_field);
+/* implicit_step! of every prognostic field of the context with dtau = dt (a stage passes alpha dt): one launch.  Interior cells only:
+ * the halos are left to the operators that follow (bz_compute_pressure_correction and bz_update_state fill what they read).  A no-op
+ * without a vertically implicit closure. */
+int bz_implicit_step(bz_ctx *ctx, const bz_state *s, double dt);
+
 /* ---- the reductions of the run! loop around the step ---- */
 /* cell_advection_timescale(model) (src/AtmosphereModels/cell_advection_timescale.jl:47-66): minimum over the interior of
  * 1 / (|u|/dx + |v|/dy + |w|/dz) into *out (host; +Inf for a fluid at rest); w == NULL gives the HorizontalFormulation.
