@@ -27,8 +27,8 @@ from .forcings import (BulkDrag, BulkSensibleHeatFlux, BulkVaporFlux, FPlane, Fi
                        GaussianMask, GeostrophicForcing, Relaxation, SmagorinskyLilly, SubsidenceForcing, geostrophic_forcings)
 from .model import compute_closure_fields_, compute_flux_bc_tendencies_  # noqa: F401,E402
 from .model import implicit_step_  # noqa: F401,E402
-from .closures import (ExplicitTimeDiscretization, HorizontalScalarDiffusivity, ScalarDiffusivity, VerticalScalarDiffusivity,  # noqa: F401,E402
-                       VerticallyImplicitTimeDiscretization)
+from .closures import (AnisotropicMinimumDissipation, DynamicSmagorinsky, ExplicitTimeDiscretization, HorizontalScalarDiffusivity,  # noqa: F401,E402
+                       ScalarDiffusivity, VerticalScalarDiffusivity, VerticallyImplicitTimeDiscretization)
 from .forcings import (FilteredSurfaceVelocities, FittedStabilityFunction, PolynomialCoefficient, RichardsonNumberMapping,  # noqa: F401,E402
                        StabilityFunctionParameters)
 from . import benchmarks  # noqa: F401,E402

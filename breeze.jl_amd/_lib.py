@@ -302,6 +302,7 @@ SYMBOLS = {
     "bz_implicit_step": (C.c_int, [_ctx, _sp, C.c_double]),
     "bz_set_bounds_preserving_advection": (C.c_int, [_ctx, C.POINTER(bz_bounds_preserving_advection)]),
     "bz_compute_closure_fields": (C.c_int, [_ctx, _sp]),
+    "bz_compressible_compute_closure_fields": (C.c_int, [_ctx, _csp]),
     "bz_set_bulk_surface_fluxes": (C.c_int, [_ctx, C.POINTER(bz_bulk_surface_fluxes)]),
     "bz_set_surface_layer": (C.c_int, [_ctx, C.POINTER(bz_surface_layer)]),
     "bz_surface_layer_initialize": (C.c_int, [_ctx, _sp]),

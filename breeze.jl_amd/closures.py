@@ -61,3 +61,17 @@ class HorizontalScalarDiffusivity:
 
     def __init__(self, *a, **kw):
         raise NotImplementedError("HorizontalScalarDiffusivity is not implemented (ScalarDiffusivity and VerticalScalarDiffusivity are)")
+
+
+class DynamicSmagorinsky:
+    """Named so that asking for it says what is missing."""
+
+    def __init__(self, *a, **kw):
+        raise NotImplementedError("DynamicSmagorinsky is not implemented (SmagorinskyLilly is)")
+
+
+class AnisotropicMinimumDissipation:
+    """Named so that asking for it says what is missing."""
+
+    def __init__(self, *a, **kw):
+        raise NotImplementedError("AnisotropicMinimumDissipation is not implemented (SmagorinskyLilly is)")

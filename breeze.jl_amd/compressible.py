@@ -289,7 +289,9 @@ _ALIASES = {"θ": "θ", "theta": "θ", "θˡⁱ": "θ", "θli": "θ", "ρ": "ρ"
 class CompressibleAtmosphereModel:
     """AtmosphereModel(grid; dynamics=CompressibleDynamics(SplitExplicitTimeDiscretization(...)), advection=WENO(order=5))
     — timestepper :AcousticRungeKutta3; coriolis = FPlane(f) and density-keyed Relaxation sponges on ρu, ρv, ρw, ρθ
-    (examples/tropical_cyclone_with_rainband.jl:434-514) are the forcing terms built; closure = nothing."""
+    (examples/tropical_cyclone_with_rainband.jl:434-514) are the forcing terms built; closure = SmagorinskyLilly(), ScalarDiffusivity(ν, κ)
+    or VerticalScalarDiffusivity(ν, κ) with the explicit time discretisation (benchmarking/run_benchmarks.jl:111-119;
+    validation/DCMIP2016_TC/dcmip2016_tc.jl:277-292) on single-GPU models that are periodic in x and y."""
 
     def __init__(self, grid, dynamics, advection=None, thermodynamic_constants=None, temperature_solver=None,
                  closure=None, coriolis=None, microphysics=None, forcing=None, device="cuda:0", substep_floattype=None,
@@ -323,8 +325,25 @@ class CompressibleAtmosphereModel:
                 raise NotImplementedError("bounds-preserving WENO is implemented for order 5")
         if not isinstance(dynamics, CompressibleDynamics):
             raise TypeError("dynamics must be CompressibleDynamics")
+        from .closures import ScalarDiffusivity
+        from .forcings import SmagorinskyLilly
+        if isinstance(closure, (tuple, list)):
+            raise NotImplementedError("closure: one closure is implemented (no closure tuples)")
         if closure is not None:
-            raise NotImplementedError("closure is outside the hot-path scope of this build")
+            if not isinstance(closure, (SmagorinskyLilly, ScalarDiffusivity)):
+                raise NotImplementedError(f"closure = {type(closure).__name__}: SmagorinskyLilly(), ScalarDiffusivity(...) and "
+                                          "VerticalScalarDiffusivity(...) are implemented")
+            if isinstance(closure, ScalarDiffusivity) and closure.vertically_implicit:
+                raise NotImplementedError("closure with VerticallyImplicitTimeDiscretization: CompressibleDynamics runs the closures with "
+                                          "ExplicitTimeDiscretization (the implicit substep of the reference is not built)")
+            if self.lateral_walls:
+                raise NotImplementedError("closure: not implemented on a compressible model between walls (Bounded x / Bounded y)")
+            if Flat in grid.topology:
+                raise NotImplementedError("closure: not implemented on a compressible model with a Flat y")
+            if type(self) is not CompressibleAtmosphereModel:
+                raise NotImplementedError("closure: not implemented on y-slab (distributed) compressible models")
+        self.closure = closure
+        self._diffusivity = isinstance(closure, ScalarDiffusivity)
         from .forcings import FPlane, split_relaxation
         if coriolis is not None and not isinstance(coriolis, FPlane):
             raise NotImplementedError("coriolis: FPlane is implemented")
@@ -470,6 +489,22 @@ class CompressibleAtmosphereModel:
         self.thermodynamic_forcing_field, _spec = materialize_field_forcing(grid, self._field_forcing, "LiquidIcePotentialTemperature", self.device)
         if self.thermodynamic_forcing_field is not None:
             self._check(lib.bz_set_field_forcing(self._ctx, C.c_void_p(self.thermodynamic_forcing_field.ptr()), _spec), "bz_set_field_forcing")
+        self.closure_fields = {}
+        if self._diffusivity:      # no closure fields: ν and κ are numbers or the user's own centre fields (dcmip2016_tc.jl:277-292)
+            Kf = {}
+            for name, value in (("ν", closure.ν), ("κ", closure.κ)):
+                if isinstance(value, Field):
+                    if value.grid is not grid or value.parent.device != self.device or value.parent.dtype != self.potential_temperature.parent.dtype:
+                        raise ValueError(f"closure {name}: the field must live on the model's grid, device and float type")
+                    Kf[name] = value
+            sd = T.bz_scalar_diffusivity(closure.formulation, 0, 0.0 if "ν" in Kf else closure.ν, 0.0 if "κ" in Kf else closure.κ)
+            self._diffusivity_fields = Kf      # keeps the arrays the context reads alive
+            self._check(lib.bz_set_scalar_diffusivity(self._ctx, C.byref(sd), C.c_void_p(Kf["ν"].ptr() if "ν" in Kf else None),
+                                                      C.c_void_p(Kf["κ"].ptr() if "κ" in Kf else None)), "bz_set_scalar_diffusivity")
+        elif closure is not None:      # build_closure_fields: νₑ (atmosphere_model.jl:276)
+            self.closure_fields = {"νₑ": fld("ccc")}
+            cl = T.bz_smagorinsky_lilly(closure.C, closure.Cb, closure.Pr)
+            self._check(lib.bz_set_closure(self._ctx, C.byref(cl), C.c_void_p(self.closure_fields["νₑ"].ptr())), "bz_set_closure")
         if self.lateral_walls:      # is_active_open_bc of the four sides (acoustic_substepping.jl:1339-1361)
             bu, bv = self.boundary_conditions.get("ρu"), self.boundary_conditions.get("ρv")
             sides = [is_active_open_bc(getattr(b, k, None)) and grid.topology[d] == Bounded
@@ -570,6 +605,13 @@ def update_state_(model, compute_tendencies=True):
     model._check(model._lib.bz_compressible_update_state(model._ctx, C.byref(model._state), C.byref(model._G),
                                                          C.byref(model._sub), 1 if compute_tendencies else 0),
                  "bz_compressible_update_state")
+
+
+def compute_closure_fields_(model):
+    """compute_closure_fields!(model.closure_fields, model.closure, model) (update_atmosphere_model_state.jl:218) alone; update_state_
+    ends with it."""
+    model._check(model._lib.bz_compressible_compute_closure_fields(model._ctx, C.byref(model._state)),
+                 "bz_compressible_compute_closure_fields")
 
 
 def refresh_linearization_(model):

@@ -13,7 +13,10 @@
 // Two kernels: the eddy viscosity (one centre array), then one pass that adds the five divergences to the tendencies.  Every
 // flux is recomputed by the two cells that share it instead of being stored: 9 stress + 6 scalar-flux arrays would cost
 // 30 words/cell of traffic, the recomputation reads u, v, w, nu, theta, q through L2 (7 words/cell) and is arithmetic otherwise.
-#include "bz_internal.h"
+#include <cstring>
+
+#include "bz_closure_carriers.h"
+#include "bz_compressible_internal.h"
 
 struct ClosureFields {
     const double *u, *v, *w, *nu, *theta, *q;
@@ -54,19 +57,21 @@ __device__ __forceinline__ void xcd_block(int &bx, int &by, int &bz)
     bz = b / (gridDim.x * gridDim.y);
 }
 
-// ipi[k] = (pst / p_r[k])^(Rd/cpd), k = -1 .. Nz (k_inverse_exner_column): the only pow of the buoyancy gradient depends on k alone
-__device__ __forceinline__ double log_theta_v(const DevGrid &g, const double *ipi, const double *T, const double *qv, long long n, int k)
+// anelastic: ipi[k] = (pst / p_r[k])^(Rd/cpd), k = -1 .. Nz (k_inverse_exner_column): the only pow of the buoyancy gradient depends on k
+// alone; compressible: the pow of the cell's own pressure (bz_closure_carriers.h)
+template <class PI>
+__device__ __forceinline__ double log_theta_v(const DevGrid &g, const PI &Pi, const double *T, const double *qv, long long n, int k)
 {
     const double q = qv[n];
     const double Rm = (1.0 - (q + 0.0 + 0.0)) * g.Rd + q * g.Rv;
-    return log(Rm / g.Rd * T[n] * ipi[k]);
+    return log(Rm / g.Rd * T[n] * Pi.at(g, n, k));
 }
 
 // ... and so does the filter width: delta2[k] = cbrt(dx dy dz_k)^2 (round 2 evaluated cbrt per cell)
-__global__ void k_inverse_exner_column(DevGrid g, double *ipi, double *delta2)
+__global__ void k_inverse_exner_column(DevGrid g, double *ipi, double *delta2, int with_ipi)
 {
     for (int k = (int)threadIdx.x - 1; k <= g.Nz; k += blockDim.x) {
-        ipi[k] = pow(g.pst / g.p_r[k], g.Rd / g.cpd);
+        if (with_ipi) ipi[k] = pow(g.pst / g.p_r[k], g.Rd / g.cpd);      // (compressible contexts read the 3-D pressure instead)
         if (k < 0 || k >= g.Nz) continue;
         const double delta = cbrt(g.dx * g.dy * g.dzc[k]);
         delta2[k] = delta * delta;
@@ -76,13 +81,16 @@ __global__ void k_inverse_exner_column(DevGrid g, double *ipi, double *delta2)
 // A workgroup walks `kchunk` levels of its row: log(theta_v) of a cell enters N^2 of three levels, and the march evaluates it once (ring of
 // three) instead of three times — the logarithm is the most expensive thing in this kernel.
 #define SMAG_KCHUNK 1      // 8 measured slower (0.36 -> 0.46 ms at 256x256x128 Float32): the strain loads bound this kernel, not the logarithms
+template <class PI>
 __global__ __launch_bounds__(256) void k_smagorinsky_viscosity(DevGrid g, ClosureFields F, const double *__restrict__ T,
-                                                               const double *__restrict__ qv, const double *__restrict__ ipi,
+                                                               const double *__restrict__ qv, PI ipi,
                                                                const double *__restrict__ delta2, double *__restrict__ nu)
 {
     int bx, by, bz;
     xcd_block(bx, by, bz);
-    const int i = bx * 256 + threadIdx.x, j = by + F.jofs, kbeg = bz * SMAG_KCHUNK, kend = min(kbeg + SMAG_KCHUNK, g.Nz);
+    // levels per workgroup: 1 where the Exner factor is a table entry (SMAG_KCHUNK), 8 where it is a pow of the cell's pressure — the ring then
+    // costs 10 pow + log per 8 cells instead of 3 per cell
+    const int i = bx * 256 + threadIdx.x, j = by + F.jofs, kbeg = bz * PI::kchunk, kend = min(kbeg + PI::kchunk, g.Nz);
     if (i >= g.Nx) return;
     const long long sx = 1, sy = g.Sx, sz = g.Sxy;
     const double *u = F.u, *v = F.v, *w = F.w;
@@ -111,7 +119,11 @@ __global__ __launch_bounds__(256) void k_smagorinsky_viscosity(DevGrid g, Closur
     }
 }
 
-__global__ __launch_bounds__(256) void k_closure_tendencies(DevGrid g, ClosureFields F, double *__restrict__ Gu,
+// RHO: the density of the flux locations (bz_closure_carriers.h).  RhoColumn is the anelastic kernel as it was; RhoField is the slow
+// momentum + rho theta pass of the compressible model (rho_d; the water scalars have the total density and a launch of their own,
+// bz_diffusivity.hip: k_water_closure, so F.q is not read)
+template <class RHO>
+__global__ __launch_bounds__(256) void k_closure_tendencies(DevGrid g, ClosureFields F, RHO R, double *__restrict__ Gu,
                                                             double *__restrict__ Gv, double *__restrict__ Gw,
                                                             double *__restrict__ Gth, double *__restrict__ Gq, double scale)
 {
@@ -123,7 +135,6 @@ __global__ __launch_bounds__(256) void k_closure_tendencies(DevGrid g, ClosureFi
     const double *u = F.u, *v = F.v, *w = F.w, *nu = F.nu;
     const double dx = g.dx, dy = g.dy, dz = g.dzc[k];
     const double rVc = g.rdx * (1.0 / dy) * g.rdzc[k];      // not g.rdy: that is the derivative quotient, stored as 0 on Flat grids
-    const double rho = g.rho[k];
     const double Ax = dy * dz, Ay = dx * dz, Az = dx * dy;
     // eddy viscosity of the 3 x 3 x 3 neighbourhood that the flux locations of this cell touch
     double nun[3][3][3];      // [dk+1][dj+1][di+1]; the 8 corners are never used
@@ -152,12 +163,12 @@ __global__ __launch_bounds__(256) void k_closure_tendencies(DevGrid g, ClosureFi
     auto nu_cff = [&](int dj, int dk) {      // y face j + dj, z face k + dk, column i
         return ((NU(0, dj - 1, dk - 1) + NU(0, dj, dk - 1)) / 2 + (NU(0, dj - 1, dk) + NU(0, dj, dk)) / 2) / 2;
     };
-    auto T11 = [&](int di) { return rho * (-2 * NU(di, 0, 0) * S11(g, u, n + di * sx)); };
-    auto T22 = [&](int dj) { return rho * (-2 * NU(0, dj, 0) * S22(g, v, n + dj * sy)); };
-    auto T33 = [&](int dk) { return g.rho[k + dk] * (-2 * NU(0, 0, dk) * S33(g, w, n + dk * sz, k + dk)); };
-    auto T12 = [&](int di, int dj) { return rho * (-2 * nu_ffc(di, dj) * S12(g, u, v, n + di * sx + dj * sy)); };
-    auto T13 = [&](int di, int dk) { return g.rho_f[k + dk] * (-2 * nu_fcf(di, dk) * S13(g, u, w, n + di * sx + dk * sz, k + dk)); };
-    auto T23 = [&](int dj, int dk) { return g.rho_f[k + dk] * (-2 * nu_cff(dj, dk) * S23(g, v, w, n + dj * sy + dk * sz, k + dk)); };
+    auto T11 = [&](int di) { return R.ccc(g, n + di * sx, k) * (-2 * NU(di, 0, 0) * S11(g, u, n + di * sx)); };
+    auto T22 = [&](int dj) { return R.ccc(g, n + dj * sy, k) * (-2 * NU(0, dj, 0) * S22(g, v, n + dj * sy)); };
+    auto T33 = [&](int dk) { return R.ccc(g, n + dk * sz, k + dk) * (-2 * NU(0, 0, dk) * S33(g, w, n + dk * sz, k + dk)); };
+    auto T12 = [&](int di, int dj) { return R.ffc(g, n + di * sx + dj * sy, k) * (-2 * nu_ffc(di, dj) * S12(g, u, v, n + di * sx + dj * sy)); };
+    auto T13 = [&](int di, int dk) { return R.fcf(g, n + di * sx + dk * sz, k + dk) * (-2 * nu_fcf(di, dk) * S13(g, u, w, n + di * sx + dk * sz, k + dk)); };
+    auto T23 = [&](int dj, int dk) { return R.cff(g, n + dj * sy + dk * sz, k + dk) * (-2 * nu_cff(dj, dk) * S23(g, v, w, n + dj * sy + dk * sz, k + dk)); };
 
     const double t12_00 = T12(0, 0), t13_00 = T13(0, 0), t23_00 = T23(0, 0);
     if (!(g.bounded_x && i == 0)) {   // x momentum at face i (walls in x: the wall face is never updated)
@@ -180,19 +191,20 @@ __global__ __launch_bounds__(256) void k_closure_tendencies(DevGrid g, ClosureFi
     const double kxm = (NU(-1, 0, 0) * rPr + kc) / 2, kxp = (kc + NU(1, 0, 0) * rPr) / 2;
     const double kym = (NU(0, -1, 0) * rPr + kc) / 2, kyp = (kc + NU(0, 1, 0) * rPr) / 2;
     const double kzm = (NU(0, 0, -1) * rPr + kc) / 2, kzp = (kc + NU(0, 0, 1) * rPr) / 2;
-    const double rfm = g.rho_f[k], rfp = g.rho_f[k + 1];
+    const double rxm = R.fcc(g, n, k), rxp = R.fcc(g, n + sx, k), rym = R.cfc(g, n, k), ryp = R.cfc(g, n + sy, k);
+    const double rfm = R.ccf(g, n, k), rfp = R.ccf(g, n + sz, k + 1);
     const double rdzfm = g.rdzf[k], rdzfp = g.rdzf[k + 1];
     auto scalar = [&](const double *c, double *G) {
         const double c0 = c[n];
-        const double Jxm = rho * (-kxm * ((c0 - c[n - sx]) * g.rdx)), Jxp = rho * (-kxp * ((c[n + sx] - c0) * g.rdx));
-        const double Jym = rho * (-kym * ((c0 - c[n - sy]) * g.rdy)), Jyp = rho * (-kyp * ((c[n + sy] - c0) * g.rdy));
+        const double Jxm = rxm * (-kxm * ((c0 - c[n - sx]) * g.rdx)), Jxp = rxp * (-kxp * ((c[n + sx] - c0) * g.rdx));
+        const double Jym = rym * (-kym * ((c0 - c[n - sy]) * g.rdy)), Jyp = ryp * (-kyp * ((c[n + sy] - c0) * g.rdy));
         const double Jzm = (k == 0) ? 0.0 : rfm * (-kzm * ((c0 - c[n - sz]) * rdzfm));
         const double Jzp = (k == g.Nz - 1) ? 0.0 : rfp * (-kzp * ((c[n + sz] - c0) * rdzfp));
         const double div = (Ax * Jxp - Ax * Jxm) + (Ay * Jyp - Ay * Jym) + (Az * Jzp - Az * Jzm);
         G[n] -= scale * (div * rVc);
     };
     scalar(F.theta, Gth);
-    scalar(F.q, Gq);
+    if constexpr (!RHO::field) scalar(F.q, Gq);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -220,20 +232,25 @@ __device__ __forceinline__ void closure_lds_barrier()
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
 }
 
-template <int TY>
-__global__ __launch_bounds__(64 * TY, 4) void k_closure_march(DevGrid g, ClosureFields F, double *__restrict__ Gu, double *__restrict__ Gv,
+// RHO = RhoField (compressible model): the carrier density is a fifth rotating plane with its one-cell frame beside u, v, w, nu, so its
+// face / edge means are LDS reads like those of nu; the moisture is not in this launch (the water scalars carry the total density).
+template <int TY, class RHO>
+__global__ __launch_bounds__(64 * TY, RHO::field ? 2 : 4) void k_closure_march(DevGrid g, ClosureFields F, RHO R, double *__restrict__ Gu, double *__restrict__ Gv,
                                                           double *__restrict__ Gw, double *__restrict__ Gth, double *__restrict__ Gq,
                                                           double scale, int kchunk)
 {
     constexpr int TR = TY + 2, TC = 68, NT = 64 * TY;
     constexpr int NF = 2 * 66 + 2 * TY;                  // frame cells of one tile
-    constexpr int NFL = 6 * NF;                          // frame loads per level: u, v, w, nu of level k+2 and theta, q of level k+1
+    constexpr bool RF = RHO::field;
+    constexpr int NF3 = RF ? 5 : 4;                      // fields with three level slots: u, v, w, nu [, rho]
+    constexpr int NF1 = RF ? 1 : 2;                      // one slot: theta [, q]
+    constexpr int NFL = (NF3 + NF1) * NF;                // frame loads per level: the three-slot fields of level k+2, theta [, q] of level k+1
     constexpr int HPT = (NFL + NT - 1) / NT;
     constexpr int TS = TR * TC;                          // one tile
-    __shared__ double S[14 * TS];                        // u, v, w, nu: three level slots each; theta, q: one
+    __shared__ double S[(3 * NF3 + NF1) * TS];
     double (*U)[TR][TC] = (double (*)[TR][TC])(S), (*V)[TR][TC] = (double (*)[TR][TC])(S + 3 * TS), (*W)[TR][TC] = (double (*)[TR][TC])(S + 6 * TS),
-           (*NUt)[TR][TC] = (double (*)[TR][TC])(S + 9 * TS);
-    double (*TH)[TC] = (double (*)[TC])(S + 12 * TS), (*Q)[TC] = (double (*)[TC])(S + 13 * TS);
+           (*NUt)[TR][TC] = (double (*)[TR][TC])(S + 9 * TS), (*RHt)[TR][TC] = (double (*)[TR][TC])(S + 12 * TS);      // RHt: RF only
+    double (*TH)[TC] = (double (*)[TC])(S + 3 * NF3 * TS), (*Q)[TC] = (double (*)[TC])(S + (3 * NF3 + 1) * TS);      // Q: !RF only
     int bx, by, bz;
     xcd_block(bx, by, bz);
     const int tx = threadIdx.x, ty = threadIdx.y, t = ty * 64 + tx;
@@ -242,7 +259,8 @@ __global__ __launch_bounds__(64 * TY, 4) void k_closure_march(DevGrid g, Closure
     if (kbeg >= kend) return;
     const long long sy = g.Sx, sz = g.Sxy;
     const double *__restrict__ u = F.u, *__restrict__ v = F.v, *__restrict__ w = F.w, *__restrict__ nu = F.nu;
-    const double *__restrict__ th = F.theta, *__restrict__ q = F.q;
+    const double *__restrict__ th = F.theta, *__restrict__ q = RF ? F.theta : F.q;      // (RF: q is never read; a valid pointer for the dead loads)
+    const double *__restrict__ rho3 = [&]() -> const double * { if constexpr (RF) return R.r; else return nullptr; }();
     const int r = ty + 1, c = tx + 1;
     // level l of a z-face field / centre field sits in slot (l - kbeg + 1) % 3; nu beyond the walls mirrors the wall level (no-flux)
     auto nu_level = [&](int l) { return min(max(l, 0), g.Nz - 1); };
@@ -262,20 +280,22 @@ __global__ __launch_bounds__(64 * TY, 4) void k_closure_march(DevGrid g, Closure
         int rr, cc;
         if (cell < 132) { rr = (cell < 66) ? 0 : TR - 1; cc = (cell < 66) ? cell : cell - 66; }
         else { const int m = cell - 132; rr = 1 + (m >> 1); cc = (m & 1) ? 65 : 0; }
-        hf[qq] = f; hoff[qq] = (f < 4 ? 3 * f : 8 + f) * TS + rr * TC + cc;
+        hf[qq] = f; hoff[qq] = (f < NF3 ? 3 * f : 2 * NF3 + f) * TS + rr * TC + cc;
         const int ii = i0 - 1 + cc, jj = j0 - 1 + rr;
         hn[qq] = (f == 3) ? g.idx(nu_col(ii), nu_row(jj), 0) : g.idx(ii, jj, 0);
     }
-    auto frame_src = [&](int f) -> const double * { return f == 0 ? u : f == 1 ? v : f == 2 ? w : f == 3 ? nu : f == 4 ? th : q; };
+    auto frame_src = [&](int f) -> const double * {
+        return f == 0 ? u : f == 1 ? v : f == 2 ? w : f == 3 ? nu : (RF && f == 4) ? rho3 : f == NF3 ? th : q;
+    };
     // level a frame load of field f fetches while the compute of level k runs: k + 2 (u, v, w, nu), k + 1 (theta, q)
     auto frame_load = [&](int qq, int k) -> double {
         const int f = hf[qq];
-        const int l = (f < 4) ? k + 2 : k + 1;
+        const int l = (f < NF3) ? k + 2 : k + 1;
         return frame_src(f)[hn[qq] + (long long)(f == 3 ? nu_level(l) : l) * sz];
     };
     auto frame_store = [&](int qq, int k, double val) {
         const int sl = (k + 2 - kbeg + 1) % 3;
-        S[hoff[qq] + (hf[qq] < 4 ? sl * TS : 0)] = val;
+        S[hoff[qq] + (hf[qq] < NF3 ? sl * TS : 0)] = val;
     };
     // ---- prologue: levels kbeg-1, kbeg, kbeg+1 of u, v, w, nu and level kbeg of theta, q ----
     for (int l = kbeg - 1; l <= kbeg + 1; ++l) {
@@ -283,16 +303,18 @@ __global__ __launch_bounds__(64 * TY, 4) void k_closure_march(DevGrid g, Closure
         const long long n = n0 + (long long)l * sz;
         U[sl][r][c] = u[n]; V[sl][r][c] = v[n]; W[sl][r][c] = w[n];
         NUt[sl][r][c] = nu[n0 + (long long)nu_level(l) * sz];
+        if constexpr (RF) RHt[sl][r][c] = rho3[n];
 #pragma unroll
         for (int qq = 0; qq < HPT; ++qq)
-            if (hok[qq] && hf[qq] < 4) frame_store(qq, l - 2, frame_load(qq, l - 2));
+            if (hok[qq] && hf[qq] < NF3) frame_store(qq, l - 2, frame_load(qq, l - 2));
     }
     double th_m = th[n0 + (long long)(kbeg - 1) * sz], th_c = th[n0 + (long long)kbeg * sz], th_p = th[n0 + (long long)(kbeg + 1) * sz];
     double q_m = q[n0 + (long long)(kbeg - 1) * sz], q_c = q[n0 + (long long)kbeg * sz], q_p = q[n0 + (long long)(kbeg + 1) * sz];
-    TH[r][c] = th_c; Q[r][c] = q_c;
+    TH[r][c] = th_c;
+    if constexpr (!RF) Q[r][c] = q_c;
 #pragma unroll
     for (int qq = 0; qq < HPT; ++qq)
-        if (hok[qq] && hf[qq] >= 4) frame_store(qq, kbeg - 1, frame_load(qq, kbeg - 1));
+        if (hok[qq] && hf[qq] >= NF3) frame_store(qq, kbeg - 1, frame_load(qq, kbeg - 1));
     __syncthreads();
 
     const double dx = g.dx, dy = g.dy;
@@ -304,13 +326,14 @@ __global__ __launch_bounds__(64 * TY, 4) void k_closure_march(DevGrid g, Closure
         const long long n2 = n + 2 * sz;
         const double pu = u[n2], pv = v[n2], pw = w[n2], pnu = nu[n0 + (long long)nu_level(k + 2) * sz];
         const double pth = th[n2], pq = q[n2];
+        double prho = 0.0;
+        if constexpr (RF) prho = rho3[n2];
         double hnext[HPT];
 #pragma unroll
         for (int qq = 0; qq < HPT; ++qq) hnext[qq] = (hok[qq] && !(CL_KO & 2)) ? frame_load(qq, k) : 0.0;
 
         const double dz = g.dzc[k];
         const double rVc = g.rdx * (1.0 / dy) * g.rdzc[k];
-        const double rho = g.rho[k];
         const double Ax = dy * dz, Ay = dx * dz, Az = dx * dy;
         auto Uc = [&](int di, int dj, int dk) { return U[dk < 0 ? sm : dk > 0 ? sp : sc][r + dj][c + di]; };
         auto Vc = [&](int di, int dj, int dk) { return V[dk < 0 ? sm : dk > 0 ? sp : sc][r + dj][c + di]; };
@@ -334,13 +357,25 @@ __global__ __launch_bounds__(64 * TY, 4) void k_closure_march(DevGrid g, Closure
         auto nu_ffc = [&](int di, int dj) { return ((NU(di - 1, dj - 1, 0) + NU(di, dj - 1, 0)) / 2 + (NU(di - 1, dj, 0) + NU(di, dj, 0)) / 2) / 2; };
         auto nu_fcf = [&](int di, int dk) { return ((NU(di - 1, 0, dk - 1) + NU(di, 0, dk - 1)) / 2 + (NU(di - 1, 0, dk) + NU(di, 0, dk)) / 2) / 2; };
         auto nu_cff = [&](int dj, int dk) { return ((NU(0, dj - 1, dk - 1) + NU(0, dj, dk - 1)) / 2 + (NU(0, dj - 1, dk) + NU(0, dj, dk)) / 2) / 2; };
-        auto T11 = [&](int di) { return rho * (-2 * NU(di, 0, 0) * s11(di)); };
-        auto T22 = [&](int dj) { return rho * (-2 * NU(0, dj, 0) * s22(dj)); };
-        auto T33 = [&](int dk) { return g.rho[k + dk] * (-2 * NU(0, 0, dk) * s33(dk)); };
-        auto T12 = [&](int di, int dj) { return rho * (-2 * nu_ffc(di, dj) * s12(di, dj)); };
+        // the density of the flux locations: the reference column, or the means of the rho tile in the order of RhoField (bz_closure_carriers.h)
+        auto RH = [&](int di, int dj, int dk) { return RHt[dk < 0 ? sm : dk > 0 ? sp : sc][r + dj][c + di]; };
+        auto r_ccc = [&](int di, int dj, int dk) { if constexpr (RF) return RH(di, dj, dk); else return g.rho[k + dk]; };
+        auto r_ffc = [&](int di, int dj) {
+            if constexpr (RF) return ((RH(di - 1, dj - 1, 0) + RH(di, dj - 1, 0)) / 2 + (RH(di - 1, dj, 0) + RH(di, dj, 0)) / 2) / 2; else return g.rho[k];
+        };
+        auto r_fcf = [&](int di, int dk) {
+            if constexpr (RF) return ((RH(di - 1, 0, dk - 1) + RH(di, 0, dk - 1)) / 2 + (RH(di - 1, 0, dk) + RH(di, 0, dk)) / 2) / 2; else return g.rho_f[k + dk];
+        };
+        auto r_cff = [&](int dj, int dk) {
+            if constexpr (RF) return ((RH(0, dj - 1, dk - 1) + RH(0, dj, dk - 1)) / 2 + (RH(0, dj - 1, dk) + RH(0, dj, dk)) / 2) / 2; else return g.rho_f[k + dk];
+        };
+        auto T11 = [&](int di) { return r_ccc(di, 0, 0) * (-2 * NU(di, 0, 0) * s11(di)); };
+        auto T22 = [&](int dj) { return r_ccc(0, dj, 0) * (-2 * NU(0, dj, 0) * s22(dj)); };
+        auto T33 = [&](int dk) { return r_ccc(0, 0, dk) * (-2 * NU(0, 0, dk) * s33(dk)); };
+        auto T12 = [&](int di, int dj) { return r_ffc(di, dj) * (-2 * nu_ffc(di, dj) * s12(di, dj)); };
         // (dk = 1 needs nu of level k+1 and k: nu_fcf / nu_cff with dk - 1 = 0, dk = 1; dk = 0 needs k-1 and k)
-        auto T13 = [&](int di, int dk) { return g.rho_f[k + dk] * (-2 * nu_fcf(di, dk) * s13(di, dk)); };
-        auto T23 = [&](int dj, int dk) { return g.rho_f[k + dk] * (-2 * nu_cff(dj, dk) * s23(dj, dk)); };
+        auto T13 = [&](int di, int dk) { return r_fcf(di, dk) * (-2 * nu_fcf(di, dk) * s13(di, dk)); };
+        auto T23 = [&](int dj, int dk) { return r_cff(dj, dk) * (-2 * nu_cff(dj, dk) * s23(dj, dk)); };
 
         const double t12_00 = T12(0, 0), t13_00 = T13(0, 0), t23_00 = T23(0, 0);
         {
@@ -361,22 +396,32 @@ __global__ __launch_bounds__(64 * TY, 4) void k_closure_march(DevGrid g, Closure
         const double kxm = (NU(-1, 0, 0) * rPr + kc) / 2, kxp = (kc + NU(1, 0, 0) * rPr) / 2;
         const double kym = (NU(0, -1, 0) * rPr + kc) / 2, kyp = (kc + NU(0, 1, 0) * rPr) / 2;
         const double kzm = (NU(0, 0, -1) * rPr + kc) / 2, kzp = (kc + NU(0, 0, 1) * rPr) / 2;
-        const double rfm = g.rho_f[k], rfp = g.rho_f[k + 1];
+        double rxm, rxp, rym, ryp, rfm, rfp;
+        if constexpr (RF) {
+            rxm = (RH(-1, 0, 0) + RH(0, 0, 0)) / 2; rxp = (RH(0, 0, 0) + RH(1, 0, 0)) / 2;
+            rym = (RH(0, -1, 0) + RH(0, 0, 0)) / 2; ryp = (RH(0, 0, 0) + RH(0, 1, 0)) / 2;
+            rfm = (RH(0, 0, -1) + RH(0, 0, 0)) / 2; rfp = (RH(0, 0, 0) + RH(0, 0, 1)) / 2;
+        } else {
+            rxm = rxp = rym = ryp = g.rho[k];
+            rfm = g.rho_f[k]; rfp = g.rho_f[k + 1];
+        }
         const double rdzfm = g.rdzf[k], rdzfp = g.rdzf[k + 1];
         auto scalar = [&](const double (*Tl)[TC], double c0, double cm, double cp, double *G) {
-            const double Jxm = rho * (-kxm * ((c0 - Tl[r][c - 1]) * g.rdx)), Jxp = rho * (-kxp * ((Tl[r][c + 1] - c0) * g.rdx));
-            const double Jym = rho * (-kym * ((c0 - Tl[r - 1][c]) * g.rdy)), Jyp = rho * (-kyp * ((Tl[r + 1][c] - c0) * g.rdy));
+            const double Jxm = rxm * (-kxm * ((c0 - Tl[r][c - 1]) * g.rdx)), Jxp = rxp * (-kxp * ((Tl[r][c + 1] - c0) * g.rdx));
+            const double Jym = rym * (-kym * ((c0 - Tl[r - 1][c]) * g.rdy)), Jyp = ryp * (-kyp * ((Tl[r + 1][c] - c0) * g.rdy));
             const double Jzm = (k == 0) ? 0.0 : rfm * (-kzm * ((c0 - cm) * rdzfm));
             const double Jzp = (k == g.Nz - 1) ? 0.0 : rfp * (-kzp * ((cp - c0) * rdzfp));
             const double div = (Ax * Jxp - Ax * Jxm) + (Ay * Jyp - Ay * Jym) + (Az * Jzp - Az * Jzm);
             if (!(CL_KO & 1)) G[n] -= scale * (div * rVc); else if (div == 1.2345) G[n] = 0.0;
         };
         scalar(TH, th_c, th_m, th_p, Gth);
-        scalar(Q, q_c, q_m, q_p, Gq);
+        if constexpr (!RF) scalar(Q, q_c, q_m, q_p, Gq);
         if (!(CL_KO & 4)) closure_lds_barrier();                           // every wave is done with slot k-1 and with the theta / q tile of level k
         // ---- stage level k+2 into the slot level k-1 leaves, and theta / q of level k+1 ----
         U[sm][r][c] = pu; V[sm][r][c] = pv; W[sm][r][c] = pw; NUt[sm][r][c] = pnu;
-        TH[r][c] = th_p; Q[r][c] = q_p;
+        if constexpr (RF) RHt[sm][r][c] = prho;
+        TH[r][c] = th_p;
+        if constexpr (!RF) Q[r][c] = q_p;
 #pragma unroll
         for (int qq = 0; qq < HPT; ++qq)
             if (hok[qq]) frame_store(qq, k, hnext[qq]);
@@ -389,9 +434,9 @@ __global__ __launch_bounds__(64 * TY, 4) void k_closure_march(DevGrid g, Closure
 // The eddy viscosity the same way (round 5): u, v, w tiles of the levels k-1, k, k+1 in LDS (one-cell frame, three rotating slots), the
 // logarithms of theta_v of the own column in a ring of three — one per level instead of three.  Same expressions as
 // k_smagorinsky_viscosity, which stays for walls, Flat y, ragged grids and the two rows beyond a y-slab.
-template <int TY>
+template <int TY, class PI>
 __global__ __launch_bounds__(64 * TY, 4) void k_smagorinsky_march(DevGrid g, ClosureFields F, const double *__restrict__ T,
-                                                                  const double *__restrict__ qv, const double *__restrict__ ipi,
+                                                                  const double *__restrict__ qv, PI ipi,
                                                                   const double *__restrict__ delta2, double *__restrict__ nu, int kchunk)
 {
     constexpr int TR = TY + 2, TC = 68, NT = 64 * TY, TS = TR * TC;
@@ -464,7 +509,7 @@ __global__ __launch_bounds__(64 * TY, 4) void k_smagorinsky_march(DevGrid g, Clo
         const double a23 = ((sq(s23(0, 0)) + sq(s23(1, 0))) / 2 + (sq(s23(0, 1)) + sq(s23(1, 1))) / 2) / 2;
         const double Sig2 = (s11 * s11 + s22 * s22 + s33 * s33) + 2 * a12 + 2 * a13 + 2 * a23;
         const double Rm = (1.0 - (qp + 0.0 + 0.0)) * g.Rd + qp * g.Rv;
-        const double lp = log(Rm / g.Rd * Tp * ipi[k + 1]);
+        const double lp = log(Rm / g.Rd * Tp * ipi.at(g, n + sz, k + 1));
         const double bdn = g.g * ((lc - lm) * g.rdzf[k]), bup = g.g * ((lp - lc) * g.rdzf[k + 1]);
         const double N2 = (bdn + bup) / 2;
         const double N2p = fmax(0.0, N2);
@@ -518,7 +563,11 @@ extern "C" int bz_set_closure(bz_ctx *ctx, const bz_smagorinsky_lilly *closure, 
         ctx->last_error = "bz_set_closure: a ScalarDiffusivity closure is attached (bz_set_scalar_diffusivity): one closure per context";
         return BZ_ERR_UNSUPPORTED;
     }
-    if (ctx->compressible || ctx->dg.formulation != 0 || ctx->dg.microphysics == 2) {      // y-slab contexts: through the library-owned distributed step (bz_comm.hip)
+    if (ctx->compressible) {      // the split-explicit model on one device, periodic in x and y (DESIGN: "Closures on the compressible model")
+        const char *what = ctx->slab_mode ? "a y-slab context" : (ctx->dg.bounded_x || ctx->dg.bounded_y) ? "a Bounded x or y (lateral walls)"
+                           : ctx->dg.flat_y ? "a Flat y" : nullptr;
+        if (what) { ctx->last_error = std::string("bz_set_closure: SmagorinskyLilly on a compressible context is not implemented on ") + what; return BZ_ERR_UNSUPPORTED; }
+    } else if (ctx->dg.formulation != 0 || ctx->dg.microphysics == 2) {      // y-slab contexts: through the library-owned distributed step (bz_comm.hip)
         ctx->last_error = "bz_set_closure: SmagorinskyLilly is implemented for the anelastic "
                           "potential-temperature model (microphysics nothing or SaturationAdjustment)";
         return BZ_ERR_UNSUPPORTED;
@@ -527,7 +576,8 @@ extern "C" int bz_set_closure(bz_ctx *ctx, const bz_smagorinsky_lilly *closure, 
     ctx->closure = *closure;
     ctx->closure_nu = eddy_viscosity;
     if (!ctx->d_closure_ipi) BZ_HIP(hipMalloc(&ctx->d_closure_ipi, (size_t)2 * (ctx->dg.Nz + 2) * sizeof(double)));      // ipi, delta2: Nz + 2 entries each
-    hipLaunchKernelGGL(k_inverse_exner_column, dim3(1), dim3(256), 0, ctx->stream, ctx->dg, ctx->d_closure_ipi + 1, ctx->d_closure_ipi + (ctx->dg.Nz + 2) + 1);
+    hipLaunchKernelGGL(k_inverse_exner_column, dim3(1), dim3(256), 0, ctx->stream, ctx->dg, ctx->d_closure_ipi + 1, ctx->d_closure_ipi + (ctx->dg.Nz + 2) + 1,
+                       ctx->compressible ? 0 : 1);
     BZ_LAUNCH_CHECK();
     ctx->has_closure = true;
     return BZ_OK;
@@ -560,7 +610,8 @@ extern "C" int bz_compute_closure_fields(bz_ctx *ctx, const bz_state *s)
     constexpr int CTY = 8;
     const bool march = !ctx->tune.no_closure_march && !g.flat_y && !g.bounded_x && !g.bounded_y && g.Nx % 64 == 0 && g.Ny % CTY == 0 && g.Nz >= 4 &&
                        g.Hx >= 1 && g.Hy >= 1 && g.Hz >= 2;
-    const double *ipi = ctx->d_closure_ipi + 1, *delta2 = ctx->d_closure_ipi + (g.Nz + 2) + 1;
+    const double *delta2 = ctx->d_closure_ipi + (g.Nz + 2) + 1;
+    const ExnerColumn ipi{ctx->d_closure_ipi + 1};
     if (march) {
         const long long tiles = (long long)(g.Nx / 64) * (g.Ny / CTY);
         int nch = (int)((CL_NCH + tiles - 1) / tiles);
@@ -568,17 +619,17 @@ extern "C" int bz_compute_closure_fields(bz_ctx *ctx, const bz_state *s)
         if (nch < 1) nch = 1;
         const int kc = (g.Nz + nch - 1) / nch;
         F.jofs = 0;
-        hipLaunchKernelGGL(k_smagorinsky_march<CTY>, dim3(g.Nx / 64, g.Ny / CTY, (g.Nz + kc - 1) / kc), dim3(64, CTY), 0, ctx->stream, g, F,
+        hipLaunchKernelGGL((k_smagorinsky_march<CTY, ExnerColumn>), dim3(g.Nx / 64, g.Ny / CTY, (g.Nz + kc - 1) / kc), dim3(64, CTY), 0, ctx->stream, g, F,
                            s->T, qv, ipi, delta2, ctx->closure_nu, kc);
         if (ctx->slab_mode) {      // the rows beyond the slab (-1 and Ny), which the tendency kernels read in place of the periodic wrap
             for (int side = 0; side < 2; ++side) {
                 F.jofs = side ? g.Ny : -1;
-                hipLaunchKernelGGL(k_smagorinsky_viscosity, dim3((g.Nx + 255) / 256, 1, (g.Nz + SMAG_KCHUNK - 1) / SMAG_KCHUNK), dim3(256), 0, ctx->stream,
+                hipLaunchKernelGGL(k_smagorinsky_viscosity<ExnerColumn>, dim3((g.Nx + 255) / 256, 1, (g.Nz + SMAG_KCHUNK - 1) / SMAG_KCHUNK), dim3(256), 0, ctx->stream,
                                    g, F, s->T, qv, ipi, delta2, ctx->closure_nu);
             }
         }
     } else
-    hipLaunchKernelGGL(k_smagorinsky_viscosity, dim3((g.Nx + 255) / 256, g.Ny + (ctx->slab_mode ? 2 : 0), (g.Nz + SMAG_KCHUNK - 1) / SMAG_KCHUNK),
+    hipLaunchKernelGGL(k_smagorinsky_viscosity<ExnerColumn>, dim3((g.Nx + 255) / 256, g.Ny + (ctx->slab_mode ? 2 : 0), (g.Nz + SMAG_KCHUNK - 1) / SMAG_KCHUNK),
                        dim3(256), 0, ctx->stream, g, F, s->T, qv, ipi, delta2, ctx->closure_nu);
     BZ_LAUNCH_CHECK();
     // walls in y (or x): nu_e is a centre field with the default no-flux condition — its first halo rows mirror the wall rows (the tendency
@@ -612,11 +663,11 @@ int bzi_apply_closure(bz_ctx *ctx, const bz_state *s, double *Gu, double *Gv, do
         if (nch > g.Nz / 16) nch = g.Nz / 16;
         if (nch < 1) nch = 1;
         const int kc = (g.Nz + nch - 1) / nch;
-        hipLaunchKernelGGL(k_closure_march<CTY>, dim3(g.Nx / 64, g.Ny / CTY, (g.Nz + kc - 1) / kc), dim3(64, CTY), 0, ctx->stream, g,
-                           closure_fields(ctx, s), Gu, Gv, Gw, Gth, Gq, scale, kc);
+        hipLaunchKernelGGL((k_closure_march<CTY, RhoColumn>), dim3(g.Nx / 64, g.Ny / CTY, (g.Nz + kc - 1) / kc), dim3(64, CTY), 0, ctx->stream, g,
+                           closure_fields(ctx, s), RhoColumn(), Gu, Gv, Gw, Gth, Gq, scale, kc);
     } else
-    hipLaunchKernelGGL(k_closure_tendencies, dim3((g.Nx + 255) / 256, g.Ny, g.Nz), dim3(256), 0, ctx->stream, g,
-                       closure_fields(ctx, s), Gu, Gv, Gw, Gth, Gq, scale);
+    hipLaunchKernelGGL(k_closure_tendencies<RhoColumn>, dim3((g.Nx + 255) / 256, g.Ny, g.Nz), dim3(256), 0, ctx->stream, g,
+                       closure_fields(ctx, s), RhoColumn(), Gu, Gv, Gw, Gth, Gq, scale);
     // user tracers diffuse like every other scalar.  The whole-step seam updates rho c in place (bzi_tracer_rk3), so there the
     // divergence goes to the density array with the stage weight, exactly as for rho theta / rho q; per-operator callers pass scale = 1
     // and the tendency arrays
@@ -626,4 +677,79 @@ int bzi_apply_closure(bz_ctx *ctx, const bz_state *s, double *Gu, double *Gv, do
                            (const double *)ctx->tracers[t].specific, (Gth == s->rho_theta) ? ctx->tracers[t].density : ctx->tracers[t].G, scale);
     BZ_LAUNCH_CHECK();
     return BZ_OK;
+}
+
+// ---- CompressibleDynamics + SplitExplicitTimeDiscretization ----------------------------------------------------------------------
+// whole 64 x 8 tiles of a periodic grid: the z-marching LDS-tiled kernels (the rule of the anelastic pair); ragged grids: cell per thread
+constexpr int CMP_CTY = 8;
+static bool cmp_closure_march(const bz_ctx *ctx)
+{
+    const DevGrid &g = ctx->dg;
+    return !ctx->tune.no_closure_march && !g.flat_y && !g.bounded_x && !g.bounded_y && g.Nx % 64 == 0 && g.Ny % CMP_CTY == 0 && g.Nz >= 4 && g.Hx >= 1 &&
+           g.Hy >= 1 && g.Hz >= 2;
+}
+static int closure_march_chunk(const DevGrid &g)      // chunks of >= 16 levels, enough workgroups to fill the chip (bzi_apply_closure)
+{
+    const long long tiles = (long long)(g.Nx / 64) * (g.Ny / CMP_CTY);
+    int nch = (int)((CL_NCH + tiles - 1) / tiles);
+    if (nch > g.Nz / 16) nch = g.Nz / 16;
+    if (nch < 1) nch = 1;
+    return (g.Nz + nch - 1) / nch;
+}
+// compute_closure_fields! at the end of compute_auxiliary_variables! (update_atmosphere_model_state.jl:218): nu_e from the velocities, T and
+// the 3-D pressure the update_state! before it left (halos included), q^v = specific_humidity(model); then the halos of nu_e (periodic in
+// x / y, zero gradient in z), which the water-scalar kernel reads.  ScalarDiffusivity closures have no closure fields: only the halos of a
+// field-valued K.
+int bzi_cmp_closure_fields(bz_ctx *ctx, const bz_compressible_state *s)
+{
+    if (ctx->has_diffusivity) return bzi_diffusivity_halos(ctx);
+    if (!ctx->has_closure) return BZ_OK;
+    const DevGrid &g = ctx->dg;
+    const bool march = cmp_closure_march(ctx);
+    ProfileScope ps(ctx, march ? "smagorinsky_march" : "smagorinsky_viscosity");
+    const double *qv = (g.microphysics == 1) ? g.qv_field : s->q;      // specific_humidity(model): the vapour fraction (Kessler: q is q^v)
+    bz_state a;
+    std::memset(&a, 0, sizeof(a));
+    a.u = s->u; a.v = s->v; a.w = s->w;
+    const ClosureFields F = closure_fields(ctx, &a);
+    const double *delta2 = ctx->d_closure_ipi + (g.Nz + 2) + 1;
+    if (march) {      // whole tiles: the z-marching LDS-tiled kernel, one pow and one log per cell (two more per column and chunk of levels)
+        const int kc = closure_march_chunk(g);
+        hipLaunchKernelGGL((k_smagorinsky_march<CMP_CTY, ExnerField>), dim3(g.Nx / 64, g.Ny / CMP_CTY, (g.Nz + kc - 1) / kc), dim3(64, CMP_CTY), 0, ctx->stream,
+                           g, F, (const double *)s->T, qv, ExnerField{s->p}, delta2, ctx->closure_nu, kc);
+    } else
+    hipLaunchKernelGGL(k_smagorinsky_viscosity<ExnerField>, dim3((g.Nx + 255) / 256, g.Ny, (g.Nz + ExnerField::kchunk - 1) / ExnerField::kchunk), dim3(256), 0,
+                       ctx->stream, g, F, (const double *)s->T, qv, ExnerField{s->p}, delta2, ctx->closure_nu);
+    BZ_LAUNCH_CHECK();
+    return bzi_fill_halo(ctx, ctx->closure_nu, 0);
+}
+
+// - d_j T_ij of the slow momentum tendencies and - div J of the slow rho theta tendency, rho_d at the flux locations, nu_e of the last
+// update_state! (acoustic_substep_helpers.jl:55-93; potential_temperature_tendency.jl:100-105).  G_rho_d gets nothing.
+int bzi_cmp_closure_slow(bz_ctx *ctx, const bz_compressible_state *s, const bz_compressible_prognostic *G)
+{
+    if (ctx->has_diffusivity) return bzi_cmp_diffusivity_slow(ctx, s, G);
+    if (!ctx->has_closure) return BZ_OK;
+    const DevGrid &g = ctx->dg;
+    const bool march = cmp_closure_march(ctx);
+    ProfileScope ps(ctx, march ? "closure_march" : "closure_tendencies");
+    bz_state a;
+    std::memset(&a, 0, sizeof(a));
+    a.u = s->u; a.v = s->v; a.w = s->w; a.theta = s->theta;
+    if (march) {
+        const int kc = closure_march_chunk(g);
+        hipLaunchKernelGGL((k_closure_march<CMP_CTY, RhoField>), dim3(g.Nx / 64, g.Ny / CMP_CTY, (g.Nz + kc - 1) / kc), dim3(64, CMP_CTY), 0, ctx->stream, g,
+                           closure_fields(ctx, &a), RhoField{s->rho_d}, G->rho_u, G->rho_v, G->rho_w, G->rho_theta, (double *)nullptr, 1.0, kc);
+    } else
+    hipLaunchKernelGGL(k_closure_tendencies<RhoField>, dim3((g.Nx + 255) / 256, g.Ny, g.Nz), dim3(256), 0, ctx->stream, g, closure_fields(ctx, &a),
+                       RhoField{s->rho_d}, G->rho_u, G->rho_v, G->rho_w, G->rho_theta, (double *)nullptr, 1.0);
+    BZ_LAUNCH_CHECK();
+    return BZ_OK;
+}
+
+extern "C" int bz_compressible_compute_closure_fields(bz_ctx *ctx, const bz_compressible_state *s)
+{
+    BZ_REQUIRE_COMPRESSIBLE();
+    if (!valid_state(s)) return BZ_ERR_INVALID;
+    return bzi_cmp_closure_fields(ctx, s);
 }

@@ -441,6 +441,9 @@ extern "C" int bz_compute_slow_tendencies(bz_ctx *ctx, const bz_compressible_sta
     // - f x (rho U) of an FPlane and the density-keyed sponges are slow terms too (dynamics_kernel_functions.jl:79,99 through the same
     // x / y_momentum_tendency; examples/tropical_cyclone_with_rainband.jl:434-514)
     if (ctx->has_forcings && (rc = bzi_apply_forcings(ctx, &a, G->rho_u, G->rho_v, G->rho_theta, G->rho_q, 1.0))) return rc;
+    // - d_j T_ij and - div J^theta of the closure, rho_d at the flux locations, between the Coriolis term and the forcings as in
+    // x / y / z_momentum_tendency (dynamics_kernel_functions.jl:77-81; acoustic_substep_helpers.jl:55-93)
+    if ((ctx->has_closure || ctx->has_diffusivity) && (rc = bzi_cmp_closure_slow(ctx, s, G))) return rc;
     return bzi_apply_relaxation(ctx, &a, &Ga, s->rho_d);
 }
 
@@ -452,13 +455,19 @@ extern "C" int bz_compute_moisture_tendency(bz_ctx *ctx, const bz_compressible_s
     BZ_REJECT_Y_WALL_OPTIONS("bz_compute_moisture_tendency");
     if (!valid_state(s) || !valid_prog(G) || !valid_sub(sub)) return BZ_ERR_INVALID;
     // (WENO order 5 kernels; the generic order 7 / 9 path evaluates the field whatever it holds)
+    const int *dry = ctx->weno_R == 3 ? bzi_moisture_state(ctx) : nullptr;
     int rc = launch_scalar_rho3d(ctx, "moisture_tendency", G->rho_q, nullptr, s->rho, sub->time_averaged_u, sub->time_averaged_v,
-                                 sub->time_averaged_w, s->q, nullptr, nullptr, nullptr, ctx->weno_R == 3 ? bzi_moisture_state(ctx) : nullptr);
-    if (rc || ctx->dg.microphysics != 2) return rc;
-    const bz_kessler_model_fields &K = ctx->kessler;      // the Kessler species ride the same transport velocities
-    rc = launch_scalar_rho3d(ctx, "kessler_species_tendencies", K.G_cloud_liquid_density, nullptr, s->rho, sub->time_averaged_u,
-                             sub->time_averaged_v, sub->time_averaged_w, K.cloud_liquid_mass_fraction, nullptr, nullptr, nullptr);
+                                 sub->time_averaged_w, s->q, nullptr, nullptr, nullptr, dry);
     if (rc) return rc;
-    return launch_scalar_rho3d(ctx, "kessler_species_tendencies", K.G_rain_density, nullptr, s->rho, sub->time_averaged_u,
-                               sub->time_averaged_v, sub->time_averaged_w, K.rain_mass_fraction, nullptr, nullptr, nullptr);
+    if (ctx->dg.microphysics == 2) {
+        const bz_kessler_model_fields &K = ctx->kessler;      // the Kessler species ride the same transport velocities
+        rc = launch_scalar_rho3d(ctx, "kessler_species_tendencies", K.G_cloud_liquid_density, nullptr, s->rho, sub->time_averaged_u,
+                                 sub->time_averaged_v, sub->time_averaged_w, K.cloud_liquid_mass_fraction, nullptr, nullptr, nullptr);
+        if (rc) return rc;
+        rc = launch_scalar_rho3d(ctx, "kessler_species_tendencies", K.G_rain_density, nullptr, s->rho, sub->time_averaged_u,
+                                 sub->time_averaged_v, sub->time_averaged_w, K.rain_mass_fraction, nullptr, nullptr, nullptr);
+        if (rc) return rc;
+    }
+    // - div J^c of the closure for every water scalar, the TOTAL density at the faces (scalar_tendency, dynamics_kernel_functions.jl:152-157)
+    return bzi_cmp_water_closure(ctx, s, G, dry);
 }

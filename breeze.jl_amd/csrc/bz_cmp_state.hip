@@ -316,6 +316,12 @@ int bzi_compressible_update_state(bz_ctx *ctx, const bz_compressible_state *s, c
         const int rc = bz_refresh_linearization(ctx, s, sub);
         if (rc) return rc;
     }
+    // compute_closure_fields! closes compute_auxiliary_variables! (update_atmosphere_model_state.jl:218): after velocities, T and p and their
+    // halos, before the tendencies of this update_state!
+    if (ctx->has_closure || ctx->has_diffusivity) {
+        const int rc = bzi_cmp_closure_fields(ctx, s);
+        if (rc) return rc;
+    }
     if (compute_tendencies) return bz_compute_moisture_tendency(ctx, s, G, sub);
     return BZ_OK;
 }
@@ -381,6 +387,7 @@ extern "C" int bz_compressible_kessler_update(bz_ctx *ctx, const bz_compressible
                                               const bz_acoustic_substepper *sub, double dt)
 {
     BZ_REQUIRE_COMPRESSIBLE();
+    BZ_REJECT_WALLS("bz_compressible_kessler_update");
     if (!valid_state(s) || !valid_prog(G) || !valid_sub(sub)) return BZ_ERR_INVALID;
     if (ctx->dg.microphysics != 2) { ctx->last_error = "bz_compressible_kessler_update: no Kessler microphysics attached"; return BZ_ERR_INVALID; }
     const int rc = bzi_kessler_columns(ctx, s->theta, s->rho_theta, s->rho_q, s->rho_d, s->p, dt);

@@ -217,6 +217,9 @@ static int compressible_step_body(bz_ctx *ctx, const bz_compressible_state *s, c
         for (int sstep = 1; sstep <= ntau; ++sstep)
             if ((rc = bzi_acoustic_substep(ctx, s, U0, G, sub, sstep))) return rc;
         if ((rc = bzi_acoustic_stage_end_fused(ctx, s, U0, G, sub, dt, betas[st], st < 2, s_next))) return rc;
+        // compute_closure_fields! of the update_state! the fused epilogue stands for: a launch of its own after it (velocities, T, p and their
+        // halos are final), on the arrays the next stage reads
+        if ((ctx->has_closure || ctx->has_diffusivity) && (rc = bzi_cmp_closure_fields(ctx, s_next))) return rc;
         if ((rc = bz_compute_moisture_tendency(ctx, s_next, G, sub))) return rc;
     }
     s = s_step;

@@ -23,13 +23,20 @@
 // scratch array per field (c' in LDS, 64 columns x Nz words per wave, leaves two waves on a CU at Nz = 128 and one at 256 and measured
 // 6.5 x the table form).  A lane touches its own column only, so the kernel has no barrier.  The modified right-hand side
 // goes through the field in place in both forms ("ScalarDiffusivity": words per cell and field).
-#include "bz_internal.h"
+#include "bz_closure_carriers.h"
+#include "bz_compressible_internal.h"
 
 // K at a cell: the centre field (halos: periodic x / y, zero gradient in z — bzi_diffusivity_halos) or the number
 struct KSource {
     const double *f;
     double c;
     __device__ __forceinline__ double at(long long n) const { return f ? f[n] : c; }
+};
+// kappa = nu_e / Pr of SmagorinskyLilly at a cell (nu_e with its halos filled), for the water scalars of the compressible model
+struct KScaled {
+    const double *f;
+    double mul;
+    __device__ __forceinline__ double at(long long n) const { return f[n] * mul; }
 };
 
 // same block order as bz_closure.hip: every XCD gets a contiguous slab of (row, level / field) space
@@ -47,8 +54,9 @@ __device__ __forceinline__ void dif_xcd_block(int &bx, int &by, int &bz)
 // VERT: the vertical formulation (every x and y flux is zero).  IMPL: the remainder a vertically implicit discretisation leaves explicit.
 // Same expressions and order of operations as k_closure_tendencies (bz_closure.hip) where the two overlap; u, v, w carry periodic halos
 // in x / y, nu its own (bzi_diffusivity_halos).
-template <bool VERT, bool IMPL>
-__global__ __launch_bounds__(256) void k_diffusivity_momentum(DevGrid g, KSource NUs, const double *__restrict__ u, const double *__restrict__ v,
+// RHO: the density of the flux locations (bz_closure_carriers.h): the reference column, or rho_d of the compressible model.
+template <bool VERT, bool IMPL, class RHO>
+__global__ __launch_bounds__(256) void k_diffusivity_momentum(DevGrid g, KSource NUs, RHO R, const double *__restrict__ u, const double *__restrict__ v,
                                                               const double *__restrict__ w, double *__restrict__ Gu, double *__restrict__ Gv,
                                                               double *__restrict__ Gw, double scale)
 {
@@ -59,7 +67,6 @@ __global__ __launch_bounds__(256) void k_diffusivity_momentum(DevGrid g, KSource
     const long long n = g.idx(i, j, k), sx = 1, sy = g.flat_y ? 0 : g.Sx, sz = g.Sxy;      // Flat y: the neighbour rows coincide with the row
     const double dx = g.dx, dy = g.dy, dz = g.dzc[k];
     const double rVc = g.rdx * (1.0 / dy) * g.rdzc[k];
-    const double rho = g.rho[k];
     const double Ax = dy * dz, Ay = dx * dz, Az = dx * dy;
     auto NU = [&](int di, int dj, int dk) { return NUs.at(n + di * sx + dj * sy + dk * sz); };
     auto nu_ffc = [&](int di, int dj) { return ((NU(di - 1, dj - 1, 0) + NU(di, dj - 1, 0)) / 2 + (NU(di - 1, dj, 0) + NU(di, dj, 0)) / 2) / 2; };
@@ -76,23 +83,26 @@ __global__ __launch_bounds__(256) void k_diffusivity_momentum(DevGrid g, KSource
     auto s33 = [&](int dk) { const long long m = n + dk * sz; return (w[m + sz] - w[m]) * g.rdzc[k + dk]; };
     auto s12 = [&](int di, int dj) { const long long m = n + di * sx + dj * sy; return ((u[m] - u[m - sy]) * g.rdy + (v[m] - v[m - 1]) * g.rdx) * 0.5; };
     // horizontal fluxes (isotropic formulation only; the time discretisation does not touch them)
-    auto T11 = [&](int di) { return rho * (-2 * NU(di, 0, 0) * s11(di)); };
-    auto T22 = [&](int dj) { return rho * (-2 * NU(0, dj, 0) * s22(dj)); };
-    auto T12 = [&](int di, int dj) { return rho * (-2 * nu_ffc(di, dj) * s12(di, dj)); };
-    auto Twx = [&](int di) { return g.rho_f[k] * (-2 * nu_fcf(di, 0) * ((dzu(di, 0) + dxw(di, 0)) * 0.5)); };      // x flux of z momentum at (x face i + di, z face k)
-    auto Twy = [&](int dj) { return g.rho_f[k] * (-2 * nu_cff(dj, 0) * ((dzv(dj, 0) + dyw(dj, 0)) * 0.5)); };
+    auto rfcf = [&](int di, int dk) { return R.fcf(g, n + di * sx + dk * sz, k + dk); };      // density at (x face i + di, z face k + dk)
+    auto rcff = [&](int dj, int dk) { return R.cff(g, n + dj * sy + dk * sz, k + dk); };
+    auto rccc = [&](int dk) { return R.ccc(g, n + dk * sz, k + dk); };
+    auto T11 = [&](int di) { return R.ccc(g, n + di * sx, k) * (-2 * NU(di, 0, 0) * s11(di)); };
+    auto T22 = [&](int dj) { return R.ccc(g, n + dj * sy, k) * (-2 * NU(0, dj, 0) * s22(dj)); };
+    auto T12 = [&](int di, int dj) { return R.ffc(g, n + di * sx + dj * sy, k) * (-2 * nu_ffc(di, dj) * s12(di, dj)); };
+    auto Twx = [&](int di) { return rfcf(di, 0) * (-2 * nu_fcf(di, 0) * ((dzu(di, 0) + dxw(di, 0)) * 0.5)); };      // x flux of z momentum at (x face i + di, z face k)
+    auto Twy = [&](int dj) { return rcff(dj, 0) * (-2 * nu_cff(dj, 0) * ((dzv(dj, 0) + dyw(dj, 0)) * 0.5)); };
     // vertical fluxes: what the discretisation leaves explicit
     auto Tuz = [&](int dk) {
-        if (VERT) return IMPL ? 0.0 : g.rho_f[k + dk] * (-nu_fcf(0, dk) * dzu(0, dk));
-        return IMPL ? g.rho_f[k + dk] * (-nu_fcf(0, dk) * dxw(0, dk)) : g.rho_f[k + dk] * (-2 * nu_fcf(0, dk) * ((dzu(0, dk) + dxw(0, dk)) * 0.5));
+        if (VERT) return IMPL ? 0.0 : rfcf(0, dk) * (-nu_fcf(0, dk) * dzu(0, dk));
+        return IMPL ? rfcf(0, dk) * (-nu_fcf(0, dk) * dxw(0, dk)) : rfcf(0, dk) * (-2 * nu_fcf(0, dk) * ((dzu(0, dk) + dxw(0, dk)) * 0.5));
     };
     auto Tvz = [&](int dk) {
-        if (VERT) return IMPL ? 0.0 : g.rho_f[k + dk] * (-nu_cff(0, dk) * dzv(0, dk));
-        return IMPL ? g.rho_f[k + dk] * (-nu_cff(0, dk) * dyw(0, dk)) : g.rho_f[k + dk] * (-2 * nu_cff(0, dk) * ((dzv(0, dk) + dyw(0, dk)) * 0.5));
+        if (VERT) return IMPL ? 0.0 : rcff(0, dk) * (-nu_cff(0, dk) * dzv(0, dk));
+        return IMPL ? rcff(0, dk) * (-nu_cff(0, dk) * dyw(0, dk)) : rcff(0, dk) * (-2 * nu_cff(0, dk) * ((dzv(0, dk) + dyw(0, dk)) * 0.5));
     };
     auto Twz = [&](int dk) {
         if (IMPL) return 0.0;
-        return VERT ? g.rho[k + dk] * (-NU(0, 0, dk) * s33(dk)) : g.rho[k + dk] * (-2 * NU(0, 0, dk) * s33(dk));
+        return VERT ? rccc(dk) * (-NU(0, 0, dk) * s33(dk)) : rccc(dk) * (-2 * NU(0, 0, dk) * s33(dk));
     };
     {
         double div = Az * Tuz(1) - Az * Tuz(0);
@@ -113,34 +123,80 @@ __global__ __launch_bounds__(256) void k_diffusivity_momentum(DevGrid g, KSource
     }
 }
 
-// - div J^c of one scalar: J = rho x (-kappa grad c) with kappa averaged to the face
-template <bool VERT, bool IMPL>
-__global__ __launch_bounds__(256) void k_diffusivity_scalar(DevGrid g, KSource Ks, const double *__restrict__ c, double *__restrict__ G, double scale)
+// - div J^c of NS scalars that share their diffusivity and their density: J = rho x (-kappa grad c) with kappa and rho averaged to the
+// face.  The face coefficients are formed once per cell.  div[q] is the flux divergence times 1 / V of scalar q.
+template <bool VERT, bool IMPL, int NS, class RHO, class KS>
+__device__ __forceinline__ void dif_scalar_divergences(const DevGrid &g, const KS &Ks, const RHO &R, long long n, int k, const double *const (&c)[NS],
+                                                       double (&out)[NS])
+{
+    const long long sy = g.flat_y ? 0 : g.Sx, sz = g.Sxy;
+    const double dx = g.dx, dy = g.dy, dz = g.dzc[k];
+    const double rVc = g.rdx * (1.0 / dy) * g.rdzc[k];
+    const double Ax = dy * dz, Ay = dx * dz, Az = dx * dy;
+    const double kc = Ks.at(n);
+    double kzm = 0.0, kzp = 0.0, rzm = 0.0, rzp = 0.0, kxm = 0.0, kxp = 0.0, kym = 0.0, kyp = 0.0, rxm = 0.0, rxp = 0.0, rym = 0.0, ryp = 0.0;
+    if (!IMPL) {
+        kzm = (Ks.at(n - sz) + kc) / 2; kzp = (kc + Ks.at(n + sz)) / 2;
+        rzm = R.ccf(g, n, k); rzp = R.ccf(g, n + sz, k + 1);
+    }
+    if (!VERT) {
+        kxm = (Ks.at(n - 1) + kc) / 2; kxp = (kc + Ks.at(n + 1)) / 2;
+        kym = (Ks.at(n - sy) + kc) / 2; kyp = (kc + Ks.at(n + sy)) / 2;
+        rxm = R.fcc(g, n, k); rxp = R.fcc(g, n + 1, k); rym = R.cfc(g, n, k); ryp = R.cfc(g, n + sy, k);
+    }
+#pragma unroll
+    for (int q = 0; q < NS; ++q) {
+        const double *__restrict__ cq = c[q];
+        const double c0 = cq[n];
+        double div = 0.0;
+        if (!IMPL) {
+            const double Jzm = (k == 0) ? 0.0 : rzm * (-kzm * ((c0 - cq[n - sz]) * g.rdzf[k]));
+            const double Jzp = (k == g.Nz - 1) ? 0.0 : rzp * (-kzp * ((cq[n + sz] - c0) * g.rdzf[k + 1]));
+            div = Az * Jzp - Az * Jzm;
+        }
+        if (!VERT) {
+            const double Jxm = rxm * (-kxm * ((c0 - cq[n - 1]) * g.rdx)), Jxp = rxp * (-kxp * ((cq[n + 1] - c0) * g.rdx));
+            const double Jym = rym * (-kym * ((c0 - cq[n - sy]) * g.rdy)), Jyp = ryp * (-kyp * ((cq[n + sy] - c0) * g.rdy));
+            div = (Ax * Jxp - Ax * Jxm) + (Ay * Jyp - Ay * Jym) + div;
+        }
+        out[q] = div * rVc;
+    }
+}
+
+template <bool VERT, bool IMPL, class RHO>
+__global__ __launch_bounds__(256) void k_diffusivity_scalar(DevGrid g, KSource Ks, RHO R, const double *__restrict__ c, double *__restrict__ G, double scale)
 {
     int bx, by, bz;
     dif_xcd_block(bx, by, bz);
     const int i = bx * 256 + threadIdx.x, j = by, k = bz;
     if (i >= g.Nx) return;
-    const long long n = g.idx(i, j, k), sy = g.flat_y ? 0 : g.Sx, sz = g.Sxy;
-    const double dx = g.dx, dy = g.dy, dz = g.dzc[k];
-    const double rVc = g.rdx * (1.0 / dy) * g.rdzc[k], rho = g.rho[k];
-    const double Ax = dy * dz, Ay = dx * dz, Az = dx * dy;
-    const double kc = Ks.at(n), c0 = c[n];
-    double div = 0.0;
-    if (!IMPL) {
-        const double kzm = (Ks.at(n - sz) + kc) / 2, kzp = (kc + Ks.at(n + sz)) / 2;
-        const double Jzm = (k == 0) ? 0.0 : g.rho_f[k] * (-kzm * ((c0 - c[n - sz]) * g.rdzf[k]));
-        const double Jzp = (k == g.Nz - 1) ? 0.0 : g.rho_f[k + 1] * (-kzp * ((c[n + sz] - c0) * g.rdzf[k + 1]));
-        div = Az * Jzp - Az * Jzm;
-    }
-    if (!VERT) {
-        const double kxm = (Ks.at(n - 1) + kc) / 2, kxp = (kc + Ks.at(n + 1)) / 2;
-        const double kym = (Ks.at(n - sy) + kc) / 2, kyp = (kc + Ks.at(n + sy)) / 2;
-        const double Jxm = rho * (-kxm * ((c0 - c[n - 1]) * g.rdx)), Jxp = rho * (-kxp * ((c[n + 1] - c0) * g.rdx));
-        const double Jym = rho * (-kym * ((c0 - c[n - sy]) * g.rdy)), Jyp = rho * (-kyp * ((c[n + sy] - c0) * g.rdy));
-        div = (Ax * Jxp - Ax * Jxm) + (Ay * Jyp - Ay * Jym) + div;
-    }
-    G[n] -= scale * (div * rVc);
+    const long long n = g.idx(i, j, k);
+    const double *const cs[1] = {c};
+    double div[1];
+    dif_scalar_divergences<VERT, IMPL, 1>(g, Ks, R, n, k, cs, div);
+    G[n] -= scale * div[0];
+}
+
+// The water scalars of the compressible model in one launch: rho q and, with Kessler, rho q^cl and rho q^r diffuse with one kappa
+// (kappa of the closure, or nu_e / Pr) and the TOTAL density at the faces, both read once per cell.
+// A dry model (the moisture scan's word, bz_moisture.hip) returns before reading: its moisture tendency is the exact zero the advection wrote.
+struct WaterList { const double *c[3]; double *G[3]; };
+template <bool VERT, int NS, class KS>
+__global__ __launch_bounds__(256) void k_water_closure(DevGrid g, KS Ks, RhoField R, WaterList L, const int *__restrict__ skip_if_dry)
+{
+    int bx, by, bz;
+    dif_xcd_block(bx, by, bz);
+    const int i = bx * 256 + threadIdx.x, j = by, k = bz;
+    if (i >= g.Nx) return;
+    if (skip_if_dry && __builtin_amdgcn_readfirstlane(*skip_if_dry) == 1) return;
+    const long long n = g.idx(i, j, k);
+    const double *cs[NS];
+    double div[NS];
+#pragma unroll
+    for (int q = 0; q < NS; ++q) cs[q] = L.c[q];
+    dif_scalar_divergences<VERT, false, NS>(g, Ks, R, n, k, cs, div);
+#pragma unroll
+    for (int q = 0; q < NS; ++q) L.G[q][n] -= div[q];
 }
 
 // ---- implicit step ------------------------------------------------------------------------------------------------------------------
@@ -304,7 +360,9 @@ extern "C" int bz_set_scalar_diffusivity(bz_ctx *ctx, const bz_scalar_diffusivit
     const DevGrid &g = ctx->dg;
     const char *what = nullptr;
     if (ctx->has_closure) what = "a SmagorinskyLilly closure is attached (bz_set_closure): one closure per context";
-    else if (ctx->compressible) what = "not implemented on a compressible context (CompressibleDynamics)";
+    else if (ctx->compressible && c->time_discretization == 1)
+        what = "VerticallyImplicitTimeDiscretization is not implemented on a compressible context (CompressibleDynamics): the explicit discretisation is";
+    else if (ctx->compressible && g.flat_y) what = "not implemented on a compressible context with a Flat y";
     else if (ctx->kinematic) what = "not implemented on a kinematic context (PrescribedDynamics)";
     else if (ctx->slab_mode) what = "not implemented on a y-slab context";
     else if (g.bounded_x || g.bounded_y) what = "not implemented between walls in x or y (Bounded x / Bounded y)";
@@ -360,7 +418,7 @@ int bzi_apply_diffusivity(bz_ctx *ctx, const bz_state *s, double *Gu, double *Gv
     const KSource NUs{ctx->diff_nu, ctx->diffusivity.nu}, KAs{ctx->diff_kappa, ctx->diffusivity.kappa};
     const dim3 grid((g.Nx + 255) / 256, g.Ny, g.Nz), block(256);
     if (dif_momentum_on(ctx)) {
-#define DIF_MOM(V, I) hipLaunchKernelGGL((k_diffusivity_momentum<V, I>), grid, block, 0, ctx->stream, g, NUs, (const double *)s->u, (const double *)s->v, (const double *)s->w, Gu, Gv, Gw, scale)
+#define DIF_MOM(V, I) hipLaunchKernelGGL((k_diffusivity_momentum<V, I, RhoColumn>), grid, block, 0, ctx->stream, g, NUs, RhoColumn(), (const double *)s->u, (const double *)s->v, (const double *)s->w, Gu, Gv, Gw, scale)
         if (vert) DIF_MOM(true, false);
         else if (impl) DIF_MOM(false, true);
         else DIF_MOM(false, false);
@@ -381,7 +439,7 @@ int bzi_apply_diffusivity(bz_ctx *ctx, const bz_state *s, double *Gu, double *Gv
             cs[ns] = (const double *)ctx->tracers[t].specific; Gs[ns++] = (double *)(in_place ? ctx->tracers[t].density : ctx->tracers[t].G);
         }
         for (int q = 0; q < ns; ++q) {
-#define DIF_SCA(V, I) hipLaunchKernelGGL((k_diffusivity_scalar<V, I>), grid, block, 0, ctx->stream, g, KAs, cs[q], Gs[q], scale)
+#define DIF_SCA(V, I) hipLaunchKernelGGL((k_diffusivity_scalar<V, I, RhoColumn>), grid, block, 0, ctx->stream, g, KAs, RhoColumn(), cs[q], Gs[q], scale)
             if (vert) DIF_SCA(true, false);
             else if (impl) DIF_SCA(false, true);
             else DIF_SCA(false, false);
@@ -439,4 +497,60 @@ extern "C" int bz_implicit_step(bz_ctx *ctx, const bz_state *s, double dt)
     if (!ctx || !s) return BZ_ERR_INVALID;
     BZ_REJECT_KINEMATIC(ctx, "bz_implicit_step");
     return bzi_implicit_step(ctx, s->rho_u, s->rho_v, s->rho_w, s->rho_theta, s->rho_q, dt);
+}
+
+// ---- CompressibleDynamics + SplitExplicitTimeDiscretization: the closure terms are slow terms of the split-explicit step ----
+// (src/TimeSteppers/acoustic_substep_helpers.jl:55-93; potential_temperature_tendency.jl:100-105; dynamics_kernel_functions.jl:132-159)
+// momentum and rho theta with rho_d at the flux locations, after the advective slow tendencies
+int bzi_cmp_diffusivity_slow(bz_ctx *ctx, const bz_compressible_state *s, const bz_compressible_prognostic *G)
+{
+    int rc;
+    if (!dif_momentum_on(ctx) && !dif_scalars_on(ctx)) return BZ_OK;      // nu = kappa = the number 0: nothing is launched
+    if ((rc = bzi_diffusivity_halos(ctx))) return rc;
+    const DevGrid &g = ctx->dg;
+    const bool vert = ctx->diffusivity.formulation == 1;
+    ProfileScope ps(ctx, "diffusivity_tendencies");
+    const KSource NUs{ctx->diff_nu, ctx->diffusivity.nu}, KAs{ctx->diff_kappa, ctx->diffusivity.kappa};
+    const RhoField R{s->rho_d};
+    const dim3 grid((g.Nx + 255) / 256, g.Ny, g.Nz), block(256);
+    bz_bools([&](auto v) {
+        if (dif_momentum_on(ctx))
+            hipLaunchKernelGGL((k_diffusivity_momentum<v(), false, RhoField>), grid, block, 0, ctx->stream, g, NUs, R, (const double *)s->u,
+                               (const double *)s->v, (const double *)s->w, G->rho_u, G->rho_v, G->rho_w, 1.0);
+        if (dif_scalars_on(ctx))
+            hipLaunchKernelGGL((k_diffusivity_scalar<v(), false, RhoField>), grid, block, 0, ctx->stream, g, KAs, R, (const double *)s->theta,
+                               G->rho_theta, 1.0);
+    }, vert);
+    BZ_LAUNCH_CHECK();
+    return BZ_OK;
+}
+
+// the water scalars (rho q; with Kessler rho q^cl, rho q^r) of either closure with the total density at the faces: one launch
+int bzi_cmp_water_closure(bz_ctx *ctx, const bz_compressible_state *s, const bz_compressible_prognostic *G, const int *skip_if_dry)
+{
+    if (!ctx->has_closure && !ctx->has_diffusivity) return BZ_OK;
+    if (ctx->has_diffusivity && !dif_scalars_on(ctx)) return BZ_OK;
+    int rc;
+    if (ctx->has_diffusivity && (rc = bzi_diffusivity_halos(ctx))) return rc;
+    const DevGrid &g = ctx->dg;
+    ProfileScope ps(ctx, "water_closure_tendencies");
+    WaterList L;
+    L.c[0] = s->q; L.G[0] = G->rho_q;
+    const bool kes = g.microphysics == 2;
+    L.c[1] = kes ? (const double *)ctx->kessler.cloud_liquid_mass_fraction : nullptr; L.G[1] = kes ? (double *)ctx->kessler.G_cloud_liquid_density : nullptr;
+    L.c[2] = kes ? (const double *)ctx->kessler.rain_mass_fraction : nullptr; L.G[2] = kes ? (double *)ctx->kessler.G_rain_density : nullptr;
+    const RhoField R{s->rho};
+    const dim3 grid((g.Nx + 255) / 256, g.Ny, g.Nz), block(256);
+    const bool vert = ctx->has_diffusivity && ctx->diffusivity.formulation == 1;
+    bz_bools([&](auto v, auto k3) {
+        constexpr int NS = k3() ? 3 : 1;
+        if (ctx->has_closure)      // kappa = nu_e / Pr; nu_e carries its halos (bzi_cmp_closure_fields)
+            hipLaunchKernelGGL((k_water_closure<false, NS, KScaled>), grid, block, 0, ctx->stream, g, KScaled{ctx->closure_nu, 1.0 / ctx->closure.prandtl_number},
+                               R, L, skip_if_dry);
+        else
+            hipLaunchKernelGGL((k_water_closure<v(), NS, KSource>), grid, block, 0, ctx->stream, g, KSource{ctx->diff_kappa, ctx->diffusivity.kappa}, R, L,
+                               skip_if_dry);
+    }, vert, kes);
+    BZ_LAUNCH_CHECK();
+    return BZ_OK;
 }

@@ -632,6 +632,11 @@ int bzi_apply_closure(bz_ctx *ctx, const bz_state *s, double *Gu, double *Gv, do
 void bzi_diffusivity_teardown(bz_ctx *ctx);
 int bzi_diffusivity_halos(bz_ctx *ctx);      // halos of a field-valued nu / kappa
 int bzi_apply_diffusivity(bz_ctx *ctx, const bz_state *s, double *Gu, double *Gv, double *Gw, double *Gth, double *Gq, double scale);
+// ---- closures on CompressibleDynamics (bz_closure.hip, bz_diffusivity.hip): closure fields, slow momentum + rho theta terms, water scalars ----
+int bzi_cmp_closure_fields(bz_ctx *ctx, const bz_compressible_state *s);
+int bzi_cmp_closure_slow(bz_ctx *ctx, const bz_compressible_state *s, const bz_compressible_prognostic *G);
+int bzi_cmp_diffusivity_slow(bz_ctx *ctx, const bz_compressible_state *s, const bz_compressible_prognostic *G);
+int bzi_cmp_water_closure(bz_ctx *ctx, const bz_compressible_state *s, const bz_compressible_prognostic *G, const int *skip_if_dry);
 // implicit_step! of every prognostic field: momentum and the two scalar densities from the arguments, species and tracers from the context
 int bzi_implicit_step(bz_ctx *ctx, double *ru, double *rv, double *rw, double *rth, double *rq, double dtau);
 int bzi_kessler_rk3(bz_ctx *ctx, double dt, double alpha, bool first);

@@ -498,6 +498,9 @@ int bz_set_acoustic_scratch(bz_ctx *ctx, double *momentum_u_second_buffer, doubl
  * transport velocities), for drivers that exchange halos between the diagnosis and the tendency. */
 int bz_compute_moisture_tendency(bz_ctx *ctx, const bz_compressible_state *s, const bz_compressible_prognostic *G,
                                  const bz_acoustic_substepper *sub);
+/* compute_closure_fields!(model.closure_fields, model.closure, model) of a compressible context alone (bz_set_closure: nu_e and its
+ * halos; bz_set_scalar_diffusivity: the halos of a field-valued K; no closure: nothing), from the state the last update_state! left. */
+int bz_compressible_compute_closure_fields(bz_ctx *ctx, const bz_compressible_state *s);
 
 /* ---- DCMIP2016 Kessler warm-rain microphysics: the operator-split column kernel ----
  * microphysics_model_update!(::DCMIP2016KesslerMicrophysics, model) (src/Microphysics/dcmip2016_kessler.jl:449-486, kernel
@@ -743,8 +746,20 @@ int bz_set_bounds_preserving_advection(bz_ctx *ctx, const bz_bounds_preserving_a
  * compute_auxiliary_variables! (src/AtmosphereModels/update_atmosphere_model_state.jl:218) — is followed line by line; the eddy
  * viscosity and kinematic fluxes are Oceananigans' SmagorinskyLilly (0.110.14, not vendored), restated from its published form
  * (oracle/closure.py: parity unpinned).  eddy_viscosity is model.closure_fields.nu_e (centre field parent, caller-owned).
- * With a closure attached bz_compute_tendencies subtracts the divergences after the advective terms.  Single-device anelastic
- * potential-temperature contexts only. */
+ * With a closure attached bz_compute_tendencies subtracts the divergences after the advective terms.  Anelastic potential-temperature
+ * contexts, and compressible contexts (bz_create_compressible) on one device that are periodic in x and y: there the closure terms are
+ * slow terms of the split-explicit step (src/TimeSteppers/acoustic_substep_helpers.jl:55-93) —
+ *   bz_compute_slow_tendencies subtracts d_j T_ij from G_rho_u, G_rho_v, G_rho_w and div J from G_rho_theta (c = theta) with the 3-D
+ *     dynamics density rho_d at the flux locations: the cell value at ccc, the two-point means of the field at the faces, the four-point
+ *     means at ffc / fcf / cff in the order of the nu averages, through the field's own halos; G_rho_d gets nothing;
+ *   bz_compute_moisture_tendency (and the update_state! of whole steps) subtracts div J from the tendencies of rho q and, with Kessler,
+ *     rho q^cl and rho q^r with the TOTAL density at the faces, one launch for all of them;
+ *   every update_state! (bz_compressible_update_state, the stage ends of bz_time_step_compressible, bz_compressible_kessler_update) ends with
+ *     compute_closure_fields!: N^2 = g dz(log theta_v) with theta_v from the model's 3-D pressure at each cell (dynamics_pressure) and
+ *     q^v = specific_humidity(model), then the halos of nu_e (periodic in x / y, zero gradient in z).  T and p carry zero-gradient z halos,
+ *     so the bottom and top face values of dz(log theta_v) are exact zeros.  The slow tendencies of a stage use the nu_e of the
+ *     update_state! before it.
+ * Compressible contexts with a Bounded x or y, a Flat y or on a y-slab return BZ_ERR_UNSUPPORTED naming the option. */
 typedef struct bz_smagorinsky_lilly {
     double smagorinsky_coefficient;   /* C  = 0.16 */
     double reduction_factor;          /* Cb = 1.0: varsigma = sqrt(1 - min(1, Cb N^2+ / Sigma^2)) */
@@ -780,10 +795,12 @@ int bz_compute_closure_fields(bz_ctx *ctx, const bz_state *s);
  * nu_field / kappa_field: centre field parents with the model's halos (caller-owned; NULL: the number in the struct).  The library
  * fills their halos — periodic in x and y, zero gradient in z — before every use (bz_compute_closure_fields, bz_compute_tendencies,
  * bz_implicit_step), because the user may have rewritten them.  Mutually exclusive with bz_set_closure: the second attach returns
- * BZ_ERR_UNSUPPORTED.  Single-device anelastic contexts, periodic in x and y (or Flat y); y-slab, walled, compressible and
- * kinematic contexts return BZ_ERR_UNSUPPORTED naming the option.  With one attached bz_compute_tendencies subtracts the explicit
+ * BZ_ERR_UNSUPPORTED.  Single-device contexts, periodic in x and y (or, anelastic, Flat y); y-slab, walled and kinematic contexts return
+ * BZ_ERR_UNSUPPORTED naming the option.  With one attached bz_compute_tendencies subtracts the explicit
  * divergences where it subtracts SmagorinskyLilly's, and bz_time_step(s)_anelastic run the implicit step of every stage (never on
- * the lean tier).  NULL detaches. */
+ * the lean tier).  Compressible contexts take the explicit discretisation only (time_discretization 1, or a Flat y, returns
+ * BZ_ERR_UNSUPPORTED naming the option): the divergences enter where SmagorinskyLilly's do — rho_d at the flux locations for momentum and
+ * rho theta, the total density for the water scalars — and the halos of a field-valued K are refilled before every use.  NULL detaches. */
 typedef struct bz_scalar_diffusivity {
     int32_t formulation;           /* 0: ScalarDiffusivity (isotropic), 1: VerticalScalarDiffusivity */
     int32_t time_discretization;   /* 0: ExplicitTimeDiscretization, 1: VerticallyImplicitTimeDiscretization */

@@ -191,12 +191,33 @@ struct BzTracerFields
     density::Ptr{Cdouble}; specific::Ptr{Cdouble}; U0::Ptr{Cdouble}; G::Ptr{Cdouble}
 end
 
-"closure = SmagorinskyLilly(): νₑ is `model.closure_fields.νₑ` (src/AtmosphereModels/atmosphere_model.jl:272-276)."
+"closure = SmagorinskyLilly(): νₑ is `model.closure_fields.νₑ` (src/AtmosphereModels/atmosphere_model.jl:272-276).  Anelastic and
+compressible contexts alike (bz_create_compressible: one device, periodic in x and y)."
 function attach_closure!(ctx, closure, νₑ)
     c = closure.coefficient              # LillyCoefficient(smagorinsky, reduction_factor); Pr from closure.Pr
     cl = BzSmagorinskyLilly(c.smagorinsky, c.reduction_factor, first(values(closure.Pr)))
     check(ccall((:bz_set_closure, libbreeze_hip), Cint, (Ptr{Cvoid}, Ref{BzSmagorinskyLilly}, Ptr{Cdouble}),
                 ctx, cl, pointer(parent(νₑ))), "bz_set_closure", ctx)
+end
+
+struct BzScalarDiffusivity
+    formulation::Int32; time_discretization::Int32
+    nu::Cdouble; kappa::Cdouble
+end
+
+"""
+closure = ScalarDiffusivity(ν, κ) / VerticalScalarDiffusivity(ν, κ): numbers or `(Center, Center, Center)` fields the caller keeps alive
+and may rewrite between steps (validation/DCMIP2016_TC/dcmip2016_tc.jl:277-292); one κ for every scalar.  Compressible contexts take the
+explicit discretisation only (the library returns BZ_ERR_UNSUPPORTED for the vertically implicit one).  NOT RUN: no Julia is installed
+where this library is built.
+"""
+function attach_scalar_diffusivity!(ctx, closure, vertical::Bool, implicit::Bool)
+    ν, κ = closure.ν, closure.κ isa NamedTuple ? first(values(closure.κ)) : closure.κ
+    fieldptr(K) = K isa Number ? Ptr{Cdouble}(C_NULL) : pointer(parent(K))
+    number(K) = K isa Number ? Cdouble(K) : 0.0
+    sd = BzScalarDiffusivity(Int32(vertical), Int32(implicit), number(ν), number(κ))
+    GC.@preserve ν κ check(ccall((:bz_set_scalar_diffusivity, libbreeze_hip), Cint, (Ptr{Cvoid}, Ref{BzScalarDiffusivity}, Ptr{Cdouble}, Ptr{Cdouble}),
+                                 ctx, sd, fieldptr(ν), fieldptr(κ)), "bz_set_scalar_diffusivity", ctx)
 end
 
 """
@@ -454,6 +475,18 @@ function create_compressible_context(model)
                    TX === Bounded && active(bu.west), TX === Bounded && active(bu.east), TY === Bounded && active(bv.south),
                    TY === Bounded && active(bv.north), a.open_boundary_relaxation)
         check(rc, "bz_set_acoustic_lateral_boundaries", ctx[])
+    end
+    # closure terms are slow terms of the split-explicit step (src/TimeSteppers/acoustic_substep_helpers.jl:55-93); the library ends every
+    # update_state! with compute_closure_fields!.  NOT RUN (no Julia where this library is built).
+    cl = model.closure
+    if cl isa Oceananigans.TurbulenceClosures.SmagorinskyLilly
+        attach_closure!(ctx[], cl, model.closure_fields.νₑ)
+    elseif cl isa Oceananigans.TurbulenceClosures.ScalarDiffusivity
+        F = typeof(cl).parameters[2]                                    # ThreeDimensionalFormulation | VerticalFormulation
+        attach_scalar_diffusivity!(ctx[], cl, F <: Oceananigans.TurbulenceClosures.VerticalFormulation,
+                                   typeof(cl).parameters[1] <: Oceananigans.TurbulenceClosures.VerticallyImplicitTimeDiscretization)
+    elseif cl !== nothing
+        error("closure = $(typeof(cl).name.name) is not implemented on the HIP compressible path")
     end
     return ctx[]
 end
