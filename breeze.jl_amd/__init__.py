@@ -18,6 +18,7 @@ from .compressible import (AcousticRungeKutta3, AcousticSubstepper, Compressible
                            ExnerReferenceState, NewtonSolver, NoDivergenceDamping, ProportionalSubsteps, ConstantSubstepSize, MonolithicFirstStage,
                            SplitExplicitTimeDiscretization, ThermalDivergenceDamping, DirectDivergenceDamping, UpperSponge,
                            LinearRamp, CubicRamp, Sin2Ramp, NormalFlowBoundaryCondition)
+from .compressible import HydrostaticallyBalancedDensity, set_to_mean_  # noqa: F401,E402
 from .microphysics import SaturationAdjustment, SecantSolver, WarmPhaseEquilibrium  # noqa: F401,E402
 from .model import cell_advection_timescale, diagnostics_stale, many_time_steps_, nan_checker  # noqa: F401,E402
 from .model import PrescribedDynamics, PrescribedVelocityFields, compute_kinematic_tendencies_  # noqa: F401,E402

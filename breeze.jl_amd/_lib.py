@@ -268,6 +268,9 @@ SYMBOLS = {
     "bz_acoustic_substep_loop": (C.c_int, [_ctx, _csp, _cpp, _cpp, _asp, C.c_double, C.c_double]),
     "bz_acoustic_rk3_substep": (C.c_int, [_ctx, _csp, _cpp, _cpp, _asp, C.c_double, C.c_double]),
     "bz_time_step_compressible": (C.c_int, [_ctx, _csp, _cpp, _cpp, _asp, C.c_double]),
+    "bz_exner_columns": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bz_set_hydrostatically_balanced_density": (C.c_int, [_ctx, _csp, C.c_double]),
+    "bz_set_exner_reference_state": (C.c_int, [_ctx, C.POINTER(bz_exner_reference_state)]),
     "bz_create_compressible_slab": (C.c_int, [C.POINTER(_ctx), C.POINTER(bz_grid), C.POINTER(bz_constants),
                                               C.POINTER(bz_exner_reference_state), C.POINTER(bz_split_explicit), C.c_int,
                                               C.c_int, C.c_int]),

@@ -8,8 +8,9 @@
                                                    src/TimeSteppers/acoustic_runge_kutta_3.jl:64-103
   set! / update_state! / time_step!                src/AtmosphereModels/set_atmosphere_model.jl:198-362,
                                                    src/TimeSteppers/acoustic_runge_kutta_3.jl:230-319
+  HydrostaticallyBalancedDensity / set_to_mean!    src/AtmosphereModels/set_to_mean.jl:152-229,243-310
 (paths relative to /root/reference; Julia's `f!` is spelled `f_`).  Every numerical operation of the time step is a
-HIP kernel behind libbreeze_hip.so; the numpy code here only builds the 1-D reference columns at construction.
+HIP kernel behind libbreeze_hip.so; the numpy code here only builds the 1-D reference columns, at construction and in set_to_mean_.
 """
 import ctypes as C
 
@@ -141,25 +142,52 @@ def _z_metrics(grid):
     return dzc, dzf
 
 
+def _exner_column(θ, qv, dzc, dzf, p0, pst, c):
+    """_compute_exner_column! (reference_states.jl:588-672) on float64 profiles θ, qᵛ of Nz levels: (π, p, ρ) and the surface Exner function."""
+    Nz = len(θ)
+    Rd, Rv = dry_air_gas_constant(c), vapor_gas_constant(c)
+    cpd, cpv, g = c.dry_air_heat_capacity, c.vapor_heat_capacity, c.gravitational_acceleration
+
+    def moist(q):      # moist_reference_constants (reference_states.jl:572-577); exactly the dry constants for q = 0
+        qd = 1 - q
+        Rm, cpm = qd * Rd + q * Rv, qd * cpd + q * cpv
+        return Rm, cpm, Rm / cpm
+
+    π, p, ρ = np.zeros(Nz), np.zeros(Nz), np.zeros(Nz)
+    Rm1, cpm1, κ1 = moist(qv[0])
+    π_surface = (p0 / pst) ** κ1
+    π[0] = π_surface - g * dzc[0] / (2 * cpm1 * θ[0])
+    p[0] = pst * π[0] ** (1 / κ1)
+    ρ[0] = p[0] / (Rm1 * θ[0] * π[0])
+    for k in range(1, Nz):
+        Rm, cpm, κ = moist(qv[k])
+        θface = (θ[k] + θ[k - 1]) / 2
+        pk = pst * (π[k - 1] - g * dzf[k] / (cpm * θface)) ** (1 / κ)
+        A = g * pst ** κ / (2 * Rm * θ[k])
+        Cc = p[k - 1] / dzf[k] - g * ρ[k - 1] / 2
+        for _ in range(5):                                   # FixedIterations(5) Newton on the discrete balance
+            ρp = pk ** (-κ)
+            f = pk / dzf[k] + A * pk * ρp - Cc
+            df = 1 / dzf[k] + A * (1 - κ) * ρp
+            pk -= f / df
+        p[k] = pk
+        π[k] = (pk / pst) ** κ
+        ρ[k] = pk / (Rm * θ[k] * π[k])
+    return π, p, ρ, π_surface, Rm1
+
+
 class ExnerReferenceState:
     """1-D, isentropic-mode ExnerReferenceState, dry or moist (`vapor_mass_fraction` a number or qᵛ(z)): the discrete
     hydrostatic balance (p[k]-p[k-1])/Δzᶠ + g (ρ[k]+ρ[k-1])/2 = 0 holds to rounding at every interior face
-    (src/Thermodynamics/reference_states.jl:572-672,718-827)."""
+    (src/Thermodynamics/reference_states.jl:572-672,718-827).  `from_profiles` builds one from θ and qᵛ given as arrays of Nz levels;
+    `set_profiles_` recomputes the columns of an existing one in place (set_to_mean!): both run the integration of the constructor."""
 
     def __init__(self, grid, constants=None, surface_pressure=101325, potential_temperature=288, standard_pressure=1e5,
                  vapor_mass_fraction=None, reference_temperature=None):
         if reference_temperature is not None:
             raise NotImplementedError("the isothermal ExnerReferenceState mode is not implemented")
-        c = constants or ThermodynamicConstants()
-        self.constants = c
-        Nz, Hz = grid.Nz, grid.Hz
-        self.surface_pressure = p0 = float(surface_pressure)
-        self.standard_pressure = pst = float(standard_pressure)
+        Nz = grid.Nz
         θfun = potential_temperature if callable(potential_temperature) else (lambda z: float(potential_temperature) + 0.0 * z)
-        self.surface_potential_temperature = float(θfun(np.float64(0.0)))
-        Rd, Rv = dry_air_gas_constant(c), vapor_gas_constant(c)
-        cpd, cpv, g = c.dry_air_heat_capacity, c.vapor_heat_capacity, c.gravitational_acceleration
-        dzc, dzf = _z_metrics(grid)
         θ = np.asarray(θfun(grid.zᶜ), dtype=np.float64)
         if vapor_mass_fraction is None:
             qv = np.zeros(Nz)
@@ -167,34 +195,46 @@ class ExnerReferenceState:
             qv = np.array([float(vapor_mass_fraction(z)) for z in grid.zᶜ])
         else:
             qv = np.full(Nz, float(vapor_mass_fraction))
-        self.vapor_mass_fraction = qv
+        self._build(grid, constants, surface_pressure, standard_pressure, θ, qv, float(θfun(np.float64(0.0))))
 
-        def moist(q):      # moist_reference_constants (reference_states.jl:572-577); exactly the dry constants for q = 0
-            qd = 1 - q
-            Rm, cpm = qd * Rd + q * Rv, qd * cpd + q * cpv
-            return Rm, cpm, Rm / cpm
+    @classmethod
+    def from_profiles(cls, grid, potential_temperature, vapor_mass_fraction=None, constants=None, surface_pressure=101325,
+                      standard_pressure=1e5, surface_potential_temperature=None):
+        """The reference state of θ and qᵛ given level by level (arrays of Nz values at the cell centres); the surface θ of the bottom
+        boundary values defaults to the first level's."""
+        θ = np.array(potential_temperature, dtype=np.float64).reshape(-1)
+        qv = np.zeros(grid.Nz) if vapor_mass_fraction is None else np.array(vapor_mass_fraction, dtype=np.float64).reshape(-1)
+        if θ.shape != (grid.Nz,) or qv.shape != (grid.Nz,):
+            raise ValueError(f"profiles must have Nz = {grid.Nz} levels")
+        self = cls.__new__(cls)
+        self._build(grid, constants, surface_pressure, standard_pressure, θ, qv,
+                    float(θ[0] if surface_potential_temperature is None else surface_potential_temperature))
+        return self
 
-        π, p, ρ = np.zeros(Nz), np.zeros(Nz), np.zeros(Nz)
-        Rm1, cpm1, κ1 = moist(qv[0])
-        π_surface = (p0 / pst) ** κ1
-        π[0] = π_surface - g * dzc[0] / (2 * cpm1 * θ[0])
-        p[0] = pst * π[0] ** (1 / κ1)
-        ρ[0] = p[0] / (Rm1 * θ[0] * π[0])
-        for k in range(1, Nz):
-            Rm, cpm, κ = moist(qv[k])
-            θface = (θ[k] + θ[k - 1]) / 2
-            pk = pst * (π[k - 1] - g * dzf[k] / (cpm * θface)) ** (1 / κ)
-            A = g * pst ** κ / (2 * Rm * θ[k])
-            Cc = p[k - 1] / dzf[k] - g * ρ[k - 1] / 2
-            for _ in range(5):                                   # FixedIterations(5) Newton on the discrete balance
-                ρp = pk ** (-κ)
-                f = pk / dzf[k] + A * pk * ρp - Cc
-                df = 1 / dzf[k] + A * (1 - κ) * ρp
-                pk -= f / df
-            p[k] = pk
-            π[k] = (pk / pst) ** κ
-            ρ[k] = pk / (Rm * θ[k] * π[k])
-        self.surface_density = ρ0 = p0 / (Rm1 * self.surface_potential_temperature * π_surface)
+    def _build(self, grid, constants, surface_pressure, standard_pressure, θ, qv, θ_surface):
+        self.constants = c = constants or ThermodynamicConstants()
+        self.grid = grid
+        self.Nz, self.Hz = grid.Nz, grid.Hz
+        self.surface_pressure = float(surface_pressure)
+        self.standard_pressure = float(standard_pressure)
+        self.surface_potential_temperature = θ_surface
+        self.surface_density = None
+        self.set_profiles_(θ, qv)
+
+    def set_profiles_(self, potential_temperature, vapor_mass_fraction):
+        """Recompute exner_function, pressure and density in place from level profiles of θ and qᵛ.  The halo levels follow the boundary
+        conditions the reference's fields are built with (reference_states.jl:795-817): pressure and density carry the ValueBoundaryCondition
+        of construction at the bottom — the surface pressure, and the surface density of the FIRST profiles, which set_to_mean! does not
+        touch — and the default no-flux condition on top; the Exner function is no-flux on both sides."""
+        Nz, Hz = self.Nz, self.Hz
+        θ = np.asarray(potential_temperature, dtype=np.float64)
+        qv = np.asarray(vapor_mass_fraction, dtype=np.float64)
+        dzc, dzf = _z_metrics(self.grid)
+        p0 = self.surface_pressure
+        π, p, ρ, π_surface, Rm1 = _exner_column(θ, qv, dzc, dzf, p0, self.standard_pressure, self.constants)
+        if self.surface_density is None:
+            self.surface_density = p0 / (Rm1 * self.surface_potential_temperature * π_surface)
+        ρ0 = self.surface_density
 
         def with_halos(a, bottom_value=None):
             out = np.zeros(Nz + 2 * Hz)
@@ -203,11 +243,22 @@ class ExnerReferenceState:
             out[Hz + Nz] = a[-1]
             return out
 
+        self.vapor_mass_fraction = np.array(qv)
         self.pressure = with_halos(p, p0)
         self.density = with_halos(ρ, ρ0)
         self.exner_function = with_halos(π)
         self.potential_temperature = with_halos(θ)
-        self.Nz, self.Hz = Nz, Hz
+
+
+class HydrostaticallyBalancedDensity:
+    """HydrostaticallyBalancedDensity(surface_pressure=None) (set_to_mean.jl:243-260): passed as `ρ` to `set`, the density is put into
+    discrete moist hydrostatic balance with the θˡⁱ and qᵛ just set, column by column upward from `surface_pressure` (None: the dynamics'
+    surface pressure)."""
+
+    def __init__(self, surface_pressure=None):
+        if surface_pressure is not None and not float(surface_pressure) > 0:
+            raise ValueError(f"`surface_pressure` must be positive (got {surface_pressure})")
+        self.surface_pressure = None if surface_pressure is None else float(surface_pressure)
 
 
 class CompressibleDynamics:
@@ -216,6 +267,11 @@ class CompressibleDynamics:
         if time_discretization is None or not isinstance(time_discretization, SplitExplicitTimeDiscretization):
             raise NotImplementedError("the HIP path implements CompressibleDynamics(SplitExplicitTimeDiscretization(...)); "
                                       "ExplicitTimeStepping is outside the hot-path scope")
+        self._reference_given = reference_state if isinstance(reference_state, ExnerReferenceState) else None
+        if self._reference_given is not None:      # an already built state: its columns are taken as they are, halo levels included
+            if reference_potential_temperature is not None or reference_vapor_mass_fraction is not None:
+                raise ValueError("an ExnerReferenceState passed as `reference_state` is mutually exclusive with an explicit reference profile")
+            reference_state = "auto"
         if reference_state not in ("auto", ":auto", None):
             raise ValueError(f"`reference_state` must be `:auto` or `nothing`; received {reference_state!r}.")
         if reference_state is None and reference_potential_temperature is not None:
@@ -399,7 +455,12 @@ class CompressibleAtmosphereModel:
             self.microphysical_fields = {k: fld("ccc") for k in ("ρqᶜˡ", "ρqʳ", "qᵛ", "qᶜˡ", "qʳ", "𝕎ʳ")}
             self.microphysical_fields["precipitation_rate"] = torch.zeros((grid.Ny + 2 * grid.Hy, grid.Nx + 2 * grid.Hx),
                                                                           dtype=self.potential_temperature.dtype, device=self.device)
-        if dynamics._reference_spec is not None:
+        if dynamics._reference_given is not None:
+            given = dynamics._reference_given
+            if (given.Nz, given.Hz) != (grid.Nz, grid.Hz):
+                raise ValueError("the ExnerReferenceState passed as `reference_state` was built on another vertical grid")
+            dynamics.reference_state = given
+        elif dynamics._reference_spec is not None:
             dynamics.reference_state = ExnerReferenceState(grid, c, surface_pressure=dynamics.surface_pressure,
                                                            potential_temperature=dynamics._reference_spec,
                                                            vapor_mass_fraction=dynamics._reference_vapor,
@@ -666,10 +727,77 @@ def _require_whole_model_on_walls(model, what):
         raise NotImplementedError(f"{what}: SaturationAdjustment is not built on a Bounded y")
 
 
-def set_(model, **kw):
-    """set!(model; ρ, θ, u, v, w, qᵗ): total density first, moisture, then establish_densities!, θ and velocities
+def _require_balance_scope(model, what):
+    """set_to_mean!, compute_reference_state and HydrostaticallyBalancedDensity: one device, (Periodic, Periodic | Flat, Bounded)."""
+    if getattr(model, "lateral_walls", False):
+        raise NotImplementedError(f"{what}: not implemented on a compressible model between walls (Bounded x / Bounded y)")
+    if type(model) is not CompressibleAtmosphereModel:
+        raise NotImplementedError(f"{what}: not implemented on y-slab (distributed) compressible models")
+
+
+def specific_humidity(model):
+    """specific_humidity(model) = model.microphysical_fields.qᵛ (microphysics_interface.jl:359); without microphysics the moisture is vapour."""
+    return model.microphysical_fields["qᵛ"] if model.microphysics is not None else model.specific_moisture
+
+
+def set_to_mean_(reference_state, model):
+    """set_to_mean!(ref::ExnerReferenceState, model) (set_to_mean.jl:152-201): the reference columns again, by the constructor's integration,
+    from the horizontal means of the model's θˡⁱ and qᵛ (bz_horizontal_average); the host object is updated in place, the context takes the
+    new columns (bz_set_exner_reference_state) and update_state! follows.  No density is rescaled: the Exner reference is the base state of
+    the perturbation form only."""
+    _require_balance_scope(model, "set_to_mean!")
+    if not isinstance(reference_state, ExnerReferenceState):
+        raise TypeError("set_to_mean!: the compressible model carries an ExnerReferenceState")
+    if reference_state is not model.dynamics.reference_state:
+        raise ValueError("set_to_mean!: `reference_state` must be the model's own (model.dynamics.reference_state)")
+    from .diagnostics import horizontal_average
+    θ = horizontal_average(model, model.potential_temperature).astype(np.float64)
+    qv = horizontal_average(model, specific_humidity(model)).astype(np.float64)
+    reference_state.set_profiles_(θ, qv)
+    T = model._T
+    model._ref_arrays = [np.ascontiguousarray(a, dtype=T.np_real) for a in (reference_state.pressure, reference_state.density)]
+    br = T.bz_exner_reference_state()
+    br.standard_pressure = model.dynamics.standard_pressure
+    br.pressure, br.density = (a.ctypes.data_as(C.POINTER(T.real)) for a in model._ref_arrays)
+    model._check(model._lib.bz_set_exner_reference_state(model._ctx, C.byref(br)), "bz_set_exner_reference_state")
+    update_state_(model, compute_tendencies=False)
+
+
+def reset_reference_state_(model):
+    """reset_reference_state!(model) (set_to_mean.jl:212-229): a no-op on a model without a reference state."""
+    ref = model.dynamics.reference_state
+    if ref is not None:
+        set_to_mean_(ref, model)
+
+
+def set_hydrostatically_balanced_density_(model, spec):
+    """set_hydrostatically_balanced_density!(model, spec) (set_to_mean.jl:262-310) behind bz_set_hydrostatically_balanced_density."""
+    _require_balance_scope(model, "HydrostaticallyBalancedDensity")
+    p0 = model.dynamics.surface_pressure if spec.surface_pressure is None else spec.surface_pressure
+    model._check(model._lib.bz_set_hydrostatically_balanced_density(model._ctx, C.byref(model._state), float(p0)),
+                 "bz_set_hydrostatically_balanced_density")
+
+
+def exner_columns_(model, potential_temperature, vapor_mass_fraction, surface_pressure, exner_function, pressure, density):
+    """_compute_exner_reference_3d! on centre Fields of the model's grid (vapor_mass_fraction None: dry): one balanced column per (i, j)."""
+    model._check(model._lib.bz_exner_columns(model._ctx, C.c_void_p(potential_temperature.ptr()),
+                                             C.c_void_p(None if vapor_mass_fraction is None else vapor_mass_fraction.ptr()),
+                                             float(surface_pressure), C.c_void_p(exner_function.ptr()), C.c_void_p(pressure.ptr()),
+                                             C.c_void_p(density.ptr())), "bz_exner_columns")
+
+
+def set_(model, compute_reference_state=False, **kw):
+    """set!(model; ρ, θ, u, v, w, qᵗ, compute_reference_state): total density first, moisture, then establish_densities!, θ and velocities
     (set_atmosphere_model.jl:198-362; compressible_time_stepping.jl:105-150).  Walls in y: v given as a function is evaluated on the
-    faces 0 … Ny-1, ρv takes the face-mean density through the no-flux halo row, and update_state! leaves exact zeros on the wall faces."""
+    faces 0 … Ny-1, ρv takes the face-mean density through the no-flux halo row, and update_state! leaves exact zeros on the wall faces.
+    ρ = HydrostaticallyBalancedDensity(p₀) is the reference's deferred density: a unit placeholder goes into ρᵈ, establish_densities! runs with
+    neither density given, and the balanced density is computed after the closing update_state!; compute_reference_state = True recomputes
+    the reference state from the horizontal means first (a no-op without one)."""
+    balanced = next((v for n, v in kw.items() if _ALIASES.get(n) == "ρ" and isinstance(v, HydrostaticallyBalancedDensity)), None)
+    if balanced is not None:
+        _require_balance_scope(model, "HydrostaticallyBalancedDensity")
+    if compute_reference_state:
+        _require_balance_scope(model, "compute_reference_state")
     _require_whole_model_on_walls(model, "set!")
     d = model.dynamics
     g = model.grid
@@ -681,8 +809,9 @@ def set_(model, **kw):
                              "settable thermodynamic variable, nor a settable diagnostic variable!")
         keys[key] = value
     ρd, ρ = d.dry_density, d.total_density
+    total_density_given = "ρ" in keys and balanced is None
     if "ρ" in keys:
-        ρd.set_interior(keys["ρ"])
+        ρd.set_interior(1.0 if balanced is not None else keys["ρ"])
     if "q" in keys:
         model.specific_moisture.set_interior(keys["q"])
         model.moisture_density.interior.copy_(ρd.interior * model.specific_moisture.interior)
@@ -696,7 +825,7 @@ def set_(model, **kw):
         condensate = model.microphysical_fields["ρqᶜˡ"].interior + (model.microphysical_fields["ρqʳ"].interior + 0.0)
     elif "qcl" in keys or "qr" in keys:
         raise ValueError("Cannot set! qᶜˡ / qʳ: the model has no Kessler microphysics")
-    if "ρ" in keys:      # establish_densities!(total_density_given)
+    if total_density_given:      # establish_densities!(total_density_given); neither given: update_state! diagnoses ρ = ρᵈ + Σρqˣ
         ρ.interior.copy_(ρd.interior)
         ρd.interior.copy_(ρ.interior - (model.moisture_density.interior + condensate))
     from .model import fill_halo_regions_
@@ -721,6 +850,10 @@ def set_(model, **kw):
         ρz = (P[Hz:Hz + Nz + 1, Hy:Hy + Ny, Hx:Hx + Nx] + P[Hz - 1:Hz + Nz, Hy:Hy + Ny, Hx:Hx + Nx]) / 2
         model.momentum["ρw"].interior.copy_(ρz * model.velocities["w"].interior)
     update_state_(model, compute_tendencies=False)
+    if compute_reference_state:
+        reset_reference_state_(model)
+    if balanced is not None:
+        set_hydrostatically_balanced_density_(model, balanced)
 
 
 def time_step_(model, Δt, whole_step=True):

@@ -207,6 +207,39 @@ extern "C" int bz_create_slab(bz_ctx **out, const bz_grid *local_grid, const bz_
     return bzi_create(out, local_grid, constants, ref, weno_order, y_nranks, y_rank, true);
 }
 
+// column tables of a context: C_COUNT columns of nf = Nz + 2 Hz + 1 entries each, one device allocation (bz_ctx::d_columns)
+enum { C_DZC, C_DZF, C_RDZF, C_AX, C_AY, C_VIC, C_VIF, C_RHO, C_RHOF, C_PR, C_TR, C_RDZC, C_ZC, C_RRHO, C_RRHOF, C_LNPI, C_COUNT };
+// the columns derived from the reference density and pressure (host arrays of nc = Nz + 2 Hz entries): rho_r, 1 / rho_r, p_r, ln(p_r / p_st) at
+// centres; Iz(rho_r) = 0.5 (rho_r[k-1] + rho_r[k]) and its reciprocal at the faces where both levels exist
+static const int REFERENCE_COLUMNS[] = {C_RHO, C_RRHO, C_PR, C_LNPI, C_RHOF, C_RRHOF};
+static void fill_reference_columns(double *cols, int nf, int nc, const double *density, const double *pressure, double standard_pressure)
+{
+    auto col = [&](int c) { return cols + (size_t)c * nf; };
+    for (int k = 0; k < nc; ++k) {
+        col(C_RHO)[k] = density[k];
+        col(C_RRHO)[k] = 1.0 / density[k];
+        col(C_PR)[k] = pressure[k];
+        col(C_LNPI)[k] = std::log(pressure[k] / standard_pressure);
+    }
+    for (int k = 1; k < nc; ++k) {
+        col(C_RHOF)[k] = 0.5 * (density[k - 1] + density[k]);
+        col(C_RRHOF)[k] = 1.0 / col(C_RHOF)[k];
+    }
+}
+
+// bz_set_exner_reference_state: the reference-derived columns of bzi_create again, from new host arrays, by the same function.  The stream is
+// drained first: kernels in flight read the tables
+int bzi_refresh_reference_columns(bz_ctx *ctx, const double *density, const double *pressure)
+{
+    const int nc = ctx->dg.Nz + 2 * ctx->dg.Hz, nf = nc + 1;
+    std::vector<double> cols((size_t)C_COUNT * nf, 0.0);
+    fill_reference_columns(cols.data(), nf, nc, density, pressure, ctx->dg.pst);
+    BZ_HIP(hipStreamSynchronize(ctx->stream));
+    for (const int c : REFERENCE_COLUMNS)
+        BZ_HIP(hipMemcpy(ctx->d_columns + (size_t)c * nf, cols.data() + (size_t)c * nf, (size_t)nf * sizeof(double), hipMemcpyHostToDevice));
+    return BZ_OK;
+}
+
 int bzi_create(bz_ctx **out, const bz_grid *grid, const bz_constants *constants, const bz_reference_state *ref,
                int weno_order, int y_nranks, int y_rank, bool slab_mode, bool compressible)
 {
@@ -285,8 +318,7 @@ int bzi_create(bz_ctx **out, const bz_grid *grid, const bz_constants *constants,
         for (int k = 0; k < nc; ++k) zc_ext[k] = grid->zf[0] + dz * ((k - Hz) + 0.5);   // Oceananigans regular-grid nodes
     }
 
-    // ---- column tables: 11 columns of nf entries each ----
-    enum { C_DZC, C_DZF, C_RDZF, C_AX, C_AY, C_VIC, C_VIF, C_RHO, C_RHOF, C_PR, C_TR, C_RDZC, C_ZC, C_RRHO, C_RRHOF, C_LNPI, C_COUNT };
+    // ---- column tables: C_COUNT columns of nf entries each ----
     std::vector<double> cols((size_t)C_COUNT * nf, 0.0);
     auto col = [&](int c) { return cols.data() + (size_t)c * nf; };
     const double dx = grid->dx, dy = grid->dy;
@@ -297,21 +329,13 @@ int bzi_create(bz_ctx **out, const bz_grid *grid, const bz_constants *constants,
         col(C_AX)[k] = dy * dzc[k];
         col(C_AY)[k] = dx * dzc[k];
         col(C_VIC)[k] = 1.0 / (dx * dy * dzc[k]);
-        col(C_RHO)[k] = ref->density[k];
-        col(C_RRHO)[k] = 1.0 / ref->density[k];
-        col(C_PR)[k] = ref->pressure[k];
         col(C_TR)[k] = ref->temperature[k];
-        col(C_LNPI)[k] = std::log(ref->pressure[k] / ref->standard_pressure);
     }
+    fill_reference_columns(cols.data(), nf, nc, ref->density, ref->pressure, ref->standard_pressure);
     for (int k = 0; k < nf; ++k) {
         col(C_DZF)[k] = dzf[k];
         col(C_RDZF)[k] = 1.0 / dzf[k];
         col(C_VIF)[k] = 1.0 / (dx * dy * dzf[k]);
-        // Iz(rho) at face k: 0.5*(rho[k-1]+rho[k]); defined where both exist
-        if (k >= 1 && k < nc) {
-            col(C_RHOF)[k] = 0.5 * (ref->density[k - 1] + ref->density[k]);
-            col(C_RRHOF)[k] = 1.0 / col(C_RHOF)[k];
-        }
     }
 
     {   // a failed allocation must not leak the half-built context
@@ -400,6 +424,7 @@ extern "C" void bz_destroy(bz_ctx *ctx)
     bzi_poisson_teardown(ctx);
     bzi_lean_teardown(ctx);
     bzi_compressible_teardown(ctx);
+    bzi_balance_teardown(ctx);
     if (ctx->d_columns) hipFree(ctx->d_columns);
     bzi_forcing_teardown(ctx);
     bzi_closure_teardown(ctx);

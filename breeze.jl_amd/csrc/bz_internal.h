@@ -463,6 +463,7 @@ struct bz_ctx {
     double *d_up2 = nullptr, *d_vp2 = nullptr;   // second buffers of the (rho u)', (rho v)' ping-pong (fused substep)
     double *d_Gp_ru = nullptr, *d_Gp_rv = nullptr;   // slow horizontal momentum tendencies minus the gradient of the stage's p^L (k_ac_stage_init<PF>, round 6)
     double *d_thL2 = nullptr;         // second buffer of theta_L: the fused stage epilogue writes the next stage's linearisation while it still reads this one's
+    double *d_balance = nullptr;      // bz_set_hydrostatically_balanced_density: old dry density + balanced total density, allocated by the first call (bz_balance.hip)
     bool thL_alt = false;             // the current theta_L lives in d_thL2 (whole-step seam only; every per-operator linearisation resets it)
     bool substep_f32 = false;         // substep_floattype = Float32 inside the Float64 library: the substepper's working fields are float arrays
     bool ac_whole_step = false;       // set around bzi_acoustic_stage_begin by the whole-step seam (AcParams::dry_q)
@@ -725,6 +726,8 @@ int bzi_tendencies_fused_rk(bz_ctx *ctx, const bz_state *s, const bz_prognostic 
 int bzi_create(bz_ctx **out, const bz_grid *grid, const bz_constants *constants, const bz_reference_state *ref,
                int weno_order, int y_nranks, int y_rank, bool slab_mode, bool compressible = false);
 void bzi_compressible_teardown(bz_ctx *ctx);
+void bzi_balance_teardown(bz_ctx *ctx);
+int bzi_refresh_reference_columns(bz_ctx *ctx, const double *density, const double *pressure);      // bz_context.hip: the columns bzi_create derives from the reference
 bool bzi_k6_stored_ok(const bz_ctx *ctx);
 int bzi_k6_stored(bz_ctx *ctx, int comp, const bz_state *s, const bz_prognostic *G, const bz_prognostic *U0, const RKEpilogue *Ein, int bm);
 int bzi_scalar_pair_tendency(bz_ctx *ctx, const bz_state *s, const bz_prognostic *G, const bz_prognostic *U0 = nullptr,

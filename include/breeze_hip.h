@@ -436,6 +436,35 @@ int bz_acoustic_rk3_substep(bz_ctx *ctx, const bz_compressible_state *s, const b
 int bz_time_step_compressible(bz_ctx *ctx, const bz_compressible_state *s, const bz_compressible_prognostic *U0,
                               const bz_compressible_prognostic *G, const bz_acoustic_substepper *sub, double dt);
 
+/* ---- discrete hydrostatic balance of the initial and the base state (csrc/bz_balance.hip) ----
+ * set!(model; rho = HydrostaticallyBalancedDensity(p0)) and set!(model; compute_reference_state = true) / set_to_mean!(::ExnerReferenceState,
+ * model) of the reference (src/AtmosphereModels/set_to_mean.jl:152-229,243-310; src/Thermodynamics/reference_states.jl:572-677,835-838).
+ * One device, (Periodic, Periodic | Flat, Bounded): contexts with a Bounded x or y and y-slab contexts return BZ_ERR_UNSUPPORTED from all
+ * three, with bz_last_error naming the function.
+ *
+ * bz_exner_columns — _compute_exner_reference_3d!: one discrete-balance Exner integration per column (i, j) of the DEVICE parent arrays
+ * theta and qv (NULL = dry), upward from the surface pressure p0: half a continuous step to level 1, then for k = 2 .. Nz a continuous first
+ * guess and exactly five Newton iterations on F(p) = p / dz_f + A p^(1 - kappa) - C with the level's moist constants, so that
+ * (p[k] - p[k-1]) / dz_f[k] + g (rho[k] + rho[k-1]) / 2 = 0 holds to rounding at every interior face.  Writes the interior of exner, pressure,
+ * density (DEVICE parent arrays of centre fields); reads only interior cells, halos are neither read nor written.  Asynchronous. */
+int bz_exner_columns(bz_ctx *ctx, const double *theta, const double *qv, double p0, double *exner, double *pressure, double *density);
+/* set_hydrostatically_balanced_density!(model, spec) on the state arrays, after the update_state! that closes set! (s->theta and the halos
+ * of s->rho_d are those it left): (1) q^v = rho_q / rho_d_old, (2) the column integration of bz_exner_columns with s->theta and that q^v gives
+ * the balanced total density, (3) rho_q and the Kessler species are scaled by rho / rho_d_old, (4) rho_d = rho - (rho_q + species), (5) its
+ * halos are filled, (6) rho_u, rho_v, rho_w (ratio of the face means of new and old dry density; the wall faces of rho_w keep their values)
+ * and rho_theta are scaled by rho_d_new / rho_d_old, (7) update_state!(compute_tendencies = false).  Specific theta and q are preserved to
+ * rounding, velocities up to the face means.  Two parent-shaped scratch arrays are allocated by the first call. */
+int bz_set_hydrostatically_balanced_density(bz_ctx *ctx, const bz_compressible_state *s, double p0);
+/* Replace the reference columns of a compressible context (what set_to_mean!(::ExnerReferenceState, model) changes for the time step):
+ * HOST arrays as in bz_create_compressible — Nz + 2 Hz entries, halo levels included, taken as they are (the host fills them with the
+ * boundary conditions the reference's fields were built with: pressure and density by the bottom values of construction, no-flux on top).
+ * Every column table bzi_create derives from them is rebuilt by the function that built it: rho_r, 1 / rho_r, p_r, ln(p_r / p_st) at centres,
+ * Iz(rho_r) and 1 / Iz(rho_r) at faces; grid metrics and the (unused) reference temperature are untouched.  The stream is drained first and
+ * the configuration epoch is bumped: no recorded step (bz_graph_enable) survives.  standard_pressure must be the one of creation.  A context
+ * created without a reference (both pointers NULL at creation) returns BZ_ERR_INVALID.  Afterwards the caller redoes what depends on the
+ * reference: update_state! (bz_compressible_update_state) and, before per-operator substeps, bz_refresh_linearization. */
+int bz_set_exner_reference_state(bz_ctx *ctx, const bz_exner_reference_state *reference_state);
+
 /* ---- y-slab decomposition of the compressible path (halo exchanges only, the column solve is local) ----
  * `local_grid` is this rank's slab as in bz_create_slab.  The caller's neighbour exchange fills the y halos (Hy rows) at the
  * points listed below; x and z halos stay the library's business.  Sequence of one WS-RK3 stage:

@@ -621,6 +621,36 @@ function compute_diagnostics!(ctx, s::BzState, inputs::BzDiagnosticInputs, kinds
                 ctx, s, inputs, length(kinds), kinds, outputs), "bz_compute_diagnostics", ctx)
 end
 
+# ---- discrete hydrostatic balance of the initial and the base state (csrc/bz_balance.hip).  Written against the header; this file has
+# not been run (no Julia in the build environment). ----
+"_compute_exner_reference_3d!: one balanced column per (i, j) of the device parent arrays θ and qᵛ (C_NULL: dry), upward from p₀."
+function exner_columns!(ctx, θ::Ptr{Cvoid}, qᵛ::Ptr{Cvoid}, p₀::Real, π::Ptr{Cvoid}, p::Ptr{Cvoid}, ρ::Ptr{Cvoid})
+    check(ccall((:bz_exner_columns, libbreeze_hip), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cdouble, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+                ctx, θ, qᵛ, p₀, π, p, ρ), "bz_exner_columns", ctx)
+    return nothing
+end
+
+"set_hydrostatically_balanced_density!(model, spec) (src/AtmosphereModels/set_to_mean.jl:271-310) on the state arrays, after update_state!."
+function set_hydrostatically_balanced_density!(model::HIPAcousticModel, p₀::Real)
+    ctx = ccontext(model)
+    check(ccall((:bz_set_hydrostatically_balanced_density, libbreeze_hip), Cint, (Ptr{Cvoid}, Ref{BzCompressibleState}, Cdouble),
+                ctx, cstate(model), p₀), "bz_set_hydrostatically_balanced_density", ctx)
+    return nothing
+end
+
+"The context's reference columns again, from host arrays of Nz + 2Hz levels (parent(field)[1, 1, :] of the recomputed ExnerReferenceState,
+halos filled): the tail of set_to_mean!(::ExnerReferenceState, model); update_state! follows."
+function set_exner_reference_state!(model::HIPAcousticModel, p::Vector{Float64}, ρ::Vector{Float64})
+    ctx = ccontext(model)
+    GC.@preserve p ρ begin
+        r = BzExnerReference(model.dynamics.standard_pressure, pointer(p), pointer(ρ))
+        check(ccall((:bz_set_exner_reference_state, libbreeze_hip), Cint, (Ptr{Cvoid}, Ref{BzExnerReference}), ctx, r),
+              "bz_set_exner_reference_state", ctx)
+    end
+    OceananigansTimeSteppers.update_state!(model; compute_tendencies=false)
+    return nothing
+end
+
 "Average(field, dims = (1, 2)) of one centre or z-face parent array into a host profile of Nz (Nz + 1) values."
 function horizontal_average!(profile::Vector{Float64}, ctx, field::Ptr{Cvoid}, z_face::Bool)
     check(ccall((:bz_horizontal_average, libbreeze_hip), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Cdouble}), ctx, field, z_face, profile),
