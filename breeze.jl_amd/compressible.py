@@ -16,7 +16,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import _lib
+from . import _context, _lib
 from .grids import Bounded, Center, Face, Flat, Periodic, RectilinearGrid  # noqa: F401
 from .model import WENO, Clock, Field, _LOC
 from .thermodynamics import ThermodynamicConstants, dry_air_gas_constant, vapor_gas_constant
@@ -342,7 +342,18 @@ _ALIASES = {"θ": "θ", "theta": "θ", "θˡⁱ": "θ", "θli": "θ", "ρ": "ρ"
             "qᵗ": "q", "qt": "q", "qᵛ": "q", "qv": "q", "qᶜˡ": "qcl", "qcl": "qcl", "qʳ": "qr", "qr": "qr"}
 
 
-class CompressibleAtmosphereModel:
+def _exner_reference_struct(T, dynamics):
+    """-> (bz_exner_reference_state of the dynamics' reference state, the column arrays it points to; None without a reference state)."""
+    ref, arrays = dynamics.reference_state, None
+    br = T.bz_exner_reference_state()
+    br.standard_pressure = dynamics.standard_pressure
+    if ref is not None:
+        arrays = [np.ascontiguousarray(a, dtype=T.np_real) for a in (ref.pressure, ref.density)]
+        br.pressure, br.density = (a.ctypes.data_as(C.POINTER(T.real)) for a in arrays)
+    return br, arrays
+
+
+class CompressibleAtmosphereModel(_context.ContextOwner):
     """AtmosphereModel(grid; dynamics=CompressibleDynamics(SplitExplicitTimeDiscretization(...)), advection=WENO(order=5))
     — timestepper :AcousticRungeKutta3; coriolis = FPlane(f) and density-keyed Relaxation sponges on ρu, ρv, ρw, ρθ
     (examples/tropical_cyclone_with_rainband.jl:434-514) are the forcing terms built; closure = SmagorinskyLilly(), ScalarDiffusivity(ν, κ)
@@ -381,15 +392,9 @@ class CompressibleAtmosphereModel:
                 raise NotImplementedError("bounds-preserving WENO is implemented for order 5")
         if not isinstance(dynamics, CompressibleDynamics):
             raise TypeError("dynamics must be CompressibleDynamics")
-        from .closures import ScalarDiffusivity
-        from .forcings import SmagorinskyLilly
-        if isinstance(closure, (tuple, list)):
-            raise NotImplementedError("closure: one closure is implemented (no closure tuples)")
+        self._diffusivity = _context.check_closure(closure, f"closure = {type(closure).__name__}")
         if closure is not None:
-            if not isinstance(closure, (SmagorinskyLilly, ScalarDiffusivity)):
-                raise NotImplementedError(f"closure = {type(closure).__name__}: SmagorinskyLilly(), ScalarDiffusivity(...) and "
-                                          "VerticalScalarDiffusivity(...) are implemented")
-            if isinstance(closure, ScalarDiffusivity) and closure.vertically_implicit:
+            if self._diffusivity and closure.vertically_implicit:
                 raise NotImplementedError("closure with VerticallyImplicitTimeDiscretization: CompressibleDynamics runs the closures with "
                                           "ExplicitTimeDiscretization (the implicit substep of the reference is not built)")
             if self.lateral_walls:
@@ -399,7 +404,6 @@ class CompressibleAtmosphereModel:
             if type(self) is not CompressibleAtmosphereModel:
                 raise NotImplementedError("closure: not implemented on y-slab (distributed) compressible models")
         self.closure = closure
-        self._diffusivity = isinstance(closure, ScalarDiffusivity)
         from .forcings import FPlane, split_relaxation
         if coriolis is not None and not isinstance(coriolis, FPlane):
             raise NotImplementedError("coriolis: FPlane is implemented")
@@ -411,18 +415,12 @@ class CompressibleAtmosphereModel:
         if (coriolis is not None or self._relaxation or self._field_forcing) and type(self) is not CompressibleAtmosphereModel:
             raise NotImplementedError("Coriolis and sponges of the compressible model: single-GPU contexts")
         self.coriolis, self.forcing = coriolis, forcing
-        from .microphysics import DCMIP2016KesslerMicrophysics, SaturationAdjustment, TetensFormula
-        if microphysics is not None and not isinstance(microphysics, (DCMIP2016KesslerMicrophysics, SaturationAdjustment)):
-            raise NotImplementedError("compressible microphysics: DCMIP2016KesslerMicrophysics() and "
-                                      "SaturationAdjustment(equilibrium = WarmPhaseEquilibrium()) are implemented")
+        self._kessler = _context.check_microphysics(microphysics, "compressible microphysics: DCMIP2016KesslerMicrophysics() and "
+                                                                  "SaturationAdjustment(equilibrium = WarmPhaseEquilibrium()) are implemented")
         self.microphysics = microphysics
-        self._kessler = isinstance(microphysics, DCMIP2016KesslerMicrophysics)
-        self._sa = isinstance(microphysics, SaturationAdjustment)
-        if self._kessler:      # validate_microphysics (dcmip2016_kessler.jl:196-207)
-            tcs = thermodynamic_constants
-            if tcs is None or not isinstance(getattr(tcs, "saturation_vapor_pressure", None), TetensFormula):
-                raise ValueError("DCMIP2016KesslerMicrophysics requires `thermodynamic_constants` with a `TetensFormula` "
-                                 "saturation vapor pressure formulation.")
+        self._sa = microphysics is not None and not self._kessler
+        if self._kessler:
+            _context.check_kessler_constants(thermodynamic_constants)
         if advection is None:
             from .model import Centered
             advection = Centered(order=2)          # the reference's default
@@ -435,26 +433,13 @@ class CompressibleAtmosphereModel:
         self.device = torch.device(device)
         torch.cuda.set_device(self.device)
         self._T = T = _lib.types(grid.ftype)
-        if grid.ftype == 4:      # eltype(grid) = Float32 (examples/splitting_supercell.jl:86): the Float32 twin of the library
-            if not isinstance(advection, WENO):
-                raise NotImplementedError("Float32 grids: WENO(order = 5 | 7 | 9) is wired up")
-            self._lib = lib = _lib.load_f32()
-        else:
-            self._lib = lib = _lib.load(advection.order, getattr(advection, "ft2_hypothesis", 0))
-
-        def fld(loc):
-            return Field(grid, _LOC[loc], self.device)
-
-        dynamics.dry_density, dynamics.total_density, dynamics.pressure = fld("ccc"), fld("ccc"), fld("ccc")
-        self.momentum = {"ρu": fld("fcc"), "ρv": fld("cfc"), "ρw": fld("ccf")}
-        self.velocities = {"u": fld("fcc"), "v": fld("cfc"), "w": fld("ccf")}
-        self.potential_temperature_density, self.potential_temperature = fld("ccc"), fld("ccc")
-        self.moisture_density, self.specific_moisture, self.temperature = fld("ccc"), fld("ccc"), fld("ccc")
+        # eltype(grid) = Float32 (examples/splitting_supercell.jl:86): the Float32 twin of the library
+        self._lib = lib = _context.load_library(grid, advection, "Float32 grids: WENO(order = 5 | 7 | 9) is wired up")
+        dynamics.dry_density, dynamics.total_density, dynamics.pressure = (Field(grid, _LOC["ccc"], self.device) for _ in range(3))
+        fld = _context.allocate_common_fields(self, grid)
         self.microphysical_fields = {}
-        if self._kessler:      # materialize_microphysical_fields(::DCMIP2016KM) (dcmip2016_kessler.jl:255-290)
-            self.microphysical_fields = {k: fld("ccc") for k in ("ρqᶜˡ", "ρqʳ", "qᵛ", "qᶜˡ", "qʳ", "𝕎ʳ")}
-            self.microphysical_fields["precipitation_rate"] = torch.zeros((grid.Ny + 2 * grid.Hy, grid.Nx + 2 * grid.Hx),
-                                                                          dtype=self.potential_temperature.dtype, device=self.device)
+        if self._kessler:
+            _context.materialize_kessler_fields(self, fld)
         if dynamics._reference_given is not None:
             given = dynamics._reference_given
             if (given.Nz, given.Hz) != (grid.Nz, grid.Hz):
@@ -469,25 +454,9 @@ class CompressibleAtmosphereModel:
         self.U0, self.G = self.timestepper.U0, self.timestepper.Gn
 
         # ---- context ----
-        self._zf = np.ascontiguousarray(grid.zᶠ, dtype=T.np_real)
-        bg = T.bz_grid()
-        bg.Nx, bg.Ny, bg.Nz = grid.Nx, grid.Ny, grid.Nz
-        bg.Hx, bg.Hy, bg.Hz = grid.Hx, grid.Hy, grid.Hz
-        for d, t in enumerate(grid.topology_codes()):
-            bg.topo[d] = t
-        bg.ftype = grid.ftype
-        bg.dx, bg.dy = grid.Δx, grid.Δy
-        bg.zf = self._zf.ctypes.data_as(C.POINTER(T.real))
-        bg.regular_z = 1 if grid.regular_z else 0
-        bc = T.bz_constants(c.gravitational_acceleration, dry_air_gas_constant(c), vapor_gas_constant(c),
-                               c.dry_air_heat_capacity, c.vapor_heat_capacity)
+        bg, self._zf = _context.grid_struct(T, grid)
         ref = dynamics.reference_state
-        br = T.bz_exner_reference_state()
-        br.standard_pressure = dynamics.standard_pressure
-        self._ref_arrays = None
-        if ref is not None:
-            self._ref_arrays = [np.ascontiguousarray(a, dtype=T.np_real) for a in (ref.pressure, ref.density)]
-            br.pressure, br.density = (a.ctypes.data_as(C.POINTER(T.real)) for a in self._ref_arrays)
+        br, self._ref_arrays = _exner_reference_struct(T, dynamics)
         td = dynamics.time_discretization
         bt = T.bz_split_explicit()
         bt.substeps = 0 if td.substeps is None else td.substeps
@@ -507,65 +476,21 @@ class CompressibleAtmosphereModel:
         bt.substep_float_bytes = 4 if (sft is np.float32 and grid.ftype == 8) else 0
         if td.sponge is not None:
             bt.sponge_ramp, bt.sponge_damping_rate, bt.sponge_depth = td.sponge.ramp.code, td.sponge.damping_rate, td.sponge.depth
-        self._ctx = C.c_void_p()
-        rc = self._create_context(lib, bg, bc, br, bt, advection.order)
-        if rc != 0:
-            raise _lib.BreezeHIPError(f"bz_create_compressible failed with code {rc}")
-        self._check(lib.bz_set_stream(self._ctx, C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)), "bz_set_stream")
+        self._open_context("bz_create_compressible", bg, _context.constants_struct(T, c), br, bt, advection.order)
         self._state = self._make_state()
         self._U0, self._G = self._make_prog(self.U0), self._make_prog(self.G)
         self._sub = self.timestepper.substepper.struct()
-        if self._sa:      # materialize_microphysical_fields(::WarmPhaseSaturationAdjustment): (q^v, q^l, q^e); q^e is the moisture slot
-            self.microphysical_fields = {"qᵛ": Field(grid, _LOC["ccc"], self.device), "qˡ": Field(grid, _LOC["ccc"], self.device),
-                                         "qᵉ": self.specific_moisture}
-            sa = T.bz_saturation_adjustment(c.liquid_reference_latent_heat, c.liquid_heat_capacity,
-                                               c.energy_reference_temperature, c.triple_point_temperature,
-                                               c.triple_point_pressure, microphysics.solver.abstol,
-                                               microphysics.solver.maxiter, 0)
-            self._check(lib.bz_set_saturation_adjustment(self._ctx, C.byref(sa),
-                                                         C.c_void_p(self.microphysical_fields["qᵛ"].ptr()),
-                                                         C.c_void_p(self.microphysical_fields["qˡ"].ptr())),
-                        "bz_set_saturation_adjustment")
+        if self._sa:
+            _context.attach_saturation_adjustment(self, fld)
         if self._kessler:
-            from .microphysics import kessler_parameter_struct
-            μ = self.microphysical_fields
-            P = kessler_parameter_struct(microphysics, c, ftype=grid.ftype)
-            K = T.bz_kessler_model_fields()
-            K.cloud_liquid_density, K.rain_density = μ["ρqᶜˡ"].ptr(), μ["ρqʳ"].ptr()
-            K.U0_cloud_liquid_density, K.U0_rain_density = self.U0["ρqᶜˡ"].ptr(), self.U0["ρqʳ"].ptr()
-            K.G_cloud_liquid_density, K.G_rain_density = self.G["ρqᶜˡ"].ptr(), self.G["ρqʳ"].ptr()
-            K.vapor_mass_fraction, K.cloud_liquid_mass_fraction, K.rain_mass_fraction = μ["qᵛ"].ptr(), μ["qᶜˡ"].ptr(), μ["qʳ"].ptr()
-            K.rain_terminal_velocity, K.precipitation_rate = μ["𝕎ʳ"].ptr(), μ["precipitation_rate"].data_ptr()
-            self._check(lib.bz_set_kessler_microphysics(self._ctx, C.byref(P), C.byref(K), dynamics.standard_pressure),
-                        "bz_set_kessler_microphysics")
+            _context.attach_kessler(self, dynamics.standard_pressure)
         if coriolis is not None:      # the f-plane term of the slow momentum tendencies (bz_set_forcings with coriolis_f alone)
             Fc = T.bz_column_forcings()
             Fc.coriolis_f = coriolis.f
             self._check(lib.bz_set_forcings(self._ctx, C.byref(Fc)), "bz_set_forcings")
-        if self._relaxation:
-            from .forcings import materialize_relaxation
-            Rx, self._relaxation_keepalive = materialize_relaxation(grid, self._relaxation, "LiquidIcePotentialTemperature", T)
-            self._check(lib.bz_set_relaxation(self._ctx, C.byref(Rx)), "bz_set_relaxation")
-        from .forcings import materialize_field_forcing
-        self.thermodynamic_forcing_field, _spec = materialize_field_forcing(grid, self._field_forcing, "LiquidIcePotentialTemperature", self.device)
-        if self.thermodynamic_forcing_field is not None:
-            self._check(lib.bz_set_field_forcing(self._ctx, C.c_void_p(self.thermodynamic_forcing_field.ptr()), _spec), "bz_set_field_forcing")
-        self.closure_fields = {}
-        if self._diffusivity:      # no closure fields: ν and κ are numbers or the user's own centre fields (dcmip2016_tc.jl:277-292)
-            Kf = {}
-            for name, value in (("ν", closure.ν), ("κ", closure.κ)):
-                if isinstance(value, Field):
-                    if value.grid is not grid or value.parent.device != self.device or value.parent.dtype != self.potential_temperature.parent.dtype:
-                        raise ValueError(f"closure {name}: the field must live on the model's grid, device and float type")
-                    Kf[name] = value
-            sd = T.bz_scalar_diffusivity(closure.formulation, 0, 0.0 if "ν" in Kf else closure.ν, 0.0 if "κ" in Kf else closure.κ)
-            self._diffusivity_fields = Kf      # keeps the arrays the context reads alive
-            self._check(lib.bz_set_scalar_diffusivity(self._ctx, C.byref(sd), C.c_void_p(Kf["ν"].ptr() if "ν" in Kf else None),
-                                                      C.c_void_p(Kf["κ"].ptr() if "κ" in Kf else None)), "bz_set_scalar_diffusivity")
-        elif closure is not None:      # build_closure_fields: νₑ (atmosphere_model.jl:276)
-            self.closure_fields = {"νₑ": fld("ccc")}
-            cl = T.bz_smagorinsky_lilly(closure.C, closure.Cb, closure.Pr)
-            self._check(lib.bz_set_closure(self._ctx, C.byref(cl), C.c_void_p(self.closure_fields["νₑ"].ptr())), "bz_set_closure")
+        _context.attach_relaxation(self, self._relaxation, "LiquidIcePotentialTemperature")
+        _context.attach_field_forcing(self, self._field_forcing, "LiquidIcePotentialTemperature")
+        _context.attach_closure(self, fld)      # (explicit only: the vertically implicit discretisation was refused above)
         if self.lateral_walls:      # is_active_open_bc of the four sides (acoustic_substepping.jl:1339-1361)
             bu, bv = self.boundary_conditions.get("ρu"), self.boundary_conditions.get("ρv")
             sides = [is_active_open_bc(getattr(b, k, None)) and grid.topology[d] == Bounded
@@ -585,9 +510,6 @@ class CompressibleAtmosphereModel:
 
     def _exchange(self, tensors):
         """y-halo exchange hook: nothing to do on a single GPU (the kernels wrap periodically)."""
-
-    def _check(self, rc, what):
-        _lib.check(self._lib, self._ctx, rc, what)
 
     def prognostic_fields(self):
         out = {"ρᵈ": self.dynamics.dry_density, "ρu": self.momentum["ρu"], "ρv": self.momentum["ρv"],
@@ -612,46 +534,11 @@ class CompressibleAtmosphereModel:
         p.rho_d, p.rho_u, p.rho_v, p.rho_w, p.rho_theta, p.rho_q = (d[k].ptr() for k in ("ρᵈ", "ρu", "ρv", "ρw", "ρθ", "ρq"))
         return p
 
-    def __del__(self):
-        try:
-            if getattr(self, "_ctx", None):
-                self._lib.bz_destroy(self._ctx)
-                self._ctx = None
-        except Exception:
-            pass
-
     def set(self, **kw):
         return set_(self, **kw)
 
     def time_step(self, Δt):
         return time_step_(self, Δt)
-
-    def synchronize(self):
-        self._check(self._lib.bz_sync(self._ctx), "bz_sync")
-
-    def graph_enable(self, on=True):
-        """hipGraph replay of whole steps (csrc/bz_graph.hip); opt-in, bit-identical to launched steps."""
-        self._check(self._lib.bz_graph_enable(self._ctx, 1 if on else 0), "bz_graph_enable")
-
-    def graph_info(self):
-        """(enabled, steps recorded, steps replayed)"""
-        en, cap, rep = C.c_int32(), C.c_int64(), C.c_int64()
-        self._check(self._lib.bz_graph_info(self._ctx, C.byref(en), C.byref(cap), C.byref(rep)), "bz_graph_info")
-        return bool(en.value), cap.value, rep.value
-
-    def profile_enable(self, on=True):
-        self._check(self._lib.bz_profile_enable(self._ctx, 1 if on else 0), "bz_profile_enable")
-
-    def profile_reset(self):
-        self._check(self._lib.bz_profile_reset(self._ctx), "bz_profile_reset")
-
-    def profile(self):
-        out = {}
-        for i in range(self._lib.bz_profile_count(self._ctx)):
-            name, ms, n = C.c_char_p(), self._T.real(), C.c_int64()
-            self._check(self._lib.bz_profile_get(self._ctx, i, C.byref(name), C.byref(ms), C.byref(n)), "bz_profile_get")
-            out[name.value.decode()] = (ms.value, n.value)
-        return out
 
     def stage_substeps(self, Δt, β):
         n, dτ = C.c_int32(), self._T.real()
@@ -754,11 +641,7 @@ def set_to_mean_(reference_state, model):
     θ = horizontal_average(model, model.potential_temperature).astype(np.float64)
     qv = horizontal_average(model, specific_humidity(model)).astype(np.float64)
     reference_state.set_profiles_(θ, qv)
-    T = model._T
-    model._ref_arrays = [np.ascontiguousarray(a, dtype=T.np_real) for a in (reference_state.pressure, reference_state.density)]
-    br = T.bz_exner_reference_state()
-    br.standard_pressure = model.dynamics.standard_pressure
-    br.pressure, br.density = (a.ctypes.data_as(C.POINTER(T.real)) for a in model._ref_arrays)
+    br, model._ref_arrays = _exner_reference_struct(model._T, model.dynamics)
     model._check(model._lib.bz_set_exner_reference_state(model._ctx, C.byref(br)), "bz_set_exner_reference_state")
     update_state_(model, compute_tendencies=False)
 
@@ -900,10 +783,7 @@ class SlabCompressibleModel(CompressibleAtmosphereModel):
         "local:<name>" — the library owns the communicator (csrc/bz_comm.hip) and `time_step` is one C call per step."""
         import torch
         from .distributed import LibraryComm, SlabDecomposition, attach_library_transport
-        if global_grid.topology != (Periodic, Periodic, Bounded):
-            raise NotImplementedError("slab decomposition implements topology (Periodic, Periodic, Bounded)")
-        if global_grid.Ny % world:
-            raise ValueError(f"Ny={global_grid.Ny} is not divisible by {world} ranks")
+        grid = _context.slab_grid(global_grid, rank, world)
         self.global_grid = G = global_grid
         self.rank, self.world = rank, world
         sft = kw.get("substep_floattype")
@@ -911,16 +791,10 @@ class SlabCompressibleModel(CompressibleAtmosphereModel):
             # the library-owned step moves the Float32 rows of the working fields (csrc/bz_comm.hip: halo_exchange, half); the
             # Python-issued exchange assumes the grid's real
             raise NotImplementedError('substep_floattype = Float32 on y-slabs: transport "rccl" or "local:<name>"')
-        Ny = G.Ny // world
-        y0 = G.yᶠ[0] + rank * Ny * G.Δy
-        z = (G.zᶠ[0], G.zᶠ[-1]) if G.regular_z else G.zᶠ
-        grid = RectilinearGrid((G.Nx, Ny, G.Nz), x=(G.xᶠ[0], G.xᶠ[0] + G.Nx * G.Δx), y=(y0, y0 + Ny * G.Δy), z=z,
-                               halo=(G.Hx, G.Hy, G.Hz), float_type=G.float_type)      # eltype(grid) travels with the slab
-        grid.Δx, grid.Δy = G.Δx, G.Δy          # bit-identical spacings on every rank
         self.decomp = None                     # set after construction: the constructor's set-up is rank-local
         self.transport = transport
         library = transport != "torch"
-        self._pending_decomp = LibraryComm(self) if library else (decomp or SlabDecomposition(G.Nx, Ny, G.Nz, G.Hy, rank, world, group))
+        self._pending_decomp = LibraryComm(self) if library else (decomp or SlabDecomposition(G.Nx, grid.Ny, G.Nz, G.Hy, rank, world, group))
         dev = device if device is not None else f"cuda:{torch.cuda.current_device()}"
         super().__init__(grid, dynamics, advection=advection, device=dev, **kw)
         if library:
@@ -941,12 +815,6 @@ class SlabCompressibleModel(CompressibleAtmosphereModel):
         self._u_buf = (sub.momentum_perturbation_u.parent, self._up2.parent)
         self._direct = isinstance(self.dynamics.time_discretization.damping, DirectDivergenceDamping)
         self._exchange([self.dynamics.pressure.parent])
-
-    def comm_info(self):
-        """(transport name, bytes this rank has sent, number of exchanges) of the library-owned communicator."""
-        name, nbytes, nex = C.c_char_p(), C.c_int64(), C.c_int32()
-        self._check(self._lib.bz_comm_info(self._ctx, C.byref(name), C.byref(nbytes), C.byref(nex)), "bz_comm_info")
-        return name.value.decode(), nbytes.value, nex.value
 
     def _create_context(self, lib, bg, bc, br, bt, order):
         return lib.bz_create_compressible_slab(C.byref(self._ctx), C.byref(bg), C.byref(bc), C.byref(br), C.byref(bt), order,

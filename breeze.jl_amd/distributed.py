@@ -24,13 +24,9 @@ one GPU); the round-end scaling run is its first exposure.
 """
 import ctypes as C
 
-import numpy as np
-
-from . import _lib
-from .grids import Bounded, Center, Face, Periodic, RectilinearGrid
+from . import _context, _lib
 from .model import AnelasticDynamics, AtmosphereModel
-from .thermodynamics import (ReferenceState, ThermodynamicConstants, dry_air_gas_constant,
-                             vapor_gas_constant)
+from .thermodynamics import ReferenceState, ThermodynamicConstants
 
 
 class SlabDecomposition:
@@ -258,10 +254,6 @@ class SlabStepper:
             self.stage(dt, alpha, n == 0)
 
 
-_LOC = {"ccc": (Center, Center, Center), "fcc": (Face, Center, Center),
-        "cfc": (Center, Face, Center), "ccf": (Center, Center, Face)}
-
-
 def attach_library_transport(self, transport, group):
     """Give the slab context `self._ctx` a library-owned communicator (csrc/bz_comm.hip): "rccl" (unique id made on rank 0 and
     broadcast over the torch.distributed group) or "local:<name>" (in-process transport between contexts of one process)."""
@@ -301,6 +293,10 @@ def attach_library_transport(self, transport, group):
     self._check(rc, "bz_comm_init_rccl")
 
 
+def _create_slab_context(self, lib, bg, bc, br, order):
+    """`_create_context` of the two anelastic slab models"""
+    return lib.bz_create_slab(C.byref(self._ctx), C.byref(bg), C.byref(bc), C.byref(br), order, self.world, self.rank)
+
 
 class LibraryComm:
     """Stand-in for SlabDecomposition when the library owns the communicator: the only thing the host still asks for is a y-halo
@@ -328,24 +324,14 @@ class LibrarySlabAtmosphereModel(AtmosphereModel):
     def __init__(self, global_grid, rank, world, transport="rccl", group=None, surface_pressure=101325, potential_temperature=288,
                  standard_pressure=1e5, thermodynamic_constants=None, device=None, **kw):
         import torch
-        G = global_grid
         from .model import PrescribedDynamics
         if isinstance(kw.get("dynamics"), PrescribedDynamics):
             raise NotImplementedError("AtmosphereModel(dynamics = PrescribedDynamics(...)): y-slab (distributed) models are not implemented")
-        if G.topology != (Periodic, Periodic, Bounded):
-            raise NotImplementedError("slab decomposition implements topology (Periodic, Periodic, Bounded)")
-        if G.Ny % world:
-            raise ValueError(f"Ny={G.Ny} is not divisible by {world} ranks")
+        grid = _context.slab_grid(global_grid, rank, world)
         if transport == "torch":
             raise ValueError('LibrarySlabAtmosphereModel runs on the library-owned communicator: transport "rccl" or "local:<name>"')
-        self.global_grid, self.rank, self.world, self.transport = G, rank, world, transport
+        self.global_grid, self.rank, self.world, self.transport = global_grid, rank, world, transport
         self._comm_ready = False
-        Ny = G.Ny // world
-        y0 = G.yᶠ[0] + rank * Ny * G.Δy
-        z = (G.zᶠ[0], G.zᶠ[-1]) if G.regular_z else G.zᶠ
-        grid = RectilinearGrid((G.Nx, Ny, G.Nz), x=(G.xᶠ[0], G.xᶠ[0] + G.Nx * G.Δx), y=(y0, y0 + Ny * G.Δy), z=z,
-                               halo=(G.Hx, G.Hy, G.Hz), float_type=G.float_type)      # eltype(grid) travels with the slab
-        grid.Δx, grid.Δy = G.Δx, G.Δy          # bit-identical spacings on every rank
         c = thermodynamic_constants or ThermodynamicConstants()
         ref = ReferenceState(grid, c, surface_pressure, potential_temperature, standard_pressure)
         dev = device if device is not None else f"cuda:{torch.cuda.current_device()}"
@@ -354,8 +340,7 @@ class LibrarySlabAtmosphereModel(AtmosphereModel):
         self._comm_ready = True
         self.set(θ=ref.potential_temperature)
 
-    def _create_context(self, lib, bg, bc, br, order):
-        return lib.bz_create_slab(C.byref(self._ctx), C.byref(bg), C.byref(bc), C.byref(br), order, self.world, self.rank)
+    _create_context = _create_slab_context
 
     def _finish_set(self, enforce_mass_conservation):
         if not self._comm_ready:
@@ -394,14 +379,8 @@ class LibrarySlabAtmosphereModel(AtmosphereModel):
         self._check(self._lib.bz_comm_update_state_and_project(self._ctx, C.byref(self._state), C.byref(self._G), 1.0, 0),
                     "bz_comm_update_state_and_project")
 
-    def comm_info(self):
-        """(transport name, bytes this rank has sent, number of exchanges) of the library-owned communicator."""
-        name, nbytes, nex = C.c_char_p(), C.c_int64(), C.c_int32()
-        self._check(self._lib.bz_comm_info(self._ctx, C.byref(name), C.byref(nbytes), C.byref(nex)), "bz_comm_info")
-        return name.value.decode(), nbytes.value, nex.value
 
-
-class SlabAtmosphereModel(SlabStepper):
+class SlabAtmosphereModel(SlabStepper, _context.ContextOwner):
     """AtmosphereModel on one y-slab of a (Periodic, Periodic, Bounded) global grid: rank r of `world` owns rows
     [r*Ny/world, (r+1)*Ny/world).  Same fields, kernels and call order as `AtmosphereModel`; halos in y and the
     Poisson transposes go through torch.distributed (backend "nccl" = RCCL on ROCm)."""
@@ -416,67 +395,36 @@ class SlabAtmosphereModel(SlabStepper):
              "local:<name>"  the C library's in-process transport (ranks = threads of this process sharing one or more GPUs)
              "torch"         this module's Python orchestration over torch.distributed (SlabStepper; also what the CPU tests drive)"""
         import torch
-        from .model import Clock, Field, WENO
-        if global_grid.topology != (Periodic, Periodic, Bounded):
-            raise NotImplementedError("slab decomposition implements topology (Periodic, Periodic, Bounded)")
+        from .model import Clock, Field
+        _context.check_slab_topology(global_grid)      # (slab_grid checks it again: here only so that it still comes before the advection check)
         if advection is None or getattr(advection, "order", None) != 5:
             raise NotImplementedError("the HIP path requires advection=WENO(order=5)")
-        if global_grid.Ny % world:
-            raise ValueError(f"Ny={global_grid.Ny} is not divisible by {world} ranks")
+        grid = _context.slab_grid(global_grid, rank, world)
         if not torch.cuda.is_available():
             raise RuntimeError("SlabAtmosphereModel needs a GPU: the HIP path has no CPU fallback")
         self.global_grid = G = global_grid
         if G.ftype != 8:
             raise NotImplementedError('SlabAtmosphereModel(transport="torch") is the Float64 cross-check of the library-owned step; '
                                       "Float32 grids decompose through LibrarySlabAtmosphereModel")
-        self.rank, self.world = rank, world
-        Ny = G.Ny // world
-        y0 = G.yᶠ[0] + rank * Ny * G.Δy
-        z = (G.zᶠ[0], G.zᶠ[-1]) if G.regular_z else G.zᶠ
-        self.grid = grid = RectilinearGrid((G.Nx, Ny, G.Nz), x=(G.xᶠ[0], G.xᶠ[0] + G.Nx * G.Δx),
-                                           y=(y0, y0 + Ny * G.Δy), z=z, halo=(G.Hx, G.Hy, G.Hz))
-        grid.Δx, grid.Δy = G.Δx, G.Δy          # bit-identical spacings on every rank
+        self.rank, self.world, self.grid = rank, world, grid
         SlabStepper.__init__(self, getattr(self, "_decomp_override", None) or
-                             SlabDecomposition(G.Nx, Ny, G.Nz, G.Hy, rank, world, group))
+                             SlabDecomposition(G.Nx, grid.Ny, G.Nz, G.Hy, rank, world, group))
         self.thermodynamic_constants = c = thermodynamic_constants or ThermodynamicConstants()
         self.reference_state = ref = ReferenceState(grid, c, surface_pressure, potential_temperature, standard_pressure)
         self.clock = Clock()
         self.device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
         torch.cuda.set_device(self.device)
-        self._lib = lib = _lib.load()
-
-        def fld(loc):
-            return Field(grid, _LOC[loc], self.device)
-
-        self.momentum = {"ρu": fld("fcc"), "ρv": fld("cfc"), "ρw": fld("ccf")}
-        self.velocities = {"u": fld("fcc"), "v": fld("cfc"), "w": fld("ccf")}
-        self.potential_temperature_density, self.potential_temperature = fld("ccc"), fld("ccc")
-        self.moisture_density, self.specific_moisture = fld("ccc"), fld("ccc")
-        self.temperature, self.pressure_anomaly = fld("ccc"), fld("ccc")
+        self._T = T = _lib.types(grid.ftype)
+        self._lib = _lib.load()
+        fld = _context.allocate_common_fields(self, grid)
+        self.pressure_anomaly = fld("ccc")
         prog = self.prognostic_fields()
         self.U0 = {k: Field(grid, f.loc, self.device) for k, f in prog.items()}
         self.G = {k: Field(grid, f.loc, self.device) for k, f in prog.items()}
 
-        self._zf = np.ascontiguousarray(grid.zᶠ, dtype=np.float64)
-        bg = _lib.bz_grid()
-        bg.Nx, bg.Ny, bg.Nz = grid.Nx, grid.Ny, grid.Nz
-        bg.Hx, bg.Hy, bg.Hz = grid.Hx, grid.Hy, grid.Hz
-        for dd, t in enumerate(grid.topology_codes()):
-            bg.topo[dd] = t
-        bg.ftype = 8
-        bg.dx, bg.dy = grid.Δx, grid.Δy
-        bg.zf = self._zf.ctypes.data_as(C.POINTER(C.c_double))
-        bg.regular_z = 1 if grid.regular_z else 0
-        bc = _lib.bz_constants(c.gravitational_acceleration, dry_air_gas_constant(c), vapor_gas_constant(c),
-                               c.dry_air_heat_capacity, c.vapor_heat_capacity)
-        self._ref_arrays = [np.ascontiguousarray(a, dtype=np.float64) for a in (ref.density, ref.pressure, ref.temperature)]
-        br = _lib.bz_reference_state(ref.surface_pressure, ref.potential_temperature, ref.standard_pressure,
-                                     *[a.ctypes.data_as(C.POINTER(C.c_double)) for a in self._ref_arrays])
-        self._ctx = C.c_void_p()
-        rc = lib.bz_create_slab(C.byref(self._ctx), C.byref(bg), C.byref(bc), C.byref(br), advection.order, world, rank)
-        if rc != 0:
-            raise _lib.BreezeHIPError(f"bz_create_slab failed with code {rc}")
-        self._check(lib.bz_set_stream(self._ctx, C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)), "bz_set_stream")
+        bg, self._zf = _context.grid_struct(T, grid)
+        br, self._ref_arrays = _context.reference_struct(T, ref)
+        self._open_context("bz_create_slab", bg, _context.constants_struct(T, c), br, advection.order)
         self._state, self._U0, self._G = self._make_state(), self._make_prog(self.U0), self._make_prog(self.G)
         if getattr(self.decomp, "pack", None) is None and hasattr(self.decomp, "_pack"):
             self.decomp.pack = self._device_pack
@@ -491,15 +439,7 @@ class SlabAtmosphereModel(SlabStepper):
     def _attach_library_transport(self, transport, group):
         attach_library_transport(self, transport, group)
 
-    def comm_info(self):
-        """(transport name, bytes this rank has sent, number of exchanges) of the library-owned communicator."""
-        name, nbytes, nex = C.c_char_p(), C.c_int64(), C.c_int32()
-        self._check(self._lib.bz_comm_info(self._ctx, C.byref(name), C.byref(nbytes), C.byref(nex)), "bz_comm_info")
-        return name.value.decode(), nbytes.value, nex.value
-
-    # plumbing shared with AtmosphereModel -------------------------------------------------
-    def _check(self, rc, what):
-        _lib.check(self._lib, self._ctx, rc, what)
+    _create_context = _create_slab_context
 
     def prognostic_fields(self):
         return {"ρu": self.momentum["ρu"], "ρv": self.momentum["ρv"], "ρw": self.momentum["ρw"],
@@ -519,31 +459,6 @@ class SlabAtmosphereModel(SlabStepper):
         p = _lib.bz_prognostic()
         p.rho_u, p.rho_v, p.rho_w, p.rho_theta, p.rho_q = (d[k].ptr() for k in ("ρu", "ρv", "ρw", "ρθ", "ρq"))
         return p
-
-    def __del__(self):
-        try:
-            if getattr(self, "_ctx", None):
-                self._lib.bz_destroy(self._ctx)
-                self._ctx = None
-        except Exception:
-            pass
-
-    def synchronize(self):
-        self._check(self._lib.bz_sync(self._ctx), "bz_sync")
-
-    def profile_enable(self, on=True):
-        self._check(self._lib.bz_profile_enable(self._ctx, 1 if on else 0), "bz_profile_enable")
-
-    def profile_reset(self):
-        self._check(self._lib.bz_profile_reset(self._ctx), "bz_profile_reset")
-
-    def profile(self):
-        out = {}
-        for i in range(self._lib.bz_profile_count(self._ctx)):
-            name, ms, n = C.c_char_p(), C.c_double(), C.c_int64()
-            self._check(self._lib.bz_profile_get(self._ctx, i, C.byref(name), C.byref(ms), C.byref(n)), "bz_profile_get")
-            out[name.value.decode()] = (ms.value, n.value)
-        return out
 
     # SlabStepper backend ---------------------------------------------------------------------
     def momentum_fields(self):

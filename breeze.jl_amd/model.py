@@ -15,10 +15,9 @@ import ctypes as C
 
 import numpy as np
 
-from . import _lib
+from . import _context, _lib
 from .grids import Bounded, Center, Face, Flat, Periodic, RectilinearGrid
-from .thermodynamics import (ReferenceState, ThermodynamicConstants, dry_air_gas_constant,
-                             vapor_gas_constant)
+from .thermodynamics import ReferenceState, ThermodynamicConstants, dry_air_gas_constant, vapor_gas_constant
 
 
 class Centered:
@@ -289,7 +288,7 @@ _ALIASES = {"θ": "θ", "theta": "θ", "θˡⁱ": "θ", "ρθ": "ρθ", "rho_the
             "θli": "θ", "ρqt": "ρq", "ρqv": "ρq"}
 
 
-class AtmosphereModel:
+class AtmosphereModel(_context.ContextOwner):
     """AtmosphereModel(grid; dynamics=AnelasticDynamics(ReferenceState(grid)), advection=WENO(order=5),
     formulation=:LiquidIcePotentialTemperature, thermodynamic_constants, timestepper=:SSPRungeKutta3).
 
@@ -339,13 +338,7 @@ class AtmosphereModel:
         self.formulation = formulation
         if timestepper not in ("SSPRungeKutta3", ":SSPRungeKutta3"):
             raise NotImplementedError("only SSPRungeKutta3 is implemented")
-        from .forcings import SmagorinskyLilly
-        from .closures import ScalarDiffusivity
-        if isinstance(closure, (tuple, list)):
-            raise NotImplementedError("closure: one closure is implemented (no closure tuples)")
-        if closure is not None and not isinstance(closure, (SmagorinskyLilly, ScalarDiffusivity)):
-            raise NotImplementedError("closure: SmagorinskyLilly(), ScalarDiffusivity(...) and VerticalScalarDiffusivity(...) are implemented")
-        self._diffusivity = isinstance(closure, ScalarDiffusivity)
+        self._diffusivity = _context.check_closure(closure)
         if self._diffusivity and any("Slab" in k.__name__ for k in type(self).__mro__):      # the y-slab models of distributed.py
             raise NotImplementedError("closure = ScalarDiffusivity / VerticalScalarDiffusivity: not implemented on y-slab (distributed) models")
         if self._diffusivity and (bounded_x or bounded_y):
@@ -353,20 +346,13 @@ class AtmosphereModel:
                                       "(Bounded x / Bounded y)")
         self.closure = closure
         self.coriolis, self.forcing, self.boundary_conditions = coriolis, forcing, boundary_conditions
-        from .microphysics import DCMIP2016KesslerMicrophysics, SaturationAdjustment, TetensFormula
-        if microphysics is not None and not isinstance(microphysics, (SaturationAdjustment, DCMIP2016KesslerMicrophysics)):
-            raise NotImplementedError("microphysics: SaturationAdjustment(equilibrium = WarmPhaseEquilibrium()) and "
-                                      "DCMIP2016KesslerMicrophysics() are implemented")
+        self._kessler = _context.check_microphysics(microphysics, "microphysics: SaturationAdjustment(equilibrium = WarmPhaseEquilibrium()) and "
+                                                                  "DCMIP2016KesslerMicrophysics() are implemented")
         if microphysics is not None and formulation != "LiquidIcePotentialTemperature":
             raise NotImplementedError("microphysics is implemented for the potential-temperature formulation")
         self.microphysics = microphysics
-        self._kessler = isinstance(microphysics, DCMIP2016KesslerMicrophysics)
-        if self._kessler:      # validate_microphysics (dcmip2016_kessler.jl:196-207)
-            tcs = thermodynamic_constants
-            if tcs is None or not isinstance(getattr(tcs, "saturation_vapor_pressure", None), TetensFormula):
-                raise ValueError("DCMIP2016KesslerMicrophysics requires `thermodynamic_constants` with a `TetensFormula` "
-                                 "saturation vapor pressure formulation. Construct the model with, e.g., "
-                                 "`thermodynamic_constants = ThermodynamicConstants(saturation_vapor_pressure = TetensFormula())`.")
+        if self._kessler:
+            _context.check_kessler_constants(thermodynamic_constants)
         _named = set(str(k).lstrip(":") for k in advection) if isinstance(advection, dict) else set()
         _tracer_names = tuple(str(n).lstrip(":") for n in ((tracers,) if isinstance(tracers, str) else tracers))
         advection, self._bounded_advection, self._scalar_order, _unnamed_differ = _split_advection(advection, _tracer_names)
@@ -401,26 +387,10 @@ class AtmosphereModel:
         self.device = torch.device(device)
         torch.cuda.set_device(self.device)
         self._T = T = _lib.types(grid.ftype)
-        if grid.ftype == 4:
-            if not isinstance(advection, WENO):
-                raise NotImplementedError("Float32 grids: WENO(order = 5 | 7 | 9) is wired up on the host side")
-            self._lib = lib = _lib.load_f32()
-        else:
-            self._lib = lib = _lib.load(advection.order, getattr(advection, "ft2_hypothesis", 0))
-
-        def fld(loc):
-            return Field(grid, _LOC[loc], self.device)
-
-        # materialize_momentum_and_velocities, formulation, moisture, diagnostics
-        self.momentum = {} if kin else {"ρu": fld("fcc"), "ρv": fld("cfc"), "ρw": fld("ccf")}      # a kinematic model has no prognostic momentum
-        self.velocities = {"u": fld("fcc"), "v": fld("cfc"), "w": fld("ccf")}
+        self._lib = lib = _context.load_library(grid, advection, "Float32 grids: WENO(order = 5 | 7 | 9) is wired up on the host side")
+        fld = _context.allocate_common_fields(self, grid, momentum=not kin)      # a kinematic model has no prognostic momentum
         # :StaticEnergy keeps rho_e / e in the thermodynamic slots (energy_density, specific_energy)
-        self.potential_temperature_density = fld("ccc")
-        self.potential_temperature = fld("ccc")
         self.energy_density, self.specific_energy = self.potential_temperature_density, self.potential_temperature
-        self.moisture_density = fld("ccc")
-        self.specific_moisture = fld("ccc")
-        self.temperature = fld("ccc")
         dynamics.pressure_anomaly = None if kin else fld("ccc")
         # the context owns the Fourier-tridiagonal solver of an anelastic model; a kinematic model has none
         self.pressure_solver = None if kin else "FourierTridiagonalPoissonSolver"
@@ -430,10 +400,8 @@ class AtmosphereModel:
                    (*self.velocities.values(), self.potential_temperature, self.specific_moisture, self.temperature, dynamics.pressure_anomaly)):
             _f._owner = weakref.ref(self)
         self.microphysical_fields = {}
-        if self._kessler:      # materialize_microphysical_fields(::DCMIP2016KM) (dcmip2016_kessler.jl:255-290)
-            self.microphysical_fields = {k: fld("ccc") for k in ("ρqᶜˡ", "ρqʳ", "qᵛ", "qᶜˡ", "qʳ", "𝕎ʳ")}
-            self.microphysical_fields["precipitation_rate"] = torch.zeros((grid.Ny + 2 * grid.Hy, grid.Nx + 2 * grid.Hx),
-                                                                          dtype=self.momentum["ρu"].parent.dtype, device=self.device)
+        if self._kessler:
+            _context.materialize_kessler_fields(self, fld)
         # tracers = (:a, :b): prognostic density fields model.tracers[name]; the specific field sits beside it
         tracers = (tracers,) if isinstance(tracers, str) else tuple(tracers)
         self.tracers = {str(n).lstrip(":"): fld("ccc") for n in tracers}
@@ -444,100 +412,38 @@ class AtmosphereModel:
 
         # ---- context: pressure solver, column tables ----
         ref = dynamics.reference_state
-        self._zf = np.ascontiguousarray(grid.zᶠ, dtype=T.np_real)
-        bg = T.bz_grid()
-        bg.Nx, bg.Ny, bg.Nz = grid.Nx, grid.Ny, grid.Nz
-        bg.Hx, bg.Hy, bg.Hz = grid.Hx, grid.Hy, grid.Hz
-        for d, t in enumerate(grid.topology_codes()):
-            bg.topo[d] = t
-        bg.ftype = grid.ftype
-        bg.dx, bg.dy = grid.Δx, grid.Δy
-        bg.zf = self._zf.ctypes.data_as(C.POINTER(T.real))
-        bg.regular_z = 1 if grid.regular_z else 0
-        bc = T.bz_constants(c.gravitational_acceleration, dry_air_gas_constant(c), vapor_gas_constant(c),
-                            c.dry_air_heat_capacity, c.vapor_heat_capacity)
-        self._ref_arrays = [np.ascontiguousarray(a, dtype=T.np_real)
-                            for a in (ref.density, ref.pressure, ref.temperature)]
-        br = T.bz_reference_state(ref.surface_pressure, ref.potential_temperature, ref.standard_pressure,
-                                  *[a.ctypes.data_as(C.POINTER(T.real)) for a in self._ref_arrays])
-        self._ctx = C.c_void_p()
-        rc = self._create_context(lib, bg, bc, br, advection.order)
-        if rc != 0:
-            raise _lib.BreezeHIPError(f"bz_create failed with code {rc}")
-        self._check(lib.bz_set_stream(self._ctx, C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)),
-                    "bz_set_stream")
+        bg, self._zf = _context.grid_struct(T, grid)
+        br, self._ref_arrays = _context.reference_struct(T, ref)
+        self._open_context("bz_create", bg, _context.constants_struct(T, c), br, advection.order)
         if kin:
             self._check(lib.bz_set_prescribed_dynamics(self._ctx, 1 if dynamics.divergence_correction else 0), "bz_set_prescribed_dynamics")
         if formulation == "StaticEnergy":
             self._check(lib.bz_set_formulation(self._ctx, 1), "bz_set_formulation")
         if self._scalar_order != advection.order:      # momentum_advection and scalar_advection of different orders
             self._check(lib.bz_set_scalar_advection_order(self._ctx, self._scalar_order), "bz_set_scalar_advection_order")
-        # materialize_microphysical_fields(::WarmPhaseSaturationAdjustment): (q^v, q^l, q^e); q^e is the specific moisture slot
         if self._kessler:
-            from .microphysics import kessler_parameter_struct
-            μ = self.microphysical_fields
-            P = kessler_parameter_struct(microphysics, c, ftype=grid.ftype)
-            K = _lib.bz_kessler_model_fields()
-            K.cloud_liquid_density, K.rain_density = μ["ρqᶜˡ"].ptr(), μ["ρqʳ"].ptr()
-            K.U0_cloud_liquid_density, K.U0_rain_density = self.U0["ρqᶜˡ"].ptr(), self.U0["ρqʳ"].ptr()
-            K.G_cloud_liquid_density, K.G_rain_density = self.G["ρqᶜˡ"].ptr(), self.G["ρqʳ"].ptr()
-            K.vapor_mass_fraction, K.cloud_liquid_mass_fraction, K.rain_mass_fraction = μ["qᵛ"].ptr(), μ["qᶜˡ"].ptr(), μ["qʳ"].ptr()
-            K.rain_terminal_velocity, K.precipitation_rate = μ["𝕎ʳ"].ptr(), μ["precipitation_rate"].data_ptr()
-            self._check(lib.bz_set_kessler_microphysics(self._ctx, C.byref(P), C.byref(K), ref.standard_pressure),
-                        "bz_set_kessler_microphysics")
+            _context.attach_kessler(self, ref.standard_pressure)
         elif microphysics is not None:
-            self.microphysical_fields = {"qᵛ": fld("ccc"), "qˡ": fld("ccc"), "qᵉ": self.specific_moisture}
-            sa = T.bz_saturation_adjustment(c.liquid_reference_latent_heat, c.liquid_heat_capacity,
-                                               c.energy_reference_temperature, c.triple_point_temperature,
-                                               c.triple_point_pressure, microphysics.solver.abstol,
-                                               microphysics.solver.maxiter, 0)
-            self._check(lib.bz_set_saturation_adjustment(self._ctx, C.byref(sa),
-                                                         C.c_void_p(self.microphysical_fields["qᵛ"].ptr()),
-                                                         C.c_void_p(self.microphysical_fields["qˡ"].ptr())),
-                        "bz_set_saturation_adjustment")
+            _context.attach_saturation_adjustment(self, fld)
         if self.tracers:
             arr = (_lib.bz_tracer_fields * len(self.tracers))()
             for t, n in enumerate(self.tracers):
                 arr[t].density, arr[t].specific = self.tracers[n].ptr(), self.specific_tracers[n].ptr()
                 arr[t].U0, arr[t].G = self.U0[n].ptr(), self.G[n].ptr()
             self._check(lib.bz_set_tracers(self._ctx, len(self.tracers), arr), "bz_set_tracers")
-        self.closure_fields = {}
         if self._bounded_advection is not None:
             ba = self._bounded_advection
             if ba["tracers"] and ba["tracers"] != 0 and len(self.tracers) == 0:
                 raise ValueError("bounds-preserving tracer advection without tracers")
             bs = T.bz_bounds_preserving_advection(ba["lower"], ba["upper"], ba["moisture"], ba["microphysical_species"], ba["tracers"], 0)
             self._check(lib.bz_set_bounds_preserving_advection(self._ctx, C.byref(bs)), "bz_set_bounds_preserving_advection")
-        if self._diffusivity:      # no closure fields: nu and kappa are numbers or the user's own centre fields
-            Kf = {}
-            for name, value in (("ν", closure.ν), ("κ", closure.κ)):
-                if isinstance(value, Field):
-                    if value.grid is not grid or value.parent.device != self.device or value.parent.dtype != self.momentum["ρu"].parent.dtype:
-                        raise ValueError(f"closure {name}: the field must live on the model's grid, device and float type")
-                    Kf[name] = value
-            sd = T.bz_scalar_diffusivity(closure.formulation, 1 if closure.vertically_implicit else 0,
-                                         0.0 if "ν" in Kf else closure.ν, 0.0 if "κ" in Kf else closure.κ)
-            self._diffusivity_fields = Kf      # keeps the arrays the context reads alive
-            self._check(lib.bz_set_scalar_diffusivity(self._ctx, C.byref(sd), C.c_void_p(Kf["ν"].ptr() if "ν" in Kf else None),
-                                                      C.c_void_p(Kf["κ"].ptr() if "κ" in Kf else None)), "bz_set_scalar_diffusivity")
-        elif closure is not None:      # build_closure_fields: nu_e (atmosphere_model.jl:276)
-            if self._kessler or formulation != "LiquidIcePotentialTemperature":
-                raise NotImplementedError("SmagorinskyLilly is implemented for the potential-temperature formulation without Kessler")
-            self.closure_fields = {"νₑ": fld("ccc")}
-            cl = T.bz_smagorinsky_lilly(closure.C, closure.Cb, closure.Pr)
-            self._check(lib.bz_set_closure(self._ctx, C.byref(cl), C.c_void_p(self.closure_fields["νₑ"].ptr())), "bz_set_closure")
+        _context.attach_closure(self, fld, smagorinsky_refused="SmagorinskyLilly is implemented for the potential-temperature formulation "
+                                "without Kessler" if self._kessler or formulation != "LiquidIcePotentialTemperature" else None)
         # coriolis / forcing / boundary_conditions of the BOMEX configuration -> one column-forcing stack (forcings.py)
-        from .forcings import materialize_forcings, materialize_relaxation, split_relaxation
+        from .forcings import materialize_forcings, split_relaxation
         forcing, _relax, _field = split_relaxation(forcing)      # Relaxation sponges and 3-D forcings: their own attachments
-        Rx, self._relaxation_keepalive = materialize_relaxation(grid, _relax, formulation, T)
-        if Rx is not None:
-            self._check(lib.bz_set_relaxation(self._ctx, C.byref(Rx)), "bz_set_relaxation")
-        from .forcings import materialize_field_forcing
-        # Forcing(f(x, y, z)) on θ / e (or ρθ / ρe): a centre field the library reads at every tendency evaluation; refresh it with
-        # model.thermodynamic_forcing_field.set_interior(...) when the forcing depends on time
-        self.thermodynamic_forcing_field, _spec = materialize_field_forcing(grid, _field, formulation, self.device)
-        if self.thermodynamic_forcing_field is not None:
-            self._check(lib.bz_set_field_forcing(self._ctx, C.c_void_p(self.thermodynamic_forcing_field.ptr()), _spec), "bz_set_field_forcing")
+        _context.attach_relaxation(self, _relax, formulation)
+        _context.attach_field_forcing(self, _field, formulation)
         F, self._forcing_keepalive = materialize_forcings(grid, coriolis, forcing, boundary_conditions, T)
         if F is not None:
             if self._kessler or formulation != "LiquidIcePotentialTemperature":
@@ -564,10 +470,6 @@ class AtmosphereModel:
         # (kinematic_driver_time_stepping.jl:16)
         if not kin:
             set_(self, θ=ref.potential_temperature)
-
-    # -- plumbing ------------------------------------------------------------
-    def _check(self, rc, what):
-        _lib.check(self._lib, self._ctx, rc, what)
 
     def prognostic_fields(self):
         out = dict(self.momentum)
@@ -596,14 +498,6 @@ class AtmosphereModel:
         p.rho_theta, p.rho_q = d["ρθ"].ptr(), d["ρq"].ptr()
         return p
 
-    def __del__(self):
-        try:
-            if getattr(self, "_ctx", None):
-                self._lib.bz_destroy(self._ctx)
-                self._ctx = None
-        except Exception:
-            pass
-
     # method spellings of the module-level functions
     def _create_context(self, lib, bg, bc, br, order):
         return lib.bz_create(C.byref(self._ctx), C.byref(bg), C.byref(bc), C.byref(br), order)
@@ -619,9 +513,6 @@ class AtmosphereModel:
         (/root/reference/benchmarking/src/timestepping.jl:11-16) and run!'s stretch between two callback iterations.  With
         diagnose_last=False the velocities / θ / qᵛ / T / pressure anomaly stay stale until update_state_(model) (stepping may go on)."""
         return many_time_steps_(self, Δt, n, diagnose_last)
-
-    def synchronize(self):
-        self._check(self._lib.bz_sync(self._ctx), "bz_sync")
 
     # -- filtered surface state (FilteredSurfaceVelocities) --------------------
     _FILTERED = {"u": 0, "v": 1, "θᵥ": 2, "θv": 2, "theta_v": 2, "θ": 3, "theta": 3, "q": 4}
@@ -660,34 +551,11 @@ class AtmosphereModel:
         if diagnostics_stale(self):
             self._refresh_diagnostics()
 
-    # -- profiling -----------------------------------------------------------
     def graph_enable(self, on=True):
         """hipGraph replay of whole steps (csrc/bz_graph.hip); opt-in, bit-identical to launched steps."""
         if self._kinematic and on:
             raise NotImplementedError("AtmosphereModel(dynamics = PrescribedDynamics(...)): hipGraph replay is not implemented")
-        self._check(self._lib.bz_graph_enable(self._ctx, 1 if on else 0), "bz_graph_enable")
-
-    def graph_info(self):
-        """(enabled, steps recorded, steps replayed)"""
-        en, cap, rep = C.c_int32(), C.c_int64(), C.c_int64()
-        self._check(self._lib.bz_graph_info(self._ctx, C.byref(en), C.byref(cap), C.byref(rep)), "bz_graph_info")
-        return bool(en.value), cap.value, rep.value
-
-    def profile_enable(self, on=True):
-        self._check(self._lib.bz_profile_enable(self._ctx, 1 if on else 0), "bz_profile_enable")
-
-    def profile_reset(self):
-        self._check(self._lib.bz_profile_reset(self._ctx), "bz_profile_reset")
-
-    def profile(self):
-        """{kernel group: (total_ms, launches)} accumulated since the last reset."""
-        out = {}
-        for i in range(self._lib.bz_profile_count(self._ctx)):
-            name, ms, n = C.c_char_p(), self._T.real(), C.c_int64()
-            self._check(self._lib.bz_profile_get(self._ctx, i, C.byref(name), C.byref(ms), C.byref(n)),
-                        "bz_profile_get")
-            out[name.value.decode()] = (ms.value, n.value)
-        return out
+        super().graph_enable(on)
 
     def max_abs_divergence(self):
         if self._kinematic:

@@ -1,12 +1,15 @@
 #!/usr/bin/env python
-"""tools/step_trace.py [--out FILE] [--only NAME ...] — which kernels a whole anelastic step launches, and the bits it leaves, for every
-tier of bz_time_step_anelastic (csrc/bz_step.hip: bzi_anelastic_tier) and of the slab drivers (csrc/bz_comm.hip).
+"""tools/step_trace.py [--compressible] [--out FILE] [--only NAME ...] — which kernels a whole anelastic step launches, and the bits it
+leaves, for every tier of bz_time_step_anelastic (csrc/bz_step.hip: bzi_anelastic_tier) and of the slab drivers (csrc/bz_comm.hip).
 
 One process.  Each configuration below creates its model with profiling on and runs one time_step ("first"), then
 time_steps(dt, 2, diagnose_last=False) followed by one time_step ("then").  After each of the two phases the output holds the profile
 (record name -> launches, in first-appearance order) and a SHA-256 of the interior of every prognostic and diagnostic field.  Two builds
 whose outputs are equal launch the same records in the same order and compute the same bits; DESIGN §4 "which tier runs where" is
-checked against the record names (profiles/step_trace_*.json).  Small grids only: 32x16x16, 64x32x16 for the CBL stack."""
+checked against the record names (profiles/step_trace_*.json).  Small grids only: 32x16x16, 64x32x16 for the CBL stack.
+
+--compressible runs the other group instead (a process of its own): the components of the compressible split-explicit model at 32x16x16,
+three time_steps each, with the profile and the digests after the first and after the third (profiles/step_trace_compressible*.json)."""
 import argparse
 import hashlib
 import json
@@ -171,6 +174,97 @@ def slab_cases(bz):
     }
 
 
+# ---- the compressible group: name -> (environment, model factory, dt) ----
+CEXT = dict(x=(0.0, 8e3), y=(0.0, 4e3), z=(0.0, 4e3))
+
+
+def cbubble(x, y, z):
+    return np.maximum(0.0, 1.0 - np.sqrt((x - 4e3) ** 2 + (y - 2e3) ** 2 + (z - 1500.0) ** 2) / 1200.0)
+
+
+def ctheta(x, y, z):
+    return 300.0 + 0.004 * z + cbubble(x, y, z)
+
+
+def cvapour(x, y, z):
+    return 0.014 * np.exp(-z / 3000.0) + 0.004 * cbubble(x, y, z)
+
+
+def compressible(bz, topology=None, moist=False, slab=False, make_kw=None, sets=None, **kw):
+    gkw = dict(CEXT)
+    if topology is not None:
+        gkw["topology"] = topology
+    flat = topology is not None and topology[1] == bz.Flat
+    if flat:
+        gkw.pop("y")
+    grid = bz.RectilinearGrid((32, 16) if flat else (32, 16, 16), **gkw)
+    dyn = bz.CompressibleDynamics(bz.SplitExplicitTimeDiscretization(substeps=6), surface_pressure=1e5, reference_potential_temperature=300.0)
+    if make_kw is not None:
+        kw.update(make_kw(grid))
+    if slab:
+        m = bz.compressible.SlabCompressibleModel(grid, 0, 1, dyn, advection=bz.WENO(order=5), transport="local:" + uuid.uuid4().hex,
+                                                  device="cuda:0", **kw)
+    else:
+        m = bz.CompressibleAtmosphereModel(grid, dyn, advection=bz.WENO(order=5), **kw)
+    ref = m.dynamics.reference_state
+    ρ = ref.density[grid.Hz:grid.Hz + grid.Nz][:, None, None]
+    two = (lambda f: (lambda x, z: f(x, 2e3 + 0 * x, z))) if flat else (lambda f: f)
+    state = dict(ρ=ρ, θ=two(ctheta), u=3.0, v=0.0 if topology is not None else -2.0, w=0.0)
+    if moist:
+        state["qᵗ"] = two(cvapour)
+    state.update(sets or {})
+    m.set(**state)
+    return m
+
+
+def nu_field(bz):
+    def make(grid):
+        ν = bz.Field(grid, (bz.Center, bz.Center, bz.Center), "cuda:0")
+        ν.set_interior(lambda x, y, z: 5.0 + 3.0 * np.sin(2 * np.pi * x / 8e3) * np.cos(2 * np.pi * y / 4e3) + 1e-3 * z)
+        return dict(closure=bz.ScalarDiffusivity(ν=ν, κ=8.0))
+    return make
+
+
+def compressible_cases(bz):
+    tc = bz.ThermodynamicConstants(saturation_vapor_pressure=bz.TetensFormula())
+    PBB, PFB = (bz.Periodic, bz.Bounded, bz.Bounded), (bz.Periodic, bz.Flat, bz.Bounded)
+    forced = dict(coriolis=bz.FPlane(f=1e-4),
+                  forcing={"ρw": bz.Relaxation(rate=0.01, mask=bz.GaussianMask(3.5e3, 5e2), target=0.0),
+                           "θ": bz.Forcing(lambda x, y, z: 1e-3 * cbubble(x, y, z))})
+    return {
+        "compressible/dry": ({}, lambda: compressible(bz), 2.0),
+        "compressible/saturation_adjustment": ({}, lambda: compressible(bz, moist=True, microphysics=sat(bz)), 2.0),
+        "compressible/kessler": ({}, lambda: compressible(bz, moist=True, thermodynamic_constants=tc, microphysics=bz.DCMIP2016KesslerMicrophysics(),
+                                                          sets=dict(qcl=lambda x, y, z: 0.003 * cbubble(x, y, z),
+                                                                    qr=lambda x, y, z: 0.001 * cbubble(x, y, z))), 2.0),
+        "compressible/smagorinsky_lilly": ({}, lambda: compressible(bz, closure=bz.SmagorinskyLilly()), 2.0),
+        "compressible/scalar_diffusivity_nu_field": ({}, lambda: compressible(bz, make_kw=nu_field(bz)), 2.0),
+        "compressible/fplane_sponge_field_forcing": ({}, lambda: compressible(bz, **forced), 2.0),
+        "compressible/walls_in_y": ({}, lambda: compressible(bz, topology=PBB), 2.0),
+        "compressible/flat_y": ({}, lambda: compressible(bz, topology=PFB), 2.0),
+        "compressible/substep_float32": ({}, lambda: compressible(bz, substep_floattype=np.float32), 2.0),
+        "compressible/slab_local_world1": ({}, lambda: compressible(bz, slab=True), 2.0),
+    }
+
+
+def compressible_fields_of(m):
+    f = dict(m.prognostic_fields())
+    f.update({"u": m.velocities["u"], "v": m.velocities["v"], "w": m.velocities["w"], "θ": m.potential_temperature, "q": m.specific_moisture,
+              "T": m.temperature, "ρ": m.dynamics.total_density, "p": m.dynamics.pressure})
+    f.update({k: v for k, v in m.microphysical_fields.items() if hasattr(v, "interior_cpu") and k not in f})
+    f.update(m.closure_fields)
+    return f
+
+
+def trace_compressible(m, dt):
+    m.profile_enable(True)
+    m.time_step(dt)
+    first = snapshot(m, compressible_fields_of)
+    m.time_step(dt)
+    m.time_step(dt)
+    return {"first": first, "then": snapshot(m, compressible_fields_of)}
+
+
 def fields_of(m):
     f = dict(m.prognostic_fields())
     f.update({"u": m.velocities["u"], "v": m.velocities["v"], "w": m.velocities["w"], "θ": m.potential_temperature, "q": m.specific_moisture,
@@ -178,9 +272,9 @@ def fields_of(m):
     return f
 
 
-def snapshot(m):
+def snapshot(m, fields=None):
     m.synchronize()
-    digests = {k: hashlib.sha256(np.ascontiguousarray(f.interior_cpu()).tobytes()).hexdigest() for k, f in fields_of(m).items()}
+    digests = {k: hashlib.sha256(np.ascontiguousarray(f.interior_cpu()).tobytes()).hexdigest() for k, f in (fields or fields_of)(m).items()}
     return {"profile": [[name, n] for name, (_, n) in m.profile().items()], "sha256": digests}
 
 
@@ -241,11 +335,15 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--out", default=None, help="write the JSON here (default: standard output)")
     ap.add_argument("--only", nargs="*", default=None, help="configuration names (default: all)")
+    ap.add_argument("--compressible", action="store_true", help="the compressible group instead of the anelastic and slab configurations")
     a = ap.parse_args()
     import breeze_jl_amd as bz
     result = {}
-    todo = [(name, env, lambda make=make, dt=dt: trace(make(), dt)) for name, (env, make, dt) in single_device_cases(bz).items()]
-    todo += [(name, env, lambda mkw=mkw, skw=skw: run_slabs(bz, mkw, skw, 2.0)) for name, (env, mkw, skw) in slab_cases(bz).items()]
+    if a.compressible:
+        todo = [(name, env, lambda make=make, dt=dt: trace_compressible(make(), dt)) for name, (env, make, dt) in compressible_cases(bz).items()]
+    else:
+        todo = [(name, env, lambda make=make, dt=dt: trace(make(), dt)) for name, (env, make, dt) in single_device_cases(bz).items()]
+        todo += [(name, env, lambda mkw=mkw, skw=skw: run_slabs(bz, mkw, skw, 2.0)) for name, (env, mkw, skw) in slab_cases(bz).items()]
     try:
         for name, env, run in todo:
             if a.only and name not in a.only:
