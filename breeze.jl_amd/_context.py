@@ -163,9 +163,14 @@ def check_closure(closure, what="closure"):
     return isinstance(closure, ScalarDiffusivity)
 
 
-def check_microphysics(microphysics, message):
-    """Nothing, warm-phase saturation adjustment or Kessler.  -> whether it is Kessler."""
-    from .microphysics import DCMIP2016KesslerMicrophysics, SaturationAdjustment
+def check_microphysics(microphysics, message, instantaneous_precipitation_refused="InstantaneousPrecipitation: not implemented on this model"):
+    """Nothing, warm-phase saturation adjustment or Kessler; InstantaneousPrecipitation where the caller passes
+    instantaneous_precipitation_refused = None (else that message is raised, at the place of this check).  -> whether it is Kessler."""
+    from .microphysics import DCMIP2016KesslerMicrophysics, InstantaneousPrecipitation, SaturationAdjustment
+    if isinstance(microphysics, InstantaneousPrecipitation):
+        if instantaneous_precipitation_refused is not None:
+            raise NotImplementedError(instantaneous_precipitation_refused)
+        return False
     if microphysics is not None and not isinstance(microphysics, (SaturationAdjustment, DCMIP2016KesslerMicrophysics)):
         raise NotImplementedError(message)
     return isinstance(microphysics, DCMIP2016KesslerMicrophysics)
@@ -213,6 +218,17 @@ def attach_saturation_adjustment(model, fld):
                                            c.triple_point_temperature, c.triple_point_pressure, solver.abstol, solver.maxiter, 0)
     model._check(model._lib.bz_set_saturation_adjustment(model._ctx, C.byref(sa), C.c_void_p(μ["qᵛ"].ptr()), C.c_void_p(μ["qˡ"].ptr())),
                  "bz_set_saturation_adjustment")
+
+
+def attach_instantaneous_precipitation(model, fld):
+    """materialize_microphysical_fields(::InstantaneousPrecipitation) (instantaneous_precipitation.jl:69-70): (qᵛ, precipitation_rate); qᵛ is
+    the specific-moisture slot (update_microphysical_fields! stores the vapour fraction the state carries, which is ρqᵛ / ρ)."""
+    c, solver = model.thermodynamic_constants, model.microphysics.saturation_adjustment.solver
+    μ = model.microphysical_fields = {"qᵛ": model.specific_moisture, "precipitation_rate": fld("ccc")}
+    sa = model._T.bz_saturation_adjustment(c.liquid_reference_latent_heat, c.liquid_heat_capacity, c.energy_reference_temperature,
+                                           c.triple_point_temperature, c.triple_point_pressure, solver.abstol, solver.maxiter, 0)
+    model._check(model._lib.bz_set_instantaneous_precipitation(model._ctx, C.byref(sa), C.c_void_p(μ["precipitation_rate"].ptr())),
+                 "bz_set_instantaneous_precipitation")
 
 
 def attach_closure(model, fld, smagorinsky_refused=None):

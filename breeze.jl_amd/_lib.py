@@ -288,6 +288,9 @@ SYMBOLS = {
                                               C.c_double]),
     "bz_kessler_model_update": (C.c_int, [_ctx, _sp, _pp, C.c_double]),
     "bz_compressible_kessler_update": (C.c_int, [_ctx, _csp, _cpp, _asp, C.c_double]),
+    "bz_set_instantaneous_precipitation": (C.c_int, [_ctx, C.POINTER(bz_saturation_adjustment), C.c_void_p]),
+    "bz_instantaneous_precipitation_update": (C.c_int, [_ctx, _csp, _cpp, _asp, C.c_double]),
+    "bz_column_integral": (C.c_int, [_ctx, C.c_void_p, C.c_void_p]),
     "bz_pack_transpose": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "bz_pack_rows": (C.c_int, [_ctx, C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32]),
     "bz_slab_transform": (C.c_int, [_ctx, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32]),

@@ -358,7 +358,9 @@ class CompressibleAtmosphereModel(_context.ContextOwner):
     — timestepper :AcousticRungeKutta3; coriolis = FPlane(f) and density-keyed Relaxation sponges on ρu, ρv, ρw, ρθ
     (examples/tropical_cyclone_with_rainband.jl:434-514) are the forcing terms built; closure = SmagorinskyLilly(), ScalarDiffusivity(ν, κ)
     or VerticalScalarDiffusivity(ν, κ) with the explicit time discretisation (benchmarking/run_benchmarks.jl:111-119;
-    validation/DCMIP2016_TC/dcmip2016_tc.jl:277-292) on single-GPU models that are periodic in x and y."""
+    validation/DCMIP2016_TC/dcmip2016_tc.jl:277-292) on single-GPU models that are periodic in x and y; microphysics = SaturationAdjustment,
+    DCMIP2016KesslerMicrophysics or — on those single-GPU periodic models — InstantaneousPrecipitation (src/Microphysics/instantaneous_precipitation.jl):
+    microphysical_fields = {"qᵛ": the specific-moisture field, "precipitation_rate": a centre Field}, the once-per-step rain-out closes time_step."""
 
     def __init__(self, grid, dynamics, advection=None, thermodynamic_constants=None, temperature_solver=None,
                  closure=None, coriolis=None, microphysics=None, forcing=None, device="cuda:0", substep_floattype=None,
@@ -415,10 +417,18 @@ class CompressibleAtmosphereModel(_context.ContextOwner):
         if (coriolis is not None or self._relaxation or self._field_forcing) and type(self) is not CompressibleAtmosphereModel:
             raise NotImplementedError("Coriolis and sponges of the compressible model: single-GPU contexts")
         self.coriolis, self.forcing = coriolis, forcing
+        # InstantaneousPrecipitation: the single-device model that is periodic in x and y (its own messages; the list below is for unknown types)
+        ip_refused = ("InstantaneousPrecipitation: not implemented on a compressible model between walls (Bounded x / Bounded y)" if self.lateral_walls
+                      else "InstantaneousPrecipitation: not implemented on y-slab (distributed) compressible models"
+                      if type(self) is not CompressibleAtmosphereModel
+                      else "InstantaneousPrecipitation: not implemented on a compressible model with a Flat y" if Flat in grid.topology else None)
         self._kessler = _context.check_microphysics(microphysics, "compressible microphysics: DCMIP2016KesslerMicrophysics() and "
-                                                                  "SaturationAdjustment(equilibrium = WarmPhaseEquilibrium()) are implemented")
+                                                                  "SaturationAdjustment(equilibrium = WarmPhaseEquilibrium()) are implemented",
+                                                    instantaneous_precipitation_refused=ip_refused)
         self.microphysics = microphysics
-        self._sa = microphysics is not None and not self._kessler
+        from .microphysics import InstantaneousPrecipitation
+        self._ip = isinstance(microphysics, InstantaneousPrecipitation)
+        self._sa = microphysics is not None and not self._kessler and not self._ip
         if self._kessler:
             _context.check_kessler_constants(thermodynamic_constants)
         if advection is None:
@@ -484,6 +494,8 @@ class CompressibleAtmosphereModel(_context.ContextOwner):
             _context.attach_saturation_adjustment(self, fld)
         if self._kessler:
             _context.attach_kessler(self, dynamics.standard_pressure)
+        if self._ip:
+            _context.attach_instantaneous_precipitation(self, fld)
         if coriolis is not None:      # the f-plane term of the slow momentum tendencies (bz_set_forcings with coriolis_f alone)
             Fc = T.bz_column_forcings()
             Fc.coriolis_f = coriolis.f
@@ -763,6 +775,9 @@ def time_step_(model, Δt, whole_step=True):
         if getattr(model, "_kessler", False):
             model._check(model._lib.bz_compressible_kessler_update(model._ctx, C.byref(model._state), C.byref(model._G),
                                                                    C.byref(model._sub), Δt), "bz_compressible_kessler_update")
+        if getattr(model, "_ip", False):       # microphysics_model_update!(::InstantaneousPrecipitation, model) with Δt = this step's
+            model._check(model._lib.bz_instantaneous_precipitation_update(model._ctx, C.byref(model._state), C.byref(model._G),
+                                                                          C.byref(model._sub), Δt), "bz_instantaneous_precipitation_update")
     model.clock.time += Δt
     model.clock.last_Δt = Δt
     model.clock.iteration += 1

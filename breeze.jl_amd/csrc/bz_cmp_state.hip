@@ -311,6 +311,17 @@ int bzi_compressible_update_state(bz_ctx *ctx, const bz_compressible_state *s, c
         }, with_linearization);
         BZ_LAUNCH_CHECK();
     }
+    // Nx < 2 Hx or Ny < 2 Hy (small_grid_update_ok): k_cmp_diagnose has stored one periodic image per direction where a cell has two; what it
+    // computed in the interior is complete, the halos of everything it produced are filled again by the generic kernels
+    if (!ctx->fused_ok && small_grid(g) && !g.bounded_y && !ctx->slab_mode) {
+        double *fa[7] = {s->rho_d, s->rho, s->rho_u, s->rho_v, s->rho_w, s->rho_theta, s->rho_q};
+        const int ka[7] = {0, 0, 0, 0, 1, 0, 0};
+        double *fb[7] = {s->u, s->v, s->w, s->theta, s->q, s->T, s->p};
+        const int kb[7] = {0, 0, 3, 0, 0, 0, 0};
+        int rc = bzi_fill_halos_multi(ctx, fa, ka, 7);
+        if (!rc) rc = bzi_fill_halos_multi(ctx, fb, kb, 7);
+        if (rc) return rc;
+    }
     // walls in y: the linearisation of the next stage by its own kernel, which also forms the zero-gradient halo rows the substeps read
     if (g.bounded_y && with_linearization) {
         const int rc = bz_refresh_linearization(ctx, s, sub);
@@ -346,7 +357,7 @@ extern "C" int bz_compressible_update_state(bz_ctx *ctx, const bz_compressible_s
     BZ_REJECT_Y_WALL_OPTIONS("bz_compressible_update_state");
     if (!valid_state(s)) return BZ_ERR_INVALID;
     if (compute_tendencies && (!valid_prog(G) || !valid_sub(sub))) return BZ_ERR_INVALID;
-    if (!ctx->fused_ok) { ctx->last_error = "compressible path needs Nx >= 2Hx and Ny >= 2Hy"; return BZ_ERR_UNSUPPORTED; }
+    if (!ctx->fused_ok && !small_grid_update_ok(ctx)) { ctx->last_error = "compressible path needs Nx >= 2Hx and Ny >= 2Hy"; return BZ_ERR_UNSUPPORTED; }
     if (ctx->d_qstate) BZ_HIP(hipMemsetAsync(ctx->d_qstate, 0, sizeof(int), ctx->stream));      // moisture scan: unknown again (set! ends here)
     bzi_moisture_unknown(ctx);
     return bzi_compressible_update_state(ctx, s, G, sub, compute_tendencies != 0, false);

@@ -224,6 +224,7 @@ static int compressible_step_body(bz_ctx *ctx, const bz_compressible_state *s, c
     }
     s = s_step;
     if (g.microphysics == 2) return bz_compressible_kessler_update(ctx, s, G, sub, dt);     // microphysics_model_update! (:316)
+    if (ctx->has_instant_precip) return bz_instantaneous_precipitation_update(ctx, s, G, sub, dt);      // the same slot (bz_instant_precip.hip)
     return BZ_OK;
 }
 

@@ -281,6 +281,17 @@ static DiagFields diag_fields(bz_ctx *ctx, const bz_compressible_state *s, const
 
 static bool ac_walls(const bz_ctx *ctx) { return ctx->dg.bounded_x || ctx->dg.bounded_y; }
 
+// Grids with Hx <= Nx < 2 Hx or Hy <= Ny < 2 Hy (the reference's 8 x 8 x 8 test grids under a halo of 5, test/instantaneous_precipitation.jl:133):
+// a cell can have two periodic images in a direction and the fused image stores of the step's kernels write one, so the acoustic loop and
+// whole steps stay refused there (check_loop_args).  update_state! (set!) and the once-per-step update of InstantaneousPrecipitation run on a
+// single-device periodic context without microphysics species and closures: k_cmp_diagnose reaches its neighbours through wrap offsets and
+// the generic halo kernels fill what it produced (bzi_compressible_update_state).
+static bool small_grid(const DevGrid &g) { return g.Nx < 2 * g.Hx || g.Ny < 2 * g.Hy; }
+static bool small_grid_update_ok(const bz_ctx *ctx)
+{
+    return small_grid(ctx->dg) && ctx->dg.microphysics == 0 && !ctx->has_closure && !ctx->has_diffusivity && !ctx->slab_mode && !ac_walls(ctx);
+}
+
 // Walls in y, a y-face field (rho v, v): the x image; the south wall face (row 0) stored as the zero it is; next to the north wall also the
 // wall face j = Ny, which lives in the first upper halo row ("Walls in y")
 #ifdef __HIPCC__
@@ -310,6 +321,9 @@ int bzi_acoustic_substep(bz_ctx *ctx, const bz_compressible_state *s, const bz_c
 int bzi_acoustic_stage_end(bz_ctx *ctx, const bz_compressible_state *s, const bz_compressible_prognostic *U0,
                            const bz_compressible_prognostic *G, const bz_acoustic_substepper *sub, double dt, double beta, bool moist,
                            bool velocities);
+// bz_instant_precip.hip: the once-per-step rain-out kernel of InstantaneousPrecipitation on the state's own arrays (bz_ctx::has_instant_precip);
+// bz_instantaneous_precipitation_update (public) is this followed by update_state! with tendencies
+int bzi_instantaneous_precipitation(bz_ctx *ctx, const bz_compressible_state *s, double dt);
 bool bzi_acoustic_stage_end_fusable(const bz_ctx *ctx);
 int bzi_acoustic_stage_end_fused(bz_ctx *ctx, const bz_compressible_state *s, const bz_compressible_prognostic *U0,
                                  const bz_compressible_prognostic *G, const bz_acoustic_substepper *sub, double dt, double beta,

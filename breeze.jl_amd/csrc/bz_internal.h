@@ -476,6 +476,10 @@ struct bz_ctx {
     bz_kessler_microphysics kessler_params;
     bz_kessler_model_fields kessler;
     double kessler_pst = 1e5;
+    // InstantaneousPrecipitation attached to a compressible context (bz_set_instantaneous_precipitation, bz_instant_precip.hip): dg.microphysics
+    // stays 0 (a stage is the vapour-only stage), dg.sa_* hold the wrapped SaturationAdjustment for bz_ds_adjust
+    bool has_instant_precip = false;
+    double *ip_precipitation_rate = nullptr;      // mu.precipitation_rate (caller-owned centre field)
     // forcing / Coriolis / bottom-flux stack (bz_set_forcings, bz_forcing.hip)
     bool has_relaxation = false;      // bz_set_relaxation: [rate target](u v w theta q), Nz + 1 entries each
     double *d_relax = nullptr;

@@ -16,7 +16,7 @@ microphysics_diagnostics.jl) — behind bz_compute_diagnostics / bz_horizontal_a
     θ̄ = azimuthal_mean(LiquidIcePotentialTemperature(model), radius=150e3, Nr=30)      # same geometry: the ring plan is reused
 
 Moisture fractions are picked from the model as grid_moisture_fractions does: no microphysics qᵛ = qᵗ and no liquid;
-SaturationAdjustment the stored qᵛ, qˡ; Kessler qᵛ, qᶜˡ + qʳ.  Anelastic models read the reference-state columns; a compressible model
+SaturationAdjustment the stored qᵛ, qˡ; Kessler qᵛ, qᶜˡ + qʳ; InstantaneousPrecipitation qᵛ = ρqᵛ / ρ and no liquid.  Anelastic models read the reference-state columns; a compressible model
 hands its own p and ρ fields to the potential temperatures and its dynamics.reference_state (required) to the other kinds.
 """
 import ctypes as C
@@ -159,7 +159,7 @@ def _inputs(model, model_pressure):
     I.moisture = model.specific_moisture.ptr()
     if getattr(model, "_kessler", False):
         I.vapor, I.liquid, I.liquid_2 = μ["qᵛ"].ptr(), μ["qᶜˡ"].ptr(), μ["qʳ"].ptr()
-    elif model.microphysics is not None:
+    elif model.microphysics is not None and not getattr(model, "_ip", False):      # (InstantaneousPrecipitation keeps no condensate: vapour only)
         I.vapor, I.liquid = μ["qᵛ"].ptr(), μ["qˡ"].ptr()
     else:
         I.vapor = model.specific_moisture.ptr()
@@ -229,6 +229,59 @@ def horizontal_average(model, field):
     model._check(model._lib.bz_horizontal_average(model._ctx, C.c_void_p(field.ptr()), 1 if field.zface else 0,
                                                   prof.ctypes.data_as(C.POINTER(model._T.real))), "bz_horizontal_average")
     return prof
+
+
+# ---- precipitation of InstantaneousPrecipitation (csrc/bz_instant_precip.hip: bz_column_integral) ----------------------------------------
+def _require_instantaneous_precipitation(model, what):
+    if not getattr(model, "_ip", False):
+        raise NotImplementedError(f"{what}: implemented for microphysics = InstantaneousPrecipitation(...) "
+                                  f"(the model carries {type(getattr(model, 'microphysics', None)).__name__})")
+
+
+class ColumnIntegral:
+    """Field(Integral(field, dims = 3)) of a centre Field of the model: `.compute()` returns the (Ny, Nx) interior view of a device array of
+    (Ny + 2 Hy, Nx + 2 Hx) values, Σₖ f[k] Δzᶜ[k] summed upward from k = 0 (deterministic).  The array is kept and rewritten by the next
+    `.compute()`."""
+
+    def __init__(self, model, field):
+        if not isinstance(field, Field) or field.zface or field.grid is not model.grid or field.dtype != model.temperature.dtype:
+            raise ValueError("ColumnIntegral: a centre Field of the model's grid and float type")
+        self.model, self.field, self.parent = model, field, None
+
+    def compute(self):
+        import torch
+        m, g = self.model, self.model.grid
+        if self.parent is None:
+            self.parent = torch.zeros((g.Ny + 2 * g.Hy, g.Nx + 2 * g.Hx), dtype=self.field.parent.dtype, device=m.device)
+        m._check(m._lib.bz_column_integral(m._ctx, C.c_void_p(self.field.ptr()), C.c_void_p(self.parent.data_ptr())), "bz_column_integral")
+        return self.parent[g.Hy:g.Hy + g.Ny, g.Hx:g.Hx + g.Nx]
+
+
+class _StoredField:
+    """A field the model already holds, behind the `.compute()` of the other diagnostics."""
+
+    def __init__(self, field):
+        self.field = field
+
+    def compute(self):
+        return self.field
+
+
+def precipitation_rate(model, phase="liquid"):
+    """precipitation_rate(model, :liquid | :ice) (instantaneous_precipitation.jl:88-89): `.compute()` gives microphysical_fields.
+    precipitation_rate (kg m⁻³ s⁻¹, the centre Field the once-per-step update writes) for :liquid; None is returned for :ice."""
+    _require_instantaneous_precipitation(model, "precipitation_rate")
+    phase = str(phase).lstrip(":")
+    if phase not in ("liquid", "ice"):
+        raise ValueError(f"`phase` must be :liquid or :ice, received {phase!r}")
+    return _StoredField(model.microphysical_fields["precipitation_rate"]) if phase == "liquid" else None
+
+
+def surface_precipitation_flux(model):
+    """surface_precipitation_flux(model) (instantaneous_precipitation.jl:99-102): the condensate leaves at once, so the surface flux is the
+    column integral of the precipitation rate, kg m⁻² s⁻¹: a ColumnIntegral, `.compute()` gives the (Ny, Nx) device array."""
+    _require_instantaneous_precipitation(model, "surface_precipitation_flux")
+    return ColumnIntegral(model, model.microphysical_fields["precipitation_rate"])
 
 
 # ---- Average of products, powers and ∂z (csrc/bz_moments.hip: bz_horizontal_moments) ----------------------------------------------------

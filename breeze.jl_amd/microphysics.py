@@ -28,6 +28,16 @@ class SaturationAdjustment:
         self.solver = solver or SecantSolver()
 
 
+class InstantaneousPrecipitation:
+    """InstantaneousPrecipitation(; equilibrium = WarmPhaseEquilibrium(), solver = SecantSolver()) (src/Microphysics/
+    instantaneous_precipitation.jl:39-55): the Reed–Jablonowski large-scale condensation.  It wraps a SaturationAdjustment
+    (`saturation_adjustment`); once per step the vapour above saturation condenses at the cell's own density, its latent heat stays in the air
+    and the condensate leaves as precipitation.  The prognostic moisture is ρqᵛ; there are no condensate fields.  CompressibleDynamics only."""
+
+    def __init__(self, equilibrium=None, solver=None):
+        self.saturation_adjustment = SaturationAdjustment(solver=solver, equilibrium=WarmPhaseEquilibrium() if equilibrium is None else equilibrium)
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # DCMIP2016 Kessler warm-rain microphysics: the operator-split column update (src/Microphysics/dcmip2016_kessler.jl)
 # ---------------------------------------------------------------------------------------------------------------------
@@ -93,9 +103,16 @@ def microphysics_model_update_(microphysics, model, fields=None, Δt=None, teten
                                standard_pressure=None):
     """microphysics_model_update!(microphysics::DCMIP2016KesslerMicrophysics, model) (dcmip2016_kessler.jl:449-486) without
     the trailing update_state!: one launch of the column kernel.  `density` / `pressure`: 3-D Fields (compressible) or None
-    for the anelastic reference columns of the model's context."""
+    for the anelastic reference columns of the model's context.
+    microphysics_model_update!(microphysics::InstantaneousPrecipitation, model) (instantaneous_precipitation.jl:115-141): the rain-out kernel
+    WITH the trailing update_state!; Δt = model.clock.last_Δt unless given; nothing happens for a Δt that is NaN, infinite or ≤ 0."""
     import ctypes as C
     from . import _lib
+    if isinstance(microphysics, InstantaneousPrecipitation):
+        Δt = model.clock.last_Δt if Δt is None else Δt
+        model._check(model._lib.bz_instantaneous_precipitation_update(model._ctx, C.byref(model._state), C.byref(model._G), C.byref(model._sub),
+                                                                      float(Δt)), "bz_instantaneous_precipitation_update")
+        return
     if fields is None:          # the model owns the Kessler fields: microphysics_model_update!(microphysics, model)
         Δt = model.clock.last_Δt if Δt is None else Δt
         model._check(model._lib.bz_kessler_model_update(model._ctx, C.byref(model._state), C.byref(model._G), float(Δt)),

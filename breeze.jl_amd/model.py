@@ -347,7 +347,9 @@ class AtmosphereModel(_context.ContextOwner):
         self.closure = closure
         self.coriolis, self.forcing, self.boundary_conditions = coriolis, forcing, boundary_conditions
         self._kessler = _context.check_microphysics(microphysics, "microphysics: SaturationAdjustment(equilibrium = WarmPhaseEquilibrium()) and "
-                                                                  "DCMIP2016KesslerMicrophysics() are implemented")
+                                                                  "DCMIP2016KesslerMicrophysics() are implemented",
+                                                    instantaneous_precipitation_refused="InstantaneousPrecipitation: implemented on CompressibleDynamics "
+                                                    "(CompressibleAtmosphereModel); not on the anelastic AtmosphereModel, the kinematic driver or their y-slab models")
         if microphysics is not None and formulation != "LiquidIcePotentialTemperature":
             raise NotImplementedError("microphysics is implemented for the potential-temperature formulation")
         self.microphysics = microphysics

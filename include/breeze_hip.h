@@ -409,7 +409,11 @@ int bz_create_compressible(bz_ctx **ctx, const bz_grid *grid, const bz_constants
  * compressible_time_stepping.jl:83-103,191-242): total density, prognostic halos, velocities, theta, q, T (Newton), p,
  * and — when compute_tendencies != 0 — the moisture tendency G->rho_q built with the total density and the substepper's
  * time-averaged transport velocities (acoustic_runge_kutta_3.jl:352-358).  The momentum / rho_theta / rho_d tendencies
- * that the reference also computes here are overwritten by compute_slow_*_tendencies! before use and are not formed. */
+ * that the reference also computes here are overwritten by compute_slow_*_tendencies! before use and are not formed.
+ * The stepping entry points of a compressible context need Nx >= 2 Hx and Ny >= 2 Hy and return BZ_ERR_UNSUPPORTED otherwise.  This call
+ * (and bz_instantaneous_precipitation_update) also runs on narrower grids (Hx <= Nx, Hy <= Ny: the reference's 8 x 8 x 8 test grids under a
+ * halo of 5) of a single-device context that is periodic in x and y and carries neither microphysics species nor a closure: the halos
+ * are then filled by the generic halo kernels after the diagnosis. */
 int bz_compressible_update_state(bz_ctx *ctx, const bz_compressible_state *s, const bz_compressible_prognostic *G,
                                  const bz_acoustic_substepper *sub, int compute_tendencies);
 
@@ -587,6 +591,43 @@ int bz_kessler_model_update(bz_ctx *ctx, const bz_state *s, const bz_prognostic 
  * (bz_create_compressible_slab) the call runs the rank-local column kernel only and the driver's exchanging update_state! follows. */
 int bz_compressible_kessler_update(bz_ctx *ctx, const bz_compressible_state *s, const bz_compressible_prognostic *G,
                                    const bz_acoustic_substepper *sub, double dt);
+
+/* ---- microphysics = InstantaneousPrecipitation(equilibrium = WarmPhaseEquilibrium(), solver) on CompressibleDynamics ----
+ * The Reed-Jablonowski large-scale condensation of validation/DCMIP2016_TC/dcmip2016_tc.jl:292
+ * (src/Microphysics/instantaneous_precipitation.jl:39-185).  The scheme wraps a SaturationAdjustment.  The prognostic moisture is the vapour
+ * density rho q^v (bz_compressible_state::rho_q); there are no condensate fields; the microphysical fields are q^v — the specific moisture
+ * rho q^v / rho that update_state! diagnoses (bz_compressible_state::q) — and a centre field precipitation_rate in kg m^-3 s^-1.
+ * Inside a stage nothing condenses (maybe_adjust_thermodynamic_state returns the state, the moisture fractions are vapour only, :73-86): a
+ * stage is the stage of a context without microphysics, and the attachment does not change what any stage kernel computes.
+ * Once per step, after the update_state! that follows stage 3 (src/TimeSteppers/acoustic_runge_kutta_3.jl:307-316),
+ * microphysics_model_update! (:115-185) does in every interior cell, with dt = clock.last_dt:
+ *     rho = total density (as that update_state! left it), rho_d = dry density, q^t = rho q^v / rho, theta_0 = rho theta / rho_d
+ *     (T, q^v+, q^l) = adjust_thermodynamic_state(LiquidIceDensityState(theta_0, q^t, p_st, rho), SaturationAdjustment) — the density-based
+ *                      warm-phase adjustment of bz_set_saturation_adjustment on a compressible context
+ *                      (src/Microphysics/saturation_adjustment.jl:236-301); a subsaturated cell short-circuits with q^v+ = q^t
+ *     R_m = (1 - q^v+) R_d + q^v+ R_v,  c_pm = (1 - q^v+) c_pd + q^v+ c_pv
+ *     theta_f = T (p_st / (rho R_m T))^(R_m / c_pm)        with_temperature of the vapour-only state (src/Thermodynamics/dynamic_states.jl:251-264):
+ *                                                          the condensate leaves, its latent warming stays
+ *     c = rho max(0, q^t - q^v+)
+ *     rho q^v <- rho q^v+,   rho theta <- rho_d theta_f,   precipitation_rate <- c / dt where c > 0 (a cell that does not condense keeps its rate)
+ * and then update_state!(model) with tendencies: rho = rho_d + rho q^v (the total density drops by the rain), T, p, velocities, halos, closure
+ * fields and the moisture tendency of the next step's first stage.  The whole update, update_state! included, is skipped when dt is NaN,
+ * infinite or <= 0 (:121).  The Newton settings of the temperature inversions are the context's (bz_split_explicit::newton_abstol / _maxiter).
+ *
+ * bz_set_instantaneous_precipitation: params = the wrapped SaturationAdjustment (constants of the liquid phase and SecantSolver(abstol,
+ *   maxiter)), precipitation_rate = the centre field (parent with halos; written at interior cells only).  NULL params detaches.  Every call
+ *   invalidates recorded steps.  BZ_ERR_UNSUPPORTED with bz_last_error naming the function: contexts not created by bz_create_compressible
+ *   (the anelastic model), contexts with Kessler or saturation adjustment attached, y-slab contexts, contexts with a Bounded x or y or a Flat y.
+ * bz_instantaneous_precipitation_update: microphysics_model_update!(microphysics, model) for per-operator drivers;
+ *   bz_time_step_compressible calls it after its third stage (a recorded step contains it).
+ * bz_column_integral: Field(Integral(field, dims = 3)) of any centre field of the context's grid: out2d[j + Hy][i + Hx] = sum_k field[k] dz_c[k],
+ *   summed from k = 0 upward (deterministic); out2d is a device array of (Ny + 2 Hy) x (Nx + 2 Hx) reals, written at interior positions
+ *   (the layout of the Kessler scheme's surface precipitation_rate).  surface_precipitation_flux(model) (:99-102) is this of
+ *   precipitation_rate, in kg m^-2 s^-1.  Runs on the context's stream without synchronising.  y-slab contexts return BZ_ERR_UNSUPPORTED. */
+int bz_set_instantaneous_precipitation(bz_ctx *ctx, const bz_saturation_adjustment *params, double *precipitation_rate);
+int bz_instantaneous_precipitation_update(bz_ctx *ctx, const bz_compressible_state *s, const bz_compressible_prognostic *G,
+                                          const bz_acoustic_substepper *sub, double dt);
+int bz_column_integral(bz_ctx *ctx, const double *field, double *out2d);
 
 /* ---- forcing, f-plane Coriolis and bottom-flux stack of the BOMEX configuration (BASELINE configs[2]) ----
  * Every forcing of examples/bomex.jl:104-196 is a horizontally uniform specific profile multiplied by the reference density

@@ -525,6 +525,48 @@ function OceananigansTimeSteppers.update_state!(model::HIPAcousticModel, callbac
     return nothing
 end
 
+#####
+##### microphysics = InstantaneousPrecipitation(...) (src/Microphysics/instantaneous_precipitation.jl).  Like the rest of this file these
+##### three bindings have never been run (Julia is not available in the build image); the Python host (breeze.jl_amd/) drives the same
+##### entry points in tests/test_instantaneous_precipitation.py.
+#####
+struct BzSaturationAdjustment
+    liquid_latent_heat::Float64; liquid_heat_capacity::Float64; energy_reference_temperature::Float64
+    triple_point_temperature::Float64; triple_point_pressure::Float64
+    abstol::Float64
+    maxiter::Int32; reserved::Int32
+end
+
+"Attach the scheme to a compressible context: the wrapped SaturationAdjustment's solver and the liquid-phase constants; `precipitation_rate` = model.microphysical_fields.precipitation_rate."
+function attach_instantaneous_precipitation!(ctx, model)
+    c = model.thermodynamic_constants
+    solver = model.microphysics.saturation_adjustment.solver
+    P = BzSaturationAdjustment(c.liquid.reference_latent_heat, c.liquid.heat_capacity, c.energy_reference_temperature,
+                               c.triple_point_temperature, c.triple_point_pressure, solver.abstol, Int32(solver.maxiter), Int32(0))
+    check(ccall((:bz_set_instantaneous_precipitation, libbreeze_hip), Cint, (Ptr{Cvoid}, Ref{BzSaturationAdjustment}, Ptr{Cdouble}),
+                ctx, P, devptr(model.microphysical_fields.precipitation_rate)), "bz_set_instantaneous_precipitation", ctx)
+    return nothing
+end
+
+# microphysics_model_update!(::InstantaneousPrecipitation, model) (instantaneous_precipitation.jl:115-141); bz_time_step_compressible calls it itself
+function AtmosphereModels.microphysics_model_update!(::Breeze.Microphysics.InstantaneousPrecipitation, model::HIPAcousticModel)
+    ctx = ccontext(model)
+    ts = model.timestepper
+    rc = ccall((:bz_instantaneous_precipitation_update, libbreeze_hip), Cint,
+               (Ptr{Cvoid}, Ref{BzCompressibleState}, Ref{BzCompressiblePrognostic}, Ref{BzAcousticSubstepper}, Cdouble),
+               ctx, cstate(model), cprognostic(ts.Gⁿ), substepper(ts.substepper), model.clock.last_Δt)
+    check(rc, "bz_instantaneous_precipitation_update", ctx)
+    return nothing
+end
+
+"Field(Integral(field, dims = 3)) into `out`, a device array of (Nx + 2Hx) × (Ny + 2Hy) reals (interior positions are written)."
+function column_integral!(out, model::HIPAcousticModel, field)
+    ctx = ccontext(model)
+    check(ccall((:bz_column_integral, libbreeze_hip), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}), ctx, devptr(field), Ptr{Float64}(UInt(pointer(out)))),
+          "bz_column_integral", ctx)
+    return out
+end
+
 
 #####
 ##### Multi-GPU: one process per GPU, y-slabs, the communicator lives inside libbreeze_hip (bz_comm.hip)
