@@ -183,8 +183,10 @@ __global__ __launch_bounds__(64 * CTY) void k_scalar_tendency_rho3d_x(DevGrid g,
             AZ[l][ty][tx] = bz_sub_rounded_c(Fz_hi, Fz_lo);
             // (z0 = c[m] and r0 = rho[m]: the ring values of this level)
             const double fx = ((r0 + rxm) / 2.0) * ((g.Ax[kl] * u0) * bz_up5(xm3, xm2, xm1, z0, xp1, xp2, u0 > 0.0));
-            double nb = __shfl_down(fx, 1);
-            const double e = __shfl(edge, kl - k0);
+            // neighbour lane's flux by a DPP move, the out-of-wave one by v_readlane (bz_internal.h; kl - k0 is wave-uniform); whole rows only,
+            // so lane 63, which the shift leaves at 0, is always replaced
+            double nb = bz_lane_down(fx);
+            const double e = bz_lane_read(edge, kl - k0);
             if (tx == 63) nb = e;
             AX[l][ty][tx] = bz_sub_rounded_c(nb, fx);
             FY[buf][l][ty][tx] = ((r0 + rym) / 2.0) * ((g.Ay[kl] * v0) * bz_up5(ym3, ym2, ym1, z0, yp1, yp2, v0 > 0.0));
@@ -346,11 +348,13 @@ __global__ __launch_bounds__(64 * SLT, 2) void k_scalar_rho3d_lds(DevGrid g, dou
         R[buf ^ 1][ty + 1][tx + 1] = r_hi;
         if (hc) C[buf ^ 1][hcr][hcc] = p_hc;
         if (hr) R[buf ^ 1][hrr][hrc] = p_hr;
+        // neighbour lane's flux by a DPP move, the out-of-wave one by v_readlane (bz_internal.h; k - k0 is wave-uniform), ahead of the barrier;
+        // whole rows only, so lane 63, which the shift leaves at 0, is always replaced
+        double nb = bz_lane_down(fx);
+        const double e = bz_lane_read(edge, k - k0);
+        if (tx == 63) nb = e;
         __syncthreads();
         {
-            double nb = __shfl_down(fx, 1);
-            const double e = __shfl(edge, k - k0);
-            if (tx == 63) nb = e;
             const double dx = bz_sub_rounded_c(nb, fx);
             const double dy = bz_sub_rounded_c(FY[buf][ty + 1][tx], fy);
             Gc[n] = -(g.Vinv_c[k] * (dx + dy + dz));

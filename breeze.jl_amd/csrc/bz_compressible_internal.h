@@ -26,26 +26,12 @@ __device__ __forceinline__ WrapIdx wrap_of(const DevGrid &g, int i, int j)
     return w;
 }
 
-// a value one lane up / down the 64-lane wavefront (lane l receives lane l - 1 / l + 1) as two v_mov_b32_dpp wave_shr:1 / wave_shl:1 — 4 cycles of
-// the vector ALU each where __shfl_up / __shfl_down are ds_bpermute_b32 at 10 ns of the CU's LDS pipe (instruction costs;
-// tools/dpp_check.hip: the same values, also with the upper lanes of a ragged row gone)
-template <int CTRL, class T>
-__device__ __forceinline__ T ac_lane_shift(T v)
-{
-    if constexpr (sizeof(T) == 8) {
-        const long long b = __builtin_bit_cast(long long, v);
-        int lo = (int)b, hi = (int)(b >> 32);
-        lo = __builtin_amdgcn_update_dpp(0, lo, CTRL, 0xf, 0xf, false);
-        hi = __builtin_amdgcn_update_dpp(0, hi, CTRL, 0xf, 0xf, false);
-        return __builtin_bit_cast(T, ((long long)hi << 32) | (long long)(unsigned)lo);
-    } else {
-        return __builtin_bit_cast(T, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, false));
-    }
-}
+// a value one lane up / down the 64-lane wavefront (lane l receives lane l - 1 / l + 1): the DPP moves of bz_internal.h (bz_lane_up /
+// bz_lane_down), or — DPP = false, the measured alternative of the forward sweep — the shuffles through the LDS pipe
 template <bool DPP>
-__device__ __forceinline__ double ac_lane_up(double v) { return DPP ? ac_lane_shift<0x138>(v) : __shfl_up(v, 1); }
+__device__ __forceinline__ double ac_lane_up(double v) { return DPP ? bz_lane_up(v) : __shfl_up(v, 1); }
 template <bool DPP>
-__device__ __forceinline__ double ac_lane_down(double v) { return DPP ? ac_lane_shift<0x130>(v) : __shfl_down(v, 1); }
+__device__ __forceinline__ double ac_lane_down(double v) { return DPP ? bz_lane_down(v) : __shfl_down(v, 1); }
 
 // update_state!: what k_cmp_diagnose (bz_cmp_state.hip) and the tail of k_ac_stage_end (bz_acoustic_kernels.h) read and write
 struct DiagFields {

@@ -108,6 +108,47 @@ __device__ __forceinline__ double bz_cdiv(double a, double b, double rb)
     const double q0 = a * rb;
     return fma(fma(-q0, b, a), rb, q0);
 }
+// Lane exchanges of the tile kernels (one tile row per 64-lane wavefront) on the vector ALU instead of the LDS pipe: __shfl_up / __shfl_down /
+// __shfl are ds_bpermute_b32 at 10 ns of the CU's LDS pipe each (two per Float64 value), and as LDS instructions they may not move across a
+// __syncthreads(); v_mov_b32_dpp and v_readlane_b32 are 4 cycles of the vector ALU (instruction costs) and can be issued
+// where their operand is complete.  tools/dpp_check.hip: the same values as the shuffles, also with the upper lanes of a ragged row gone.
+// bz_lane_shift<CTRL>: one v_mov_b32_dpp per 32-bit half, CTRL 0x138 = wave_shr:1 (lane l receives lane l - 1), 0x130 = wave_shl:1 (lane l
+// receives lane l + 1).  A lane WITHOUT a source (lane 0 / lane 63) receives 0 (old = 0, bound_ctrl off) — not its own value, as the shuffles
+// give: every caller overwrites that lane or never stores it, and says so where it calls.  All 64 lanes must be active at the call: a DPP
+// move reads nothing from an inactive lane.
+template <int CTRL, class T>
+__device__ __forceinline__ T bz_lane_shift(T v)
+{
+    if constexpr (sizeof(T) == 8) {
+        const long long b = __builtin_bit_cast(long long, v);
+        int lo = (int)b, hi = (int)(b >> 32);
+        lo = __builtin_amdgcn_update_dpp(0, lo, CTRL, 0xf, 0xf, false);
+        hi = __builtin_amdgcn_update_dpp(0, hi, CTRL, 0xf, 0xf, false);
+        return __builtin_bit_cast(T, ((long long)hi << 32) | (long long)(unsigned)lo);
+    } else {
+        static_assert(sizeof(T) == 4, "bz_lane_shift: 32- or 64-bit values");
+        return __builtin_bit_cast(T, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, false));
+    }
+}
+template <class T>
+__device__ __forceinline__ T bz_lane_up(T v) { return bz_lane_shift<0x138>(v); }        // lane l receives lane l - 1; lane 0 receives 0
+template <class T>
+__device__ __forceinline__ T bz_lane_down(T v) { return bz_lane_shift<0x130>(v); }      // lane l receives lane l + 1; lane 63 receives 0
+// the value lane `lane` holds, for a WAVE-UNIFORM lane index (made a scalar here): one v_readlane_b32 per 32-bit half, the result a scalar
+// register pair — what __shfl(v, lane) returns in every lane when all 64 are active
+template <class T>
+__device__ __forceinline__ T bz_lane_read(T v, int lane)
+{
+    const int l = __builtin_amdgcn_readfirstlane(lane);
+    if constexpr (sizeof(T) == 8) {
+        const long long b = __builtin_bit_cast(long long, v);
+        const int lo = __builtin_amdgcn_readlane((int)b, l), hi = __builtin_amdgcn_readlane((int)(b >> 32), l);
+        return __builtin_bit_cast(T, ((long long)hi << 32) | (long long)(unsigned)lo);
+    } else {
+        static_assert(sizeof(T) == 4, "bz_lane_read: 32- or 64-bit values");
+        return __builtin_bit_cast(T, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), l));
+    }
+}
 __device__ __forceinline__ double bz_rk_apply(int mode, double dt, double alpha, double oma, const double *u0,
                                               double *u0_out, double G, double uold, long long n)
 {

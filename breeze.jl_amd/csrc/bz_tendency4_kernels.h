@@ -172,12 +172,14 @@ __global__ __launch_bounds__(64 * TY) void k_scalar_pair_lds(DevGrid g, const do
 #pragma unroll
         for (int q = 0; q < HPT; ++q)
             if (hok[q]) { T[buf ^ 1][0][hr[q]][hc[q]] = ha[q]; T[buf ^ 1][1][hr[q]][hc[q]] = hb[q]; }
+        // x flux of the next face from lane tx + 1 (DPP move; bz_internal.h) or, in lane le, lane `src` of the out-of-wave batch (v_readlane), ahead of
+        // the barrier.  Lane 63 receives 0: it is lane le (replaced) or beyond a ragged row (store = false).
+        double na = bz_lane_down(fxa), nb = bz_lane_down(fxb);
+        const double xa = bz_lane_read(ea, src), xb = bz_lane_read(eb, src);
+        if (tx == le) { na = xa; nb = xb; }
         __syncthreads();
         // ---- combine ----
         {
-            double na = __shfl_down(fxa, 1), nb = __shfl_down(fxb, 1);
-            const double xa = __shfl(ea, src), xb = __shfl(eb, src);
-            if (tx == le) { na = xa; nb = xb; }
             const double dya = FY[buf][0][ty + 1][tx] - fya;
             const double dyb = FY[buf][1][ty + 1][tx] - fyb;
             const double Vi = g.Vinv_c[k];
@@ -393,11 +395,13 @@ __global__ __launch_bounds__(64 * TY) void k_u_tend_lds(DevGrid g, Tend3Fields F
 #pragma unroll
         for (int q = 0; q < HPT; ++q)
             if (hok[q]) T[buf ^ 1][hr[q]][hcol[q]] = hnext[q];
+        // x flux of centre i - 1 from lane tx - 1 (DPP move; bz_internal.h) or, in lane le = 0, lane `src` of the out-of-wave batch (v_readlane), ahead
+        // of the barrier.  Lane 0 receives 0 from the shift and is the lane replaced.
+        double nb = bz_lane_up(fx);
+        const double e = bz_lane_read(edge, src);
+        if (tx == le) nb = e;
         __syncthreads();
         {
-            double nb = __shfl_up(fx, 1);
-            const double e = __shfl(edge, src);
-            if (tx == le) nb = e;
             const double dx = fx - nb;
             const double dy = FY[buf][ty + 1][tx] - fy;
             if (store)
@@ -524,11 +528,13 @@ __global__ __launch_bounds__(64 * TY) void k_w_tend_lds(DevGrid g, Tend3Fields F
         const double Axn = g.Ax[k + 2], Ayn = g.Ay[k + 2];
         const double qun = Axn * ru[n + 2 * sz], qvn = Ayn * rv[n + 2 * sz];
         const double qtn = top ? Ayn * rv[ntop0 + lev + 2 * sz] : 0.0;
+        // x flux of the next face from lane tx + 1 (DPP move; bz_internal.h) or, in lane le, lane `src` of the out-of-wave batch (v_readlane), ahead of
+        // the barrier.  Lane 63 receives 0: it is lane le (replaced) or beyond a ragged row (store = false).
+        double nb = bz_lane_down(fx);
+        const double e = bz_lane_read(edge, src);
+        if (tx == le) nb = e;
         __syncthreads();
         {
-            double nb = __shfl_down(fx, 1);
-            const double e = __shfl(edge, src);
-            if (tx == le) nb = e;
             const double dx = nb - fx;
             const double dy = FY[buf][ty + 1][tx] - fy;
             const double adv = -(g.Vinv_f[k] * (dx + dy + (fz_hi - fz_lo)));
@@ -665,11 +671,13 @@ __global__ __launch_bounds__(64 * TY) void k_v_tend_lds(DevGrid g, Tend3Fields F
 #pragma unroll
         for (int q = 0; q < HPT; ++q)
             if (hok[q]) frame_store(buf ^ 1, q, hnext[q]);
+        // x flux of the next face from lane tx + 1 (DPP move; bz_internal.h) or, in lane le, lane `src` of the out-of-wave batch (v_readlane), ahead of
+        // the barrier.  Lane 63 receives 0: it is lane le (replaced) or beyond a ragged row (store = false).
+        double nb = bz_lane_down(fx);
+        const double e = bz_lane_read(edge, src);
+        if (tx == le) nb = e;
         __syncthreads();
         {
-            double nb = __shfl_down(fx, 1);
-            const double e = __shfl(edge, src);
-            if (tx == le) nb = e;
             const double dx = nb - fx;
             const double dy = fy - FY[buf][ty][tx];
             if (store)

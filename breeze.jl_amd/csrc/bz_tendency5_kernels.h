@@ -469,6 +469,22 @@ __device__ __forceinline__ void k5_scalar_pair_body(const DevGrid &g, const Lean
         if (zz) fzb_hi = 0.0;
         else fzb_hi = (BZ_KO & 128) ? rf * (cfz * b[3]) : rf * (cfz * bz_upB(b[1], b[2], b[3], b[4], b[5], tb, lz, Bz));
         }
+        // x flux of the upper face = the low-face flux of lane tx + 1 (DPP move, vector ALU) or, in the row's last lane le, lane `src` of the
+        // out-of-wave batch (v_readlane: src is wave-uniform).  Formed here, where the fluxes are complete, not behind the level's barrier:
+        // neither operand depends on it.  Lane 63 receives 0 from the shift: it is lane le (replaced) or a lane beyond a ragged row (store =
+        // false).  Outside the wave-uniform shortcut branches above, so all 64 lanes are active; both fields after the second one's fluxes
+        // (the first field's exchange ahead of them cost the general body with y walls two registers of scratch).
+        double na = bz_lane_down(fxa);
+        const double xa = bz_lane_read(ea, src);
+        if (tx == le) na = xa;
+        const double dxa = na - fxa;
+        double dxb = 0.0;
+        if constexpr (Q) {
+            double nb = bz_lane_down(fxb);
+            const double xb = bz_lane_read(eb, src);
+            if (tx == le) nb = xb;
+            dxb = nb - fxb;
+        }
         // the cell's own prognostic values (read three levels ago as ring tops: an L2 / Infinity-Cache hit), requested before the staging
         // arithmetic so that the RK update after the barrier finds them
         double pa_n, pb_n;
@@ -500,19 +516,13 @@ __device__ __forceinline__ void k5_scalar_pair_body(const DevGrid &g, const Lean
         if (!(BZ_KO & 64)) __syncthreads();
         // ---- combine, SSP-RK3 update, temperature of the updated cell for the next stage's buoyancy ----
         {
-            double na = __shfl_down(fxa, 1);
-            const double xa = __shfl(ea, src);
-            if (tx == le) na = xa;
             const double dya = FY[buf][0][ty + 1][tx] - fya;
             const double Vi = Vi_k;
-            const double ga = -(Vi * ((na - fxa) + dya + (fza_hi - fza)));
+            const double ga = -(Vi * (dxa + dya + (fza_hi - fza)));
             double gb = 0.0;
             if constexpr (Q) {
-                double nb = __shfl_down(fxb, 1);
-                const double xb = __shfl(eb, src);
-                if (tx == le) nb = xb;
                 const double dyb = FY[buf][1][ty + 1][tx] - fyb;
-                gb = -(Vi * ((nb - fxb) + dyb + (fzb_hi - fzb)));
+                gb = -(Vi * (dxb + dyb + (fzb_hi - fzb)));
             }
             if (store) {
                 const double rth = bz_rk_apply_pre(E.mode, E.dt, E.alpha, E.oma, u0a, E.u0_out, ga, pa_n, n);
@@ -687,6 +697,16 @@ __global__ __launch_bounds__(64 * TY, BZ_LEAN_WAVES) void k6_u(DevGrid g, Lean5 
         const double *rur = RU[buf][ty] + tc, *ur = Uk[ty + 3] + tc;
         const double ax = bz_symm4(Ax * rur[-1], Ax * q0, Ax * rur[1], Ax * rur[2]);
         const double fx = ax * bz_up5(ur[-2], ur[-1], c0, ur[1], ur[2], ur[3], ax > 0.0);
+        // flux at centre i - 1: lane tx - 1 (DPP move) or, in lane le = 0, lane `src` of the out-of-wave batch (v_readlane, src wave-uniform); formed
+        // here, ahead of the level's barrier, which neither operand depends on.  Lane 0 receives 0 from the shift and is the lane replaced.
+        // (The forcing instantiations keep their shuffles behind the barrier: with the exchange moved or replaced the compiler contracts
+        // one product of their epilogue differently — one v_fma_f64 less, one v_add_f64 more — and their results move in the last bit.)
+        double nb = 0.0;
+        if constexpr (!MF) {
+            nb = bz_lane_up(fx);
+            const double e = bz_lane_read(edge, src);
+            if (tx == le) nb = e;
+        }
         // ---- y: flux at the own low y-face ----
         const double *rvr = RV[buf][ty] + tc;
         const double ay = bz_symm4(Ay * rvr[-2], Ay * rvr[-1], Ay * rvr[0], Ay * rvr[1]);
@@ -715,9 +735,11 @@ __global__ __launch_bounds__(64 * TY, BZ_LEAN_WAVES) void k6_u(DevGrid g, Lean5 
         if (h2ok) { if (h2sel) RW[buf ^ 1][h2r][h2c] = p_h2; else RV[buf ^ 1][h2r][h2c] = p_h2; }
         if (!(BZ_KO & 16384) && (!(BZ_KO & 8192) || ((k - kbeg) & 1))) bz6_barrier();
         {
-            double nb = __shfl_up(fx, 1);
-            const double e = __shfl(edge, src);
-            if (tx == le) nb = e;
+            if constexpr (MF) {
+                nb = __shfl_up(fx, 1);
+                const double e = __shfl(edge, src);
+                if (tx == le) nb = e;
+            }
             const double dx = fx - nb;
             const double dy = (BZ_KO & 16384) ? 0.5 * fy : FY[buf][ty + 1][tx] - fy;
             double Gu = -(g.Vinv_c[k] * (dx + dy + (fz_hi - fz_lo)));
@@ -874,6 +896,16 @@ __global__ __launch_bounds__(64 * TY, ((MF && WY) ? 4 : BZ_LEAN_WAVES)) void k6_
         // ---- x: flux at (x-face i, y-face j): rho_u rows j-2..j+1, v x-stencil derived from the rho_v row ----
         const double ut = bz_symm4y<WY>(MU[ty][tx], MU[ty + 1][tx], MU[ty + 2][tx], MU[ty + 3][tx], Bf);
         const double fx = ut * bz_up5(vrow[-3], vrow[-2], vrow[-1], c0, vrow[1], vrow[2], ut > 0.0);
+        // flux at x-face i + 1: lane tx + 1 (DPP move) or, in the row's last lane le, lane `src` of the out-of-wave batch (v_readlane, src
+        // wave-uniform); formed here, ahead of the level's barrier, which neither operand depends on.  Lane 63 receives 0 from the shift: it is
+        // lane le (replaced) or a lane beyond a ragged row (store = false; the wall-face stores below do not use it).
+        // (The forcing instantiations keep their shuffles behind the barrier, as in k6_u: the same bits as before.)
+        double nb = 0.0;
+        if constexpr (!MF) {
+            nb = bz_lane_down(fx);
+            const double e = bz_lane_read(edge, src);
+            if (tx == le) nb = e;
+        }
         // ---- y: flux at centre j: rho_v rows j-1..j+2, v rows j-2..j+3 (walls: order 2 from faces j, j+1 next to a wall) ----
         const double vt = (!WY || Bc == 3) ? bz_symm4(MV[ty + 1][tx], MV[ty + 2][tx], MV[ty + 3][tx], MV[ty + 4][tx]) : bz_symm2(MV[ty + 2][tx], MV[ty + 3][tx]);
         const double fy = vt * bz_up5y<WY>(V[ty + 1][tc], V[ty + 2][tc], c0, V[ty + 4][tc], V[ty + 5][tc], V[ty + 6][tc], vt > 0.0, Bc);
@@ -905,9 +937,11 @@ __global__ __launch_bounds__(64 * TY, ((MF && WY) ? 4 : BZ_LEAN_WAVES)) void k6_
             if (hok[q]) frame_store(buf ^ 1, q, hnext[q], k + 1);
         bz6_barrier();
         {
-            double nb = __shfl_down(fx, 1);
-            const double e = __shfl(edge, src);
-            if (tx == le) nb = e;
+            if constexpr (MF) {
+                nb = __shfl_down(fx, 1);
+                const double e = __shfl(edge, src);
+                if (tx == le) nb = e;
+            }
             const double dx = nb - fx;
             const double dy = fy - FY[buf][ty][tx];
             double Gv = -(g.Vinv_c[k] * (dx + dy + (fz_hi - fz_lo)));
@@ -945,8 +979,17 @@ __global__ __launch_bounds__(64 * TY, ((MF && WY) ? 4 : BZ_LEAN_WAVES)) void k6_
 // ---------------------------------------------------------------------------------------------------------------------
 // buoyancy of a cell from its prognostic densities: T = Pi^(Rm/cpm) theta as bz_temperature5r (the bits of the stored diagnostic),
 // q = rho q / rho_r, then the expression of buoyancy3
+// DRY (the DRYQ body of k6_w: rho q identically zero): q = 0 folded at compile time — T = pi theta, R_m = R_d.  The same bits as the
+// general expression gives for rq = +0: bz_cdiv(+0, rho, rrho) = +0, so every wavefront takes the dry Exner factor, and
+// (1 - 0) R_d + 0 R_v = R_d exactly (with or without contraction of the sum into an FMA); about nine instructions per cell and level less.
+template <bool DRY = false>
 __device__ __forceinline__ double buoyancy5(const DevGrid &g, double rth, double rq, int k, double rho, double rrho, double pi, double T_ref)
 {
+    if constexpr (DRY) {
+        const double T = pi * bz_cdiv(rth, rho, rrho);
+        const double rhop = rho * (g.Rd * T_ref / (g.Rd * T) - 1.0);
+        return -g.g * rhop;
+    }
     const double th = bz_cdiv(rth, rho, rrho), q = bz_cdiv(rq, rho, rrho);
     double T;
     if (__all(q == 0.0)) T = pi * th;
@@ -1038,7 +1081,7 @@ __global__ __launch_bounds__(64 * TY, BZ6_W_WAVES) void k6_w(DevGrid g, Lean5 L,
         const int B = bz_buffer_center(kbeg - 1, g.Nz);
         const double wt = (B == 3) ? bz_symm4(qw[0], qw[1], qw[2], qw[3]) : bz_symm2(qw[1], qw[2]);
         fz_lo = wt * bz_upB(wr[0], wr[1], wr[2], wr[3], wr[4], wr[5], wt > 0.0, B);
-        if constexpr (BM == 4) b_lo = buoyancy5(g, pa[n - sz], dryq ? 0.0 : pb[n - sz], kbeg - 1, LV.rho(kbeg - 1), LV.rrho(kbeg - 1), LV.pi(kbeg - 1), LV.T_r(kbeg - 1));
+        if constexpr (BM == 4) b_lo = buoyancy5<dryq>(g, pa[n - sz], dryq ? 0.0 : pb[n - sz], kbeg - 1, LV.rho(kbeg - 1), LV.rrho(kbeg - 1), LV.pi(kbeg - 1), LV.T_r(kbeg - 1));
         else if constexpr (BM == 0) b_lo = buoyancy3(g, bT[n - sz], bq[n - sz], kbeg - 1);
         else if constexpr (BM == 3) b_lo = bz_buoyancy(g, bT, bq, (long long)(n - sz), kbeg - 1);
         else if constexpr (BM == 2) { b_lo = bT[n - sz] - g.p_r[kbeg - 1]; r_lo = bq[n - sz] - g.rho[kbeg - 1]; }
@@ -1079,6 +1122,13 @@ __global__ __launch_bounds__(64 * TY, BZ6_W_WAVES) void k6_w(DevGrid g, Lean5 L,
         const double *wrow = Tk[ty + 3] + tc;
         const double ut = (Bf == 3) ? bz_symm4(qu[0], qu[1], qu[2], qu[3]) : bz_symm2(qu[1], qu[2]);
         const double fx = ut * bz_up5(wrow[-3], wrow[-2], wrow[-1], w0, wrow[1], wrow[2], ut > 0.0);
+        // flux at x-face i + 1: lane tx + 1 (DPP move) or, in the row's last lane le, lane `src` of the out-of-wave batch (v_readlane, src
+        // wave-uniform); formed here, ahead of the level's barrier, which neither operand depends on.  Lane 63 receives 0 from the shift: it is
+        // lane le (replaced) or a lane beyond a ragged row (store = false).
+        double nb = bz_lane_down(fx);
+        const double e = bz_lane_read(edge, src);
+        if (tx == le) nb = e;
+        const double dx = nb - fx;
         const double vt = (Bf == 3) ? bz_symm4(qv[0], qv[1], qv[2], qv[3]) : bz_symm2(qv[1], qv[2]);
         const double fy = vt * bz_up5y<WY>(Tk[ty][tc], Tk[ty + 1][tc], Tk[ty + 2][tc], w0, Tk[ty + 4][tc], Tk[ty + 5][tc], vt > 0.0, by5_face<WY>(g, __builtin_amdgcn_readfirstlane(j)));
         FY[buf][ty][tx] = fy;
@@ -1095,7 +1145,7 @@ __global__ __launch_bounds__(64 * TY, BZ6_W_WAVES) void k6_w(DevGrid g, Lean5 L,
             fz_hi = wt * bz_upB(wr[1], wr[2], wr[3], wr[4], wr[5], wnew, wt > 0.0, B);
         }
         double b_hi = 0.0, r_hi = 0.0;
-        if constexpr (BM == 4) b_hi = buoyancy5(g, Tcur, rqcur, k, LV.rho(k), LV.rrho(k), LV.pi(k), LV.T_r(k));
+        if constexpr (BM == 4) b_hi = buoyancy5<dryq>(g, Tcur, rqcur, k, LV.rho(k), LV.rrho(k), LV.pi(k), LV.T_r(k));
         else if constexpr (BM == 0) b_hi = buoyancy3(g, Tcur, rqcur, k);
         else if constexpr (BM == 3) b_hi = bz_buoyancy(g, bT, bq, (long long)n, k);
         else if constexpr (BM == 2) { b_hi = Tcur - g.p_r[k]; r_hi = rqcur - g.rho[k]; }
@@ -1103,10 +1153,6 @@ __global__ __launch_bounds__(64 * TY, BZ6_W_WAVES) void k6_w(DevGrid g, Lean5 L,
         if (hok) T[buf ^ 1][hr][hc] = ST ? p_h : bz_cdiv(p_h, LV.rho_f(k + 1), LV.rrho_f(k + 1));
         bz6_barrier();
         {
-            double nb = __shfl_down(fx, 1);
-            const double e = __shfl(edge, src);
-            if (tx == le) nb = e;
-            const double dx = nb - fx;
             const double dy = FY[buf][ty + 1][tx] - fy;
             const double adv = -((ST ? g.Vinv_f[k] : LV.Vinv_f(k)) * (dx + dy + (fz_hi - fz_lo)));
             double Gval;

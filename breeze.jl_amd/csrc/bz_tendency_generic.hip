@@ -612,8 +612,10 @@ __global__ __launch_bounds__(64 * MTY, MARCH_WAVES) void k_tendency_m(DevGrid g,
             const int kl = k + l;
             const long long m = n + l * sz;
             const double fx = Fl.X(m, kl);
-            double nb = XC ? __shfl_up(fx, 1) : __shfl_down(fx, 1);
-            const double e = __shfl(edge, kl - kbeg);
+            // neighbour lane's flux by a DPP move, the out-of-wave one by v_readlane (bz_internal.h; kl - kbeg is wave-uniform); whole rows only,
+            // so the lane the shift leaves at 0 is always lane le, replaced below
+            double nb = XC ? bz_lane_up(fx) : bz_lane_down(fx);
+            const double e = bz_lane_read(edge, kl - kbeg);
             if (tx == le) nb = e;
             AX[l][ty][tx] = XC ? bz_sub_rounded(fx, nb) : bz_sub_rounded(nb, fx);
             const int reps = (ty == l) ? 2 : 1;            // wave-uniform: wave l also takes the outside row of level l
