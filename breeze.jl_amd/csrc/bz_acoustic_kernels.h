@@ -30,14 +30,11 @@ __device__ __forceinline__ bool ac_accumulate(const AcParams &P)
 // earlier (PMC r05: stage-init 12.2 GB per launch for 10.2 GB of words, stage-end 23.0 / 25.1 for 19.9 / 22.0).  Here XCD c owns the groups of
 // eight rows G = c, c + 8, ... and walks a group x fastest, then its eight rows, then z: the level below is eight rows of traffic away (~0.7 MB),
 // the row below inside the group too.  Ny a multiple of 64, else launch order.
-#ifndef AC_PENCIL
-#define AC_PENCIL 1
-#endif
 __device__ __forceinline__ void ac_pencil_block(int &bx, int &j, int &k)
 {
     bx = blockIdx.x; j = blockIdx.y; k = blockIdx.z;
     const unsigned gx = gridDim.x, gy = gridDim.y, gz = gridDim.z;
-    if (AC_PENCIL && (gy & 63u) == 0) {
+    if ((gy & 63u) == 0) {
         const unsigned w = bx + gx * (j + gy * k), c = w & 7u;
         unsigned r = w >> 3;
         bx = (int)(r % gx); r /= gx;
@@ -180,21 +177,11 @@ __device__ __forceinline__ double ac_face_update(double up, double G, double rt_
 
 // block shapes of the column kernels (measured on MI355X, 512x512x256: forward sweep 64x4 99 ms/step vs 256x1 102;
 // backward sweep 256x1 32.5 vs 64x4 37.8)
-#ifndef ACX
 #define ACX 64
-#endif
-#ifndef ACY
 #define ACY 4
-#endif
-#ifndef ABX
 #define ABX 256
-#endif
-#ifndef ABY
 #define ABY 1
-#endif
-#ifndef AC_MINW
 #define AC_MINW 1
-#endif
 // _build_predictors! + _build_vertical_rhs! + forward sweep of the BatchedTridiagonalSolver
 // (acoustic_substepping.jl:605-659,907-970).  FUSED: the horizontal step (k_ac_horizontal) of the four faces of the
 // column is evaluated in place of loading (rho u)', (rho v)': each face is computed by its two adjacent columns with
@@ -229,10 +216,7 @@ __global__ __launch_bounds__(ACX * ACY, AC_MINW) void k_ac_column_forward(DevGri
     // the whole grid later (47 KB per block and level x 1024 resident blocks: long evicted), so every line of theta_L and C crossed
     // the fabric twice.  Now the x neighbours come from the neighbouring lanes' ring values (a row of the block is one wavefront; only
     // its two edge lanes load), and the y neighbours are requested together with the own-column value of their level and carried.
-#ifndef AC_FX
-#define AC_FX 1
-#endif
-    const bool FX = AC_FX && FUSED && (ACX == 64) && sizeof(ST) == 8;      // (Float32 working fields: measured slower — 74 -> 101 ms per step of forward sweeps — and stay on the loads)
+    const bool FX = FUSED && (ACX == 64) && sizeof(ST) == 8;      // (Float32 working fields: measured slower — 74 -> 101 ms per step of forward sweeps — and stay on the loads)
     const int lane = threadIdx.x;
     double thy_m0 = 0.0, thy_p0 = 0.0, thy_m1 = 0.0, thy_p1 = 0.0;      // theta_L of rows j-1 / j+1 at levels k and k+1
     double cy_m0 = 0.0, cy_p0 = 0.0;                                    // C of rows j-1 / j+1 at level k
@@ -373,30 +357,11 @@ __device__ __forceinline__ T ac_ld(const T *base, unsigned e)
 {
     return *(const T *)((const char *)base + (size_t)(e * (unsigned)sizeof(T)));
 }
+// (non-temporal forms for the words no other column reads were tried and did not pay: every access is a plain one)
 template <class T, class V>
 __device__ __forceinline__ void ac_st(T *base, unsigned e, V v)
 {
     *(T *)((char *)base + (size_t)(e * (unsigned)sizeof(T))) = (T)v;
-}
-// the same for words no other column reads (or that are read once): non-temporal, so that they do not displace the neighbour-shared
-// lines (theta_L, C, (rho theta)', the momentum perturbations and their tendencies) from the L2 before the neighbour row asks for them
-#ifndef AC2_NT
-#define AC2_NT 0
-#endif
-#ifndef AC2_BARRIER
-#define AC2_BARRIER 0
-#endif
-template <class T>
-__device__ __forceinline__ T ac_ld_nt(const T *base, unsigned e)
-{
-    if (AC2_NT & 1) return __builtin_nontemporal_load((const T *)((const char *)base + (size_t)(e * (unsigned)sizeof(T))));
-    return ac_ld(base, e);
-}
-template <class T, class V>
-__device__ __forceinline__ void ac_st_nt(T *base, unsigned e, V v)
-{
-    if (AC2_NT & 2) __builtin_nontemporal_store((T)v, (T *)((char *)base + (size_t)(e * (unsigned)sizeof(T))));
-    else ac_st(base, e, v);
 }
 
 template <bool DAMP, bool PF>
@@ -486,7 +451,7 @@ __global__ __launch_bounds__((CFG & 1) ? 512 : 256, (CFG & 2) ? 3 : 2) void k_ac
             L.rp = pert(F.U0_rho_d, F.rho_d, e); L.rthp = pert(F.U0_rth, F.rth, e);
             L.rt_ym = pert(F.U0_rth, F.rth, eym); L.rt_yp = pert(F.U0_rth, F.rth, eyp);
         } else {
-        L.rp = ac_ld_nt(F.rp, e); L.rthp = ac_ld(F.rthp, e);
+        L.rp = ac_ld(F.rp, e); L.rthp = ac_ld(F.rthp, e);
         L.rt_ym = ac_ld(F.rthp, eym); L.rt_yp = ac_ld(F.rthp, eyp);
         }
         L.o0 = 0.0; L.o_ym = 0.0; L.o_yp = 0.0;
@@ -504,8 +469,8 @@ __global__ __launch_bounds__((CFG & 1) ? 512 : 256, (CFG & 2) ? 3 : 2) void k_ac
             L.p_ym = ac_ld(F.p, eym); L.p_yp = ac_ld(F.p, eyp);
         }
         L.au_o = 0.0; L.av_o = 0.0;
-        if (!FIRST && acc && P.acc_mode != 1) { L.au_o = ac_ld_nt(F.au, e); L.av_o = ac_ld_nt(F.av, e); }
-        L.Grho = ac_ld_nt(F.G_rho_d, e); L.Grth = ac_ld_nt(F.G_rth, e); L.Gs_k = ac_ld_nt(F.Gs, e);
+        if (!FIRST && acc && P.acc_mode != 1) { L.au_o = ac_ld(F.au, e); L.av_o = ac_ld(F.av, e); }
+        L.Grho = ac_ld(F.G_rho_d, e); L.Grth = ac_ld(F.G_rth, e); L.Gs_k = ac_ld(F.Gs, e);
         L.e_th = 0.0; L.e_C = 0.0; L.e_rt = 0.0; L.e_o = 0.0;
         if (edge) {
             const unsigned ee = e + dedge;
@@ -517,7 +482,7 @@ __global__ __launch_bounds__((CFG & 1) ? 512 : 256, (CFG & 2) ? 3 : 2) void k_ac
         const unsigned e1 = (k + 1 < Nz) ? e + sz : e, e2 = (k + 2 < Nz) ? e1 + sz : e1;
         L.C_n = ac_ld(F.Clin, e1); L.cy_mn = ac_ld(F.Clin, e1 + dym); L.cy_pn = ac_ld(F.Clin, e1 + dyp);
         L.th_n = ac_ld(F.thL, e2); L.thy_mn = ac_ld(F.thL, e2 + dym); L.thy_pn = ac_ld(F.thL, e2 + dyp);
-        L.w_n = INIT == 2 ? 0.0 : INIT == 1 ? pert_w(e1 + sz) : ac_ld_nt(F.rwp, e1 + sz);
+        L.w_n = INIT == 2 ? 0.0 : INIT == 1 ? pert_w(e1 + sz) : ac_ld(F.rwp, e1 + sz);
         return L;
     };
     constexpr bool PIPE = (CFG & 8) != 0;
@@ -589,18 +554,18 @@ __global__ __launch_bounds__((CFG & 1) ? 512 : 256, (CFG & 2) ? 3 : 2) void k_ac
             if (j == 0) ac_st(F.rthp, e + dym, rt_ym);
             if (j == g.Ny - 1) ac_st(F.rthp, e + dyp, rt_yp);
         }
-        ac_st_nt(F.rup, e, up0);
-        ac_st_nt(F.rvp, e, vp0);
+        ac_st(F.rup, e, up0);
+        ac_st(F.rvp, e, vp0);
         if (acc && (FIRST || P.acc_mode != 1)) {
-            ac_st_nt(F.au, e, au_n);
-            ac_st_nt(F.av, e, av_n);
+            ac_st(F.au, e, au_n);
+            ac_st(F.av, e, av_n);
         }
-        ac_st_nt(F.rs, e, rs);
-        ac_st_nt(F.rths, e, rths);
-        if (FIRST) ac_st_nt(F.tfac, e, t);
-        ac_st_nt(F.phi, e, phi);
+        ac_st(F.rs, e, rs);
+        ac_st(F.rths, e, rths);
+        if (FIRST) ac_st(F.tfac, e, t);
+        ac_st(F.phi, e, phi);
         phi_m = phi;
-        if (AC2_BARRIER || (CFG & 4)) __builtin_amdgcn_s_barrier();      // the rows of a block advance together: a row's y neighbours are requested while their lines are near
+        if (CFG & 4) __builtin_amdgcn_s_barrier();      // the rows of a block advance together: a row's y neighbours are requested while their lines are near
 
         // advance the rings
         rs_m = rs; rths_m = rths; rp_m = rp; rthp_m = rthp;

@@ -216,12 +216,7 @@ __global__ __launch_bounds__(256) void k_closure_tendencies(DevGrid g, ClosureFi
 // immediate offset, and a level costs each thread six own-column loads (requested one level ahead), at most two frame cells and the five
 // read-modify-writes.  Same expressions, same order of operations as k_closure_tendencies (which stays for walls, Flat y and ragged grids).
 // grid (Nx / 64, Ny / TY, ceil(Nz / kchunk)), block (64, TY); Nx % 64 == 0, Ny % TY == 0.
-#ifndef CL_KO
-#define CL_KO 0      // timing experiments only (results WRONG): 1 no read-modify-write of the G arrays; 2 no frame staging; 4 one barrier per level
-#endif
-#ifndef CL_NCH
-#define CL_NCH 2048
-#endif
+constexpr int CL_NCH = 2048;      // workgroups the chunking of the march aims for
 // Workgroup barrier that orders LDS traffic only (the idiom of k_tridiag_coop, bz_poisson.hip): __syncthreads() is a fence over every
 // address space, so hipcc drains the level's five read-modify-write stores (s_waitcnt vmcnt(0)) in front of each of the two barriers of
 // a level; the global traffic of this kernel is each thread's own column, nothing another thread reads.
@@ -330,7 +325,7 @@ __global__ __launch_bounds__(64 * TY, RHO::field ? 2 : 4) void k_closure_march(D
         if constexpr (RF) prho = rho3[n2];
         double hnext[HPT];
 #pragma unroll
-        for (int qq = 0; qq < HPT; ++qq) hnext[qq] = (hok[qq] && !(CL_KO & 2)) ? frame_load(qq, k) : 0.0;
+        for (int qq = 0; qq < HPT; ++qq) hnext[qq] = hok[qq] ? frame_load(qq, k) : 0.0;
 
         const double dz = g.dzc[k];
         const double rVc = g.rdx * (1.0 / dy) * g.rdzc[k];
@@ -380,17 +375,17 @@ __global__ __launch_bounds__(64 * TY, RHO::field ? 2 : 4) void k_closure_march(D
         const double t12_00 = T12(0, 0), t13_00 = T13(0, 0), t23_00 = T23(0, 0);
         {
             const double div = (Ax * T11(0) - Ax * T11(-1)) + (Ay * T12(0, 1) - Ay * t12_00) + (Az * T13(0, 1) - Az * t13_00);
-            if (!(CL_KO & 1)) Gu[n] -= scale * (div * rVc); else if (div == 1.2345) Gu[n] = 0.0;
+            Gu[n] -= scale * (div * rVc);
         }
         {
             const double div = (Ax * T12(1, 0) - Ax * t12_00) + (Ay * T22(0) - Ay * T22(-1)) + (Az * T23(0, 1) - Az * t23_00);
-            if (!(CL_KO & 1)) Gv[n] -= scale * (div * rVc); else if (div == 1.2345) Gv[n] = 0.0;
+            Gv[n] -= scale * (div * rVc);
         }
         if (k >= 1) {
             const double dzf = g.dzf[k];
             const double Axf = dy * dzf, Ayf = dx * dzf;
             const double div = (Axf * T13(1, 0) - Axf * t13_00) + (Ayf * T23(1, 0) - Ayf * t23_00) + (Az * T33(0) - Az * T33(-1));
-            if (!(CL_KO & 1)) Gw[n] -= scale * (div * (g.rdx * (1.0 / dy) * g.rdzf[k])); else if (div == 1.2345) Gw[n] = 0.0;
+            Gw[n] -= scale * (div * (g.rdx * (1.0 / dy) * g.rdzf[k]));
         }
         const double kc = NU(0, 0, 0) * rPr;
         const double kxm = (NU(-1, 0, 0) * rPr + kc) / 2, kxp = (kc + NU(1, 0, 0) * rPr) / 2;
@@ -412,11 +407,11 @@ __global__ __launch_bounds__(64 * TY, RHO::field ? 2 : 4) void k_closure_march(D
             const double Jzm = (k == 0) ? 0.0 : rfm * (-kzm * ((c0 - cm) * rdzfm));
             const double Jzp = (k == g.Nz - 1) ? 0.0 : rfp * (-kzp * ((cp - c0) * rdzfp));
             const double div = (Ax * Jxp - Ax * Jxm) + (Ay * Jyp - Ay * Jym) + (Az * Jzp - Az * Jzm);
-            if (!(CL_KO & 1)) G[n] -= scale * (div * rVc); else if (div == 1.2345) G[n] = 0.0;
+            G[n] -= scale * (div * rVc);
         };
         scalar(TH, th_c, th_m, th_p, Gth);
         if constexpr (!RF) scalar(Q, q_c, q_m, q_p, Gq);
-        if (!(CL_KO & 4)) closure_lds_barrier();                           // every wave is done with slot k-1 and with the theta / q tile of level k
+        closure_lds_barrier();                           // every wave is done with slot k-1 and with the theta / q tile of level k
         // ---- stage level k+2 into the slot level k-1 leaves, and theta / q of level k+1 ----
         U[sm][r][c] = pu; V[sm][r][c] = pv; W[sm][r][c] = pw; NUt[sm][r][c] = pnu;
         if constexpr (RF) RHt[sm][r][c] = prho;

@@ -224,9 +224,7 @@ __global__ __launch_bounds__(64 * CTY) void k_scalar_tendency_rho3d_x(DevGrid g,
 // row outside the tile: wave 0).  7 loads per thread and level (13 with G_rho).  Same expressions per flux as k_scalar_tendency_rho3d_x:
 // same bits.  grid (Nx / 64, Ny / SLT, chunks): Nx a multiple of 64, Ny of SLT; XCD bands of tile rows where gridDim.y is a multiple of 8.
 // ---------------------------------------------------------------------------------------------------------------------
-#ifndef SLT
-#define SLT 8
-#endif
+#define SLT 8      // tile rows
 template <bool GRHO, bool WY = false>
 __global__ __launch_bounds__(64 * SLT, 2) void k_scalar_rho3d_lds(DevGrid g, double *__restrict__ Gc, double *__restrict__ Grho,
                                                                 const double *__restrict__ rho, const double *__restrict__ u,

@@ -54,8 +54,6 @@ void bzi_read_tuning(bz_tuning &t)
     t.no_closure_march = on("BZ_NO_CLOSURE_MARCH");
     t.no_dry_shortcut = on("BZ_NO_DRY_SHORTCUT");
     t.side_scalar = on("BZ_SIDE_SCALAR");
-    t.side_cus = num("BZ_SIDE_CUS", 0);
-    t.side_cu_layout = num("BZ_SIDE_CU_LAYOUT", 0);
     t.no_fuse_forcing = on("BZ_NO_FUSE_FORCING");
     t.no_fold_forcing = on("BZ_NO_FOLD_FORCING");
     t.no_fuse_level_sums = on("BZ_NO_FUSE_LEVEL_SUMS");
@@ -70,13 +68,9 @@ void bzi_read_tuning(bz_tuning &t)
     t.no_tridiag_coop = on("BZ_NO_TRIDIAG_COOP");
     t.no_xfft = on("BZ_NO_XFFT");
     t.poisson_kxmajor = num("BZ_POISSON_KXMAJOR", 1);
-    t.poisson_kx_chunk_mb = num("BZ_POISSON_KX_CHUNK_MB", 0);
     t.poisson_kx_pad = num("BZ_POISSON_KX_PAD", 1);
     t.poisson_kx_chunk_kb = num("BZ_POISSON_KX_CHUNK_KB", 0);
     t.poisson_chunk = num("BZ_POISSON_CHUNK", 0);
-    t.xf_kchunk_f = num("BZ_XF_KCHUNK_F", 0);
-    t.xf_kchunk_i = num("BZ_XF_KCHUNK_I", 0);
-    t.generic_onepass = on("BZ_GENERIC_ONEPASS");
     t.no_generic_march = on("BZ_NO_GENERIC_MARCH");
     t.no_rho3d_exchange = on("BZ_NO_RHO3D_EXCHANGE");
     t.scalar_lds = num("BZ_SCALAR_LDS", 1);

@@ -96,16 +96,13 @@ __device__ __forceinline__ void st_yface(const DevGrid &g, double *__restrict__ 
 // traffic, r02_pmc_traffic.json).  Here XCD c owns the rows j in [c Ny/8, (c+1) Ny/8) of every level and walks them x fastest,
 // then y, then z: the row below was read by the previous workgroups of the same XCD (except at its first row), the level below one
 // eighth of a plane earlier (1.8 MB of traffic at 512^2 Float64: inside the 4 MB L2), and all XCDs stream through the same level.
-#ifndef BZ_STREAM_BANDS_F32
-#define BZ_STREAM_BANDS_F32 1
-#endif
 __device__ __forceinline__ void bz_stream_block(int gx, int Ny, int nk, int &bx, int &j, int &k)
 {
     const unsigned w = blockIdx.x;
     unsigned r;
     // (Float32: round 3 measured plain launch order faster with one cell per thread, 0.87 against 0.95 ms for k_project_lean at 512^3; with two
-    // cells per thread — one workgroup per 512-cell row — the band order wins, 0.910 -> 0.872 ms: BZ_STREAM_BANDS_F32)
-    if ((sizeof(double) == 8 || BZ_STREAM_BANDS_F32) && (Ny & 7) == 0) {
+    // cells per thread — one workgroup per 512-cell row — the band order wins, 0.910 -> 0.872 ms: both precisions take it)
+    if ((Ny & 7) == 0) {
         const unsigned c = w & 7u, rows = (unsigned)Ny >> 3;
         r = w >> 3;
         bx = (int)(r % (unsigned)gx); r /= (unsigned)gx;
@@ -276,9 +273,7 @@ struct PLFields {
 };
 // PV consecutive x cells per thread: 1 in Float64; 2 in the Float32 build, where a 4-byte request per lane moves 256 bytes per wave
 // instruction — the Float32 kernel streamed at 3.7 TB/s against 5.5 TB/s for the same kernel in Float64 (round 4: 8 bytes per lane)
-#ifndef BZ_PV
-#define BZ_PV (sizeof(double) == 8 ? 1 : 2)
-#endif
+constexpr int BZ_PV = sizeof(double) == 8 ? 1 : 2;
 typedef double bz_pv2 __attribute__((ext_vector_type(2), aligned(sizeof(double))));      // two consecutive reals, element-aligned
 template <int PV> __device__ __forceinline__ void pv_load(const double *__restrict__ p, double (&v)[PV])
 {
@@ -362,12 +357,11 @@ __global__ __launch_bounds__(256) void k_project_lean(DevGrid g, PLFields F, dou
 static size_t xf_lds_bytes(int n2) { return ((size_t)XF_RB * XF_ROW_STRIDE(n2) + xf_w_entries(n2) + XF_WST_SLOTS(n2)) * sizeof(double2); }
 // levels one block of the x-transform kernels walks: 16 on large grids (the twiddle table is staged once per block), fewer when
 // that would leave less than ~1024 blocks for the 256 CUs (64^3: 32 blocks of 16 levels took 52 us, 512 blocks of one level 1/3 of that)
-static int xf_chunk(int forced, int dflt, const DevGrid &g)
+static int xf_chunk(int dflt, const DevGrid &g)
 {
     int kc = dflt;
     const long long rows = (long long)(g.Ny / XF_RB) * g.Nz;
     while (kc > 1 && rows / kc < 1024) kc >>= 1;
-    if (forced > 0) kc = forced;
     return kc < g.Nz ? kc : g.Nz;
 }
 
@@ -379,7 +373,7 @@ int bzi_xf_forward(bz_ctx *ctx, const bz_state *s, double dt, const bz_prognosti
 {
     const DevGrid &g = ctx->dg;
     if (khi <= 0) { klo = 0; khi = g.Nz; }      // whole column
-    const int n2 = g.Nx / 2, kc = xf_chunk(ctx->tune.xf_kchunk_f, 16, g);
+    const int n2 = g.Nx / 2, kc = xf_chunk(16, g);
     const dim3 grid(g.Ny / XF_RB, (khi - klo + kc - 1) / kc), block(XF_RB * (n2 / 4));
     const size_t lds = xf_lds_bytes(n2);
     XfLayout L;
@@ -410,7 +404,7 @@ int bzi_xf_inverse(bz_ctx *ctx, const double *hat, double *phi, int blocks, int 
 {
     const DevGrid &g = ctx->dg;
     if (khi <= 0) { klo = 0; khi = g.Nz; }
-    const int n2 = g.Nx / 2, kc = xf_chunk(ctx->tune.xf_kchunk_i, 16, g);
+    const int n2 = g.Nx / 2, kc = xf_chunk(16, g);
     XfLayout L;
     L.nkx = blocks > 1 ? ctx->nkx : n2 + 1;
     L.nxp = blocks > 1 ? ctx->nkx * blocks : n2 + 1;

@@ -361,8 +361,6 @@ struct bz_tuning {
     bool no_k6_stored = false;        // BZ_NO_K6_STORED: the stored-velocity tiers keep the fourth-generation tile kernels (k_{u,v,w}_tend_lds)
     bool no_dry_shortcut = false;     // BZ_NO_DRY_SHORTCUT: the lean kernels always carry rho q (no moisture scan)
     bool side_scalar = false;         // BZ_SIDE_SCALAR: scalar kernel beside the pressure solve on one GPU too
-    int side_cus = 0;                 // BZ_SIDE_CUS=N: the side stream is created on N of the GPU's CUs (CU mask)
-    int side_cu_layout = 0;           // BZ_SIDE_CU_LAYOUT (experiments): 0 the first N mask bits, 1 every (total / N)-th bit
     bool no_fuse_forcing = false;     // BZ_NO_FUSE_FORCING
     bool no_fold_forcing = false;     // BZ_NO_FOLD_FORCING: the fused-RK tier keeps the momentum terms of the forcing stack in the forcing pass
     int ac_xcd = 1;                   // BZ_AC_XCD=0: the forward acoustic sweep in launch order (XCD = tile column) instead of XCD = band of tile rows
@@ -378,15 +376,12 @@ struct bz_tuning {
     bool no_tridiag_coop = false;     // BZ_NO_TRIDIAG_COOP: sequential Thomas kernel
     bool no_xfft = false;             // BZ_NO_XFFT: library 2-D plans instead of the hand-written x transforms
     int poisson_kxmajor = 1;          // BZ_POISSON_KXMAJOR=0: level-major half spectrum, three whole-spectrum passes between the x transforms
-    int poisson_kx_chunk_mb = 0;      // BZ_POISSON_KX_CHUNK_MB: spectrum bytes per chunk of the kx-major pipeline (0: 256 MB)
     int poisson_kx_chunk_kb = 0;      // BZ_POISSON_KX_CHUNK_KB: the same in KB (tests: the chunked pipeline on small grids)
     int poisson_kx_pad = 1;           // BZ_POISSON_KX_PAD: phantom lines per wavenumber of the kx-major spectrum (0 .. 4)
     int poisson_chunk = 0;            // BZ_POISSON_CHUNK: level-chunked Poisson pipeline (needs BZ_NO_XFFT)
-    int xf_kchunk_f = 0, xf_kchunk_i = 0;      // BZ_XF_KCHUNK_F / _I: levels per block of the x transforms (0: automatic)
     int scalar_lds = 1;               // BZ_SCALAR_LDS=0: the 3-D-density scalar tendency keeps the kernel that reads its stencils through the L1 (k_scalar_tendency_rho3d_x)
     bool no_rho3d_exchange = false;   // BZ_NO_RHO3D_EXCHANGE: the compressible scalar tendency keeps the kernel that evaluates five fluxes per cell
     bool no_generic_march = false;    // BZ_NO_GENERIC_MARCH: WENO 7 / 9 keep the two-pass (flux arrays + divergence) kernels everywhere
-    bool generic_onepass = false;     // BZ_GENERIC_ONEPASS: WENO 7 / 9 with every flux evaluated by both of its cells
     bool no_ac_fuse = false;          // BZ_NO_AC_FUSE: three kernels per acoustic substep
     bool no_ac_end_fuse = false;      // BZ_NO_AC_END_FUSE: stage epilogue as finalize + recover + update_state (three passes) and store_initial_state as copies
     bool comm_no_overlap = false;     // BZ_COMM_NO_OVERLAP

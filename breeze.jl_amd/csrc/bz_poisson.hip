@@ -142,9 +142,7 @@ __global__ void __launch_bounds__(64) k_tridiag_solve(int NXH, int Ny, int Nz, c
 // 0.28 in Float32): the persistent grid below is sized for one resident workgroup per CU (`resident`), each walking ngroups / 256
 // column groups with the next group's rows in flight.  4 (two workgroups per CU, <= 128 VGPRs) was measured again in round 4 (ADVICE
 // r03): the kernel spills and takes 0.98 ms — the rows of a group held in registers are the design, not an accident of the allocator.
-#ifndef TCO_MIN_WAVES
 #define TCO_MIN_WAVES 2
-#endif
 // Workgroup barrier that orders LDS traffic only.  __syncthreads() is a workgroup-scope fence over every address space: hipcc then waits
 // for the global stores of the previous column group before it lets the next group's arithmetic start (s_waitcnt vmcnt(10) in the loop
 // of k_tridiag_coop), i.e. the store drain of every group is exposed.  Every barrier of that kernel protects LDS exchange buffers.
@@ -553,8 +551,9 @@ int bzi_poisson_setup(bz_ctx *ctx, const double *h_rho /* Nz+2Hz, halo-inclusive
         // 1.24 ms whole, 0.84 ms in 128 - 256 MB chunks).  That needs a wavenumber range to be contiguous: hatT[(kx Nz + k) Ny + ky]
         // (xf_addr, k_tridiag_coop::col_addr).  Shapes: the cooperative tridiagonal kernel's, Ny a multiple of its column group.
         const size_t spec = (size_t)ctx->NXH * Nz * Ny * sizeof(hipfftDoubleComplex);
+        constexpr size_t KX_CHUNK_MB = 256;      // spectrum bytes per chunk of the pipeline: the Infinity Cache
         const size_t chunk_bytes = ctx->tune.poisson_kx_chunk_kb > 0 ? (size_t)ctx->tune.poisson_kx_chunk_kb << 10      // (tests: small grids take the pipeline too)
-                                   : (size_t)(ctx->tune.poisson_kx_chunk_mb > 0 ? ctx->tune.poisson_kx_chunk_mb : 256) << 20;
+                                   : KX_CHUNK_MB << 20;
         if (ctx->tune.poisson_kxmajor && !g.bounded_y && tridiag_coop_segs(ctx, Ny) && Ny % TCO_COLS == 0 && spec > chunk_bytes + chunk_bytes / 2) {
             const int nch = (int)((spec + chunk_bytes - 1) / chunk_bytes);
             ctx->kx_cw = (ctx->NXH + nch - 1) / nch;

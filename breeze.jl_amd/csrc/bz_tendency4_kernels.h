@@ -16,9 +16,6 @@
 #include "bz_internal.h"
 #include "bz_weno.h"
 
-#ifndef BZ4_XCD
-#define BZ4_XCD 1
-#endif
 template <int TY>
 __global__ __launch_bounds__(64 * TY) void k_scalar_pair_lds(DevGrid g, const double *__restrict__ u,
                                                             const double *__restrict__ v,
@@ -41,7 +38,7 @@ __global__ __launch_bounds__(64 * TY) void k_scalar_pair_lds(DevGrid g, const do
     int bx = blockIdx.x, by = blockIdx.y, bz = blockIdx.z;
     {
         const unsigned gx = gridDim.x, gy = gridDim.y, W = gx * gy * gridDim.z;
-        if (BZ4_XCD && (W & 7u) == 0) {
+        if ((W & 7u) == 0) {
             unsigned w = bx + gx * (by + gy * bz);
             w = (w & 7u) * (W >> 3) + (w >> 3);
             bx = (int)(w % gx); by = (int)((w / gx) % gy); bz = (int)(w / (gx * gy));

@@ -41,17 +41,8 @@ int bzi_lean_setup(bz_ctx *ctx)
     hipLaunchKernelGGL(k_lev_rows, dim3((n + 63) / 64), dim3(64), 0, 0, g, ctx->d_pi_dry, (LevRow5 *)ctx->d_lev_rows, n);
     BZ_HIP(hipGetLastError());
     BZ_HIP(hipDeviceSynchronize());
-    if (ctx->tune.side_cus > 0 && ctx->tune.side_cus < ctx->num_cus) {
-        // a side stream that owns a share of the CUs: the scalar-pair kernel (issue-bound) then runs BESIDE the pressure solve (bandwidth-
-        // bound) instead of in front of it — two unmasked streams simply take turns (measured: every kernel stretches by the other's time)
-        uint32_t mask[32] = {0};
-        const int total = ctx->num_cus, want = ctx->tune.side_cus;
-        for (int b = 0; b < want; ++b) {
-            const int bit = ctx->tune.side_cu_layout == 1 ? (int)((long long)b * total / want) : b;
-            mask[bit >> 5] |= 1u << (bit & 31);
-        }
-        BZ_HIP(hipExtStreamCreateWithCUMask(&ctx->side_stream, (uint32_t)((total + 31) / 32), mask));
-    } else
+    // plain side stream: two unmasked streams take turns (every kernel stretches by the other's time), and a side stream on a CU mask of its
+    // own bought nothing either (HISTORY.md)
     BZ_HIP(hipStreamCreateWithFlags(&ctx->side_stream, hipStreamNonBlocking));
     BZ_HIP(hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming));
     BZ_HIP(hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming));

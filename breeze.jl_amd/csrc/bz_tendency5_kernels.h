@@ -22,30 +22,6 @@
 // element index type of the momentum kernels: 64-bit, so that the +-1, +-2, +-3 neighbours of a row fold into the immediate offset
 // of one address per array and level (with 32-bit unsigned indices every neighbour costs its own address arithmetic: measured
 // +10 % on the x-momentum kernel); the scalar-pair kernel keeps 32-bit indices, which is what lets it fit 128 VGPRs
-#ifndef BZ_KO
-#define BZ_KO 0      // timing experiments only (tools/gpu_knockout.sh): bit n removes one ingredient of k5_scalar_pair; results are then WRONG
-#endif
-#ifndef BZ6_ROTATE_DUTY
-#define BZ6_ROTATE_DUTY 0
-#endif
-#ifndef BZ6_UNROLL2
-#define BZ6_UNROLL2 0
-#endif
-#ifndef BZ6_LDS_BARRIER
-#define BZ6_LDS_BARRIER 0
-#endif
-// per-level barrier of the sixth-generation kernels: __syncthreads(), or (experiments) the LDS-scoped release / s_barrier / acquire idiom that
-// leaves the level's global loads and stores in flight across it (bz_poisson.hip: tco_lds_barrier)
-__device__ __forceinline__ void bz6_barrier()
-{
-#if BZ6_LDS_BARRIER
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-#else
-    __syncthreads();
-#endif
-}
 typedef long long ix_t;
 typedef unsigned ix32_t;     // z-momentum kernel: 32-bit (138 -> 121 VGPRs, 3 -> 4 waves per SIMD; measured 3.61 -> 2.94 ms)
 
@@ -84,34 +60,20 @@ static_assert(sizeof(LevRow5) == 16 * sizeof(double), "LevRow5 is sixteen reals"
 // build (three workgroups, <= 80 VGPRs: a Float32 value is one register, and the Float32 kernels sat at 84-85 — allocated as 88,
 // i.e. five waves per SIMD = still two workgroups).  Measured at 512^3 Float32: scalar-pair kernel 2.04 -> 1.88 ms with three spilled
 // registers; the z-momentum kernel and the forcing variant of the y-momentum kernel spill eight and lose 7-13 %, so they keep the default.
-#ifndef BZ_LEAN_WAVES
 #define BZ_LEAN_WAVES (sizeof(double) == 8 ? 4 : 6)
-#endif
 // Round-4 additions to the scalar-pair kernel — the zero-field shortcut of the second scalar and ring tops requested one level ahead —
 // cost ~8 registers.  The Float32 kernel sat at 80 registers for six waves per SIMD: with the additions it spilled (19 registers,
 // 1.78 -> 2.48 ms per launch at 512^3; the shortcut alone 2.25), so the Float32 scalar kernel is compiled for four waves per SIMD
 // instead (two workgroups per CU, as Float64) with both additions on: 1.47 ms (four waves without them: 1.85).  The momentum kernels
 // keep BZ_LEAN_WAVES.
-#ifndef BZ5_ZERO_SHORTCUT
-#define BZ5_ZERO_SHORTCUT 1
-#endif
-#ifndef BZ5_TOPS_AHEAD
-#define BZ5_TOPS_AHEAD 1
-#endif
-#ifndef BZ6_W_WAVES
-#define BZ6_W_WAVES 4
-#endif
 // (later in round 4 the Float32 objects lost the SLP vectoriser — csrc/Makefile: F32FLAGS — and with it the operand-pair moves: the Float32
 // scalar kernel needs 75 - 80 registers with both additions and runs at six waves again: 0.97 -> 0.92 ms per launch in its dry form)
-#ifndef BZ5_EB
-#define BZ5_EB 64      // levels per batch of the out-of-wave x flux (lane l <-> level k + l): a power of two <= 64
-#endif
-#ifndef BZ5_RAW_LDS
-#define BZ5_RAW_LDS 0      // 1: the general scalar-pair body's own-cell raw prognostic values ride LDS slots instead of being re-read (measured: 1.6 GB less traffic per launch, 1.5 % faster on one box, 4 % slower on another: off)
-#endif
-#ifndef BZ5_SCALAR_WAVES
 #define BZ5_SCALAR_WAVES (sizeof(double) == 8 ? 4 : 6)
-#endif
+#define BZ6_W_WAVES 4           // the z-momentum kernel, both precisions
+constexpr int BZ5_EB = 64;      // levels per batch of the out-of-wave x flux (lane l <-> level k + l): a power of two <= 64
+// Decided experiments of the momentum kernels' level loop (HISTORY.md has the figures): the per-level barrier is __syncthreads() — an
+// LDS-scoped release / s_barrier / acquire bought nothing —, the top-row duty flux stays with wave 0 (rotated over the waves: +2 %), and the
+// loop is not unrolled by two.
 
 struct Lean5 {
     const double *ru, *rv, *rw;      // stage-start momentum (halos valid)
@@ -228,7 +190,7 @@ __device__ __forceinline__ double bz_symm4y(double qm2, double qm1, double q0, d
 // (update_atmosphere_model_state.jl:333-343).  Every flux of it is an exact zero and its update is 0 -> 0, so the instantiation
 // neither loads nor stores anything of q: 4.6 of the kernel's 13 words per cell.  Identical bits: the arrays stay zero.
 template <int TY, bool WY, bool DRYQ>
-__device__ __forceinline__ void k5_scalar_pair_body(const DevGrid &g, const Lean5 &F, int kchunk, const RKEpilogue &E, double *Tp, double *FYp, int *ZF, double *RAWp)
+__device__ __forceinline__ void k5_scalar_pair_body(const DevGrid &g, const Lean5 &F, int kchunk, const RKEpilogue &E, double *Tp, double *FYp, int *ZF)
 {
     constexpr bool Q = !DRYQ;
     constexpr int TR = TY + 6, TC = 72;                 // tile rows, padded row length (70 used)
@@ -237,11 +199,8 @@ __device__ __forceinline__ void k5_scalar_pair_body(const DevGrid &g, const Lean
     constexpr int HPT = (NHALO + NT - 1) / NT;          // frame cells per thread
     double(*T)[2][TR][TC] = (double(*)[2][TR][TC])Tp;                  // T[2][2][TR][TC]
     double(*FY)[2][TY + 1][64] = (double(*)[2][TY + 1][64])FYp;        // FY[2][2][TY + 1][64]
-    // General body: the RAW rho theta, rho q of the own column's levels k .. k + 2, each thread's own three slots per field (no barrier: a
-    // thread reads and writes only its own).  The RK update needs the cell's prognostic bits; they arrived three levels earlier as ring
-    // tops, and re-reading them from memory then (round 4) went to the fabric for two words per cell (PMC: 13.9 GB per launch for 8.9 GB
-    // of compulsory words — the dry body, which has the registers to carry them, moves 1.30x its words).  RAW[3][2][NT].
-    double *__restrict__ RAW = RAWp;
+    // General body: the RK update re-reads the cell's own prognostic values.  Carrying them in per-thread LDS slots instead moved 1.6 GB
+    // less per launch and was 1.5 % faster on one box, 4 % slower on another, so they are re-read.
     // Zero-field shortcut of the second scalar (rho q of a dry run is identically zero, and the reference advects it all the same:
     // update_atmosphere_model_state.jl:333-343).  ZF[l % 3] != 0: every staged value of q at level l — the tile and its frame — is +-0.
     // Then the x / y reconstructions of that level return exactly 0 (WENO of zeros; every variant of bz_weno5) and the fluxes are
@@ -249,7 +208,7 @@ __device__ __forceinline__ void k5_scalar_pair_body(const DevGrid &g, const Lean
     // per-thread count of consecutive zero ring tops.  Identical bits either way (the sums of +-0 fluxes the RK update sees are +0 with
     // or without the shortcut, and alpha (0 + dt * -0) = +0); costs ~8 instructions per level where q is not zero, saves three
     // reconstructions (~150) where it is.  (ZF: three ints of the caller's LDS; this local form still serves fields that are zero only in part.)
-    constexpr bool ZS = BZ5_ZERO_SHORTCUT && Q;
+    constexpr bool ZS = Q;
 
     int bx, by, bz;
     bz_block5(F, bx, by, bz);
@@ -310,7 +269,6 @@ __device__ __forceinline__ void k5_scalar_pair_body(const DevGrid &g, const Lean
         if constexpr (Q) {
             const double rawb = pb[n + s * sz - 3 * sz];
             b[s] = bz_cdiv(rawb, rh, rr);
-            if (BZ5_RAW_LDS && s >= 3) { RAW[((s - 3) * 2 + 0) * NT + t] = raw; RAW[((s - 3) * 2 + 1) * NT + t] = rawb; }
         } else b[s] = 0.0;
     }
     double fza, fzb = 0.0;
@@ -357,8 +315,8 @@ __device__ __forceinline__ void k5_scalar_pair_body(const DevGrid &g, const Lean
     double rvtop_n = (tyu == 0 || (Q && tyu == TY / 2)) ? rv[ntop0] : 0.0;      // top-face duties of the first level: rows 0 and TY / 2
     // ring tops arrive one level ahead as well: they are consumed mid-level (vertical flux), and a load issued at the top of its own
     // level sits behind the previous level's stores in the in-order memory counter
-    double ta_nx = 0.0, tb_nx = 0.0;
-    if constexpr (BZ5_TOPS_AHEAD) { ta_nx = pa[n + 3 * sz]; if constexpr (Q) tb_nx = pb[n + 3 * sz]; }
+    double ta_nx = pa[n + 3 * sz], tb_nx = 0.0;
+    if constexpr (Q) tb_nx = pb[n + 3 * sz];
     for (int k = kbeg; k < kend; ++k, n += sz) {
         // ---- loads, issued in the order their values are needed (s_waitcnt counts vector loads in order, so waiting for a load
         //      waits for everything issued before it): ring tops (vertical flux, mid-level), next level's frame cells (staging, end of
@@ -367,14 +325,11 @@ __device__ __forceinline__ void k5_scalar_pair_body(const DevGrid &g, const Lean
         //      latency per level and wave, because the advecting fluxes are the first thing a level computes) ----
         double ha[HPT], hb[HPT];
         const unsigned lev = (unsigned)(k + 1 - kbeg) * sz;
-        double ta_raw, tb_raw = 0.0;
-        if constexpr (BZ5_TOPS_AHEAD) {
-            ta_raw = ta_nx; tb_raw = tb_nx;
-            const unsigned up = (k + 4 <= g.Nz + g.Hz - 1) ? 4 * sz : 3 * sz;      // the last level's request stays inside the parent array (unused)
-            ta_nx = pa[n + up];
-            if constexpr (Q) tb_nx = pb[n + up];
-        } else { ta_raw = pa[n + 3 * sz]; if constexpr (Q) tb_raw = pb[n + 3 * sz]; }
-        const int lv3 = (ZS || (Q && BZ5_RAW_LDS)) ? (k - kbeg) % 3 : 0;
+        const double ta_raw = ta_nx, tb_raw = tb_nx;
+        const unsigned up = (k + 4 <= g.Nz + g.Hz - 1) ? 4 * sz : 3 * sz;      // the last level's request stays inside the parent array (unused)
+        ta_nx = pa[n + up];
+        if constexpr (Q) tb_nx = pb[n + up];
+        const int lv3 = ZS ? (k - kbeg) % 3 : 0;
         bool zxy = false;
         if constexpr (ZS) {
             if (t == 0) ZF[(lv3 + 2) % 3] = 1;      // reset the flag of level k + 2 (set while level k + 1 is staged, at the end of the next trip)
@@ -382,17 +337,16 @@ __device__ __forceinline__ void k5_scalar_pair_body(const DevGrid &g, const Lean
         }
 #pragma unroll
         for (int q = 0; q < HPT; ++q) {
-            if (BZ_KO & 2) { ha[q] = ta_raw; hb[q] = tb_raw; }
-            else { ha[q] = hok[q] ? pa[hn[q] + lev] : 0.0; hb[q] = (Q && hok[q]) ? pb[hn[q] + lev] : 0.0; }
+            ha[q] = hok[q] ? pa[hn[q] + lev] : 0.0;
+            hb[q] = (Q && hok[q]) ? pb[hn[q] + lev] : 0.0;
         }
-        const double u0a = (BZ_KO & 16) ? ta_raw : (E.mode == 2) ? E.u0[n] : 0.0, u0b = (BZ_KO & 16) ? tb_raw : (Q && E.mode == 2) ? E.u0b[n] : 0.0;
+        const double u0a = (E.mode == 2) ? E.u0[n] : 0.0, u0b = (Q && E.mode == 2) ? E.u0b[n] : 0.0;
         const double ru_t = ru_n, rv_t = rv_n, rw_t = rw_n, rvtop = rvtop_n;
         // The y face above the tile belongs to no row of the tile: one wavefront per field evaluates it, and the duty rotates with the
         // level (field a: row (k - kbeg) mod TY, field b: half a turn later).
         const int turn = (k - kbeg) & (TY - 1);
         const bool duty_a = tyu == turn, duty_b = Q && tyu == ((turn + TY / 2) & (TY - 1));
-        if (BZ_KO & 32) { ru_n = ta_raw * 1e-3; rv_n = tb_raw; rw_n = ta_raw * 1e-4; } else {
-        ru_n = ru[n + sz]; rv_n = rv[n + sz]; rw_n = rw[n + 2 * sz]; }      // level k + 1 (level kend of the last trip is a halo level: in bounds, unused)
+        ru_n = ru[n + sz]; rv_n = rv[n + sz]; rw_n = rw[n + 2 * sz];      // level k + 1 (level kend of the last trip is a halo level: in bounds, unused)
         {
             const int turn_n = (turn + 1) & (TY - 1);
             const bool duty_n = tyu == turn_n || (Q && tyu == ((turn_n + TY / 2) & (TY - 1)));
@@ -459,15 +413,14 @@ __device__ __forceinline__ void k5_scalar_pair_body(const DevGrid &g, const Lean
         } else {
             const double(*Tk)[TC] = T[buf][1];
             const double *rr_ = Tk[ty + 3] + tx;
-            if (BZ_KO & 128) { fxb = rho * (cfx * b[3]); fyb = rho * (cfy * b[3]); } else {
             fxb = rho * (cfx * bz_up5(rr_[0], rr_[1], rr_[2], b[3], rr_[4], rr_[5], lx));
-            fyb = rho * (cfy * bz_up5y<WY>(Tk[ty][c], Tk[ty + 1][c], Tk[ty + 2][c], b[3], Tk[ty + 4][c], Tk[ty + 5][c], ly, Byj)); }
+            fyb = rho * (cfy * bz_up5y<WY>(Tk[ty][c], Tk[ty + 1][c], Tk[ty + 2][c], b[3], Tk[ty + 4][c], Tk[ty + 5][c], ly, Byj));
             FY[buf][1][ty][tx] = fyb;
             if (duty_b)
                 FY[buf][1][TY][tx] = rho * (cfy2 * bz_up5y<WY>(Tk[TY][c], Tk[TY + 1][c], Tk[TY + 2][c], Tk[TY + 3][c], Tk[TY + 4][c], Tk[TY + 5][c], ly2, Byt));
         }
         if (zz) fzb_hi = 0.0;
-        else fzb_hi = (BZ_KO & 128) ? rf * (cfz * b[3]) : rf * (cfz * bz_upB(b[1], b[2], b[3], b[4], b[5], tb, lz, Bz));
+        else fzb_hi = rf * (cfz * bz_upB(b[1], b[2], b[3], b[4], b[5], tb, lz, Bz));
         }
         // x flux of the upper face = the low-face flux of lane tx + 1 (DPP move, vector ALU) or, in the row's last lane le, lane `src` of the
         // out-of-wave batch (v_readlane: src is wave-uniform).  Formed here, where the fluxes are complete, not behind the level's barrier:
@@ -489,12 +442,7 @@ __device__ __forceinline__ void k5_scalar_pair_body(const DevGrid &g, const Lean
         // arithmetic so that the RK update after the barrier finds them
         double pa_n, pb_n;
         if constexpr (DRYQ) { pa_n = araw[0]; pb_n = b[3]; araw[0] = araw[1]; araw[1] = araw[2]; araw[2] = ta_raw; }
-        else if (BZ_KO & 4) { pa_n = a[3]; pb_n = b[3]; }
-        else if constexpr (BZ5_RAW_LDS) {
-            double *ra = RAW + (lv3 * 2 + 0) * NT + t, *rb = ra + NT;
-            pa_n = *ra; pb_n = *rb;
-            *ra = ta_raw; *rb = tb_raw;      // level k + 3 takes the slot
-        } else { pa_n = pa[n]; pb_n = pb[n]; }
+        else { pa_n = pa[n]; pb_n = pb[n]; }
         // ---- stage level k+1 in the other buffer ----
         T[buf ^ 1][0][ty + 3][tx + 3] = a[4];
         if constexpr (Q) T[buf ^ 1][1][ty + 3][tx + 3] = b[4];
@@ -513,7 +461,7 @@ __device__ __forceinline__ void k5_scalar_pair_body(const DevGrid &g, const Lean
                 }
             if (ZS && !__all(z1) && tx == 0) ZF[(lv3 + 1) % 3] = 0;
         }
-        if (!(BZ_KO & 64)) __syncthreads();
+        __syncthreads();
         // ---- combine, SSP-RK3 update, temperature of the updated cell for the next stage's buoyancy ----
         {
             const double dya = FY[buf][0][ty + 1][tx] - fya;
@@ -562,9 +510,8 @@ __global__ __launch_bounds__(64 * TY) __attribute__((amdgpu_waves_per_eu(BZ5_SCA
     __shared__ double T[2 * 2 * TR * TC];
     __shared__ double FY[2 * 2 * (TY + 1) * 64];
     __shared__ int ZF[3];
-    __shared__ double RAW[(!DRYQ && BZ5_RAW_LDS) ? 3 * 2 * 64 * TY : 1];
     if (bz_lean_skip<DRYQ, GUARD>(F)) return;
-    k5_scalar_pair_body<TY, WY, DRYQ>(g, F, kchunk, E, T, FY, ZF, RAW);
+    k5_scalar_pair_body<TY, WY, DRYQ>(g, F, kchunk, E, T, FY, ZF);
 }
 
 // out-of-wave x fluxes of the momentum kernels with the advected velocity derived from its momentum component
@@ -626,7 +573,7 @@ __global__ __launch_bounds__(64 * TY, BZ_LEAN_WAVES) void k6_u(DevGrid g, Lean5 
     F.ru = L.ru; F.rv = L.rv; F.rw = L.rw; F.u = F.v = F.w = F.T = F.q = nullptr; F.c = ST ? L.vel : nullptr; F.G = L.out;
     ix_t n = (ix_t)g.idx(ic, jc, kbeg);
     // frame cell 1: the u tile's frame (raw rho_u; its side cells next to the interior also feed the raw rho_u tile)
-    const bool h1ok = !(BZ_KO & 32768) && t < NH1;
+    const bool h1ok = t < NH1;
     int h1r = 0, h1c = 0;
     {
         const int h = h1ok ? t : 0;
@@ -636,7 +583,7 @@ __global__ __launch_bounds__(64 * TY, BZ_LEAN_WAVES) void k6_u(DevGrid g, Lean5 
     const ix_t h1n = (ix_t)g.idx(min(i0 - 3 + h1c, g.Nx + 2), min(j0 - 3 + h1r, g.Ny + 2), kbeg);
     const bool h1raw = h1ok && h1r >= 3 && h1r < TY + 3 && (h1c == 2 || h1c == 67 || h1c == 68);
     // frame cell 2: rho_v side columns (cols i0-2, i0-1, i0+64; rows j0 .. j0+TY), rho_v top row, rho_w side columns (upper face)
-    const bool h2ok = !(BZ_KO & 32768) && t < NH2;
+    const bool h2ok = t < NH2;
     int h2sel = 0, h2r = 0, h2c = 0;             // sel 0: rho_v, 1: rho_w
     {
         const int id = h2ok ? t : 0;
@@ -670,9 +617,6 @@ __global__ __launch_bounds__(64 * TY, BZ_LEAN_WAVES) void k6_u(DevGrid g, Lean5 
 
     double edge = 0.0;
     int buf = 0;
-#if BZ6_UNROLL2
-#pragma unroll 2
-#endif
     for (int k = kbeg; k < kend; ++k, n += sz) {
         const ix_t lev1 = (ix_t)(k + 1 - kbeg) * sz;
         // ---- prefetch for level k+1 (consumed at the end of this iteration / in the next one) ----
@@ -680,11 +624,11 @@ __global__ __launch_bounds__(64 * TY, BZ_LEAN_WAVES) void k6_u(DevGrid g, Lean5 
         // behind the ring-top load: the stored-velocity ring top took its registers
         const double p_top = ST ? ru[n + sz] : ru[n + ((k + 4 <= g.Nz + g.Hz - 1) ? 4 * sz : 3 * sz)];
         const double p_topv = ST ? vel[n + ((k + 4 <= g.Nz + g.Hz - 1) ? 4 * sz : 3 * sz)] : 0.0;
-        const double p_h1 = (BZ_KO & 256) ? p_top : h1ok ? (ST ? vel : ru)[h1n + lev1] : 0.0;
+        const double p_h1 = h1ok ? (ST ? vel : ru)[h1n + lev1] : 0.0;
         const double p_h1raw = (ST && h1raw) ? ru[h1n + lev1] : 0.0;
-        const double p_h2 = (BZ_KO & 512) ? p_top : h2ok ? h2src[h2n + lev1] : 0.0;
-        const double p_rv = (BZ_KO & 1024) ? p_top * 0.5 : rv[n + sz], p_rw = (BZ_KO & 1024) ? p_top * 0.25 : rw[n + 2 * sz];
-        const double p_u0 = (BZ_KO & 2048) ? p_top : (E.mode == 2) ? E.u0[n + sz] : 0.0;
+        const double p_h2 = h2ok ? h2src[h2n + lev1] : 0.0;
+        const double p_rv = rv[n + sz], p_rw = rw[n + 2 * sz];
+        const double p_u0 = (E.mode == 2) ? E.u0[n + sz] : 0.0;
         if (((k - kbeg) & (BZ5_EB - 1)) == 0) {
             const int kk = min(k + (tx & (BZ5_EB - 1)), kend - 1);
             edge = ST ? flux_x_at<T3_U>(g, F, ie, jc, kk) : flux_x_lean<T3_U>(g, F, ru, ie, jc, kk);
@@ -712,7 +656,7 @@ __global__ __launch_bounds__(64 * TY, BZ_LEAN_WAVES) void k6_u(DevGrid g, Lean5 
         const double ay = bz_symm4(Ay * rvr[-2], Ay * rvr[-1], Ay * rvr[0], Ay * rvr[1]);
         const double fy = ay * bz_up5y<WY>(Uk[ty][tc], Uk[ty + 1][tc], Uk[ty + 2][tc], c0, Uk[ty + 4][tc], Uk[ty + 5][tc], ay > 0.0, by5_face<WY>(g, __builtin_amdgcn_readfirstlane(j)));
         FY[buf][ty][tx] = fy;
-        if (ty == (BZ6_ROTATE_DUTY ? ((k - kbeg) & (TY - 1)) : 0) && !(BZ_KO & 4096)) {
+        if (ty == 0) {
             const double *rvt = RV[buf][TY] + tc;
             const double at = bz_symm4(Ay * rvt[-2], Ay * rvt[-1], Ay * rvt[0], Ay * rvt[1]);
             FY[buf][TY][tx] = at * bz_up5y<WY>(Uk[TY][tc], Uk[TY + 1][tc], Uk[TY + 2][tc], Uk[TY + 3][tc], Uk[TY + 4][tc], Uk[TY + 5][tc], at > 0.0,
@@ -733,7 +677,7 @@ __global__ __launch_bounds__(64 * TY, BZ_LEAN_WAVES) void k6_u(DevGrid g, Lean5 
             if (h1raw) RU[buf ^ 1][h1r - 3][h1c] = ST ? p_h1raw : p_h1;
         }
         if (h2ok) { if (h2sel) RW[buf ^ 1][h2r][h2c] = p_h2; else RV[buf ^ 1][h2r][h2c] = p_h2; }
-        if (!(BZ_KO & 16384) && (!(BZ_KO & 8192) || ((k - kbeg) & 1))) bz6_barrier();
+        __syncthreads();
         {
             if constexpr (MF) {
                 nb = __shfl_up(fx, 1);
@@ -741,7 +685,7 @@ __global__ __launch_bounds__(64 * TY, BZ_LEAN_WAVES) void k6_u(DevGrid g, Lean5 
                 if (tx == le) nb = e;
             }
             const double dx = fx - nb;
-            const double dy = (BZ_KO & 16384) ? 0.5 * fy : FY[buf][ty + 1][tx] - fy;
+            const double dy = FY[buf][ty + 1][tx] - fy;
             double Gu = -(g.Vinv_c[k] * (dx + dy + (fz_hi - fz_lo)));
             if constexpr (MF) {      // -x_f_cross_U + rho F_u: rho_v at (i-1, j), (i-1, j+1), (i, j), (i, j+1) from the raw rho_v tile
                 if (L.mforce & 1) {
@@ -910,7 +854,7 @@ __global__ __launch_bounds__(64 * TY, ((MF && WY) ? 4 : BZ_LEAN_WAVES)) void k6_
         const double vt = (!WY || Bc == 3) ? bz_symm4(MV[ty + 1][tx], MV[ty + 2][tx], MV[ty + 3][tx], MV[ty + 4][tx]) : bz_symm2(MV[ty + 2][tx], MV[ty + 3][tx]);
         const double fy = vt * bz_up5y<WY>(V[ty + 1][tc], V[ty + 2][tc], c0, V[ty + 4][tc], V[ty + 5][tc], V[ty + 6][tc], vt > 0.0, Bc);
         FY[buf][ty + 1][tx] = fy;
-        if (ty == 0 && !(BZ_KO & 4096)) {       // centre j0-1: rho_v rows j0-2..j0+1, v rows j0-3..j0+2
+        if (ty == 0) {       // centre j0-1: rho_v rows j0-2..j0+1, v rows j0-3..j0+2
             const double vb = (!WY || Bc0 == 3) ? bz_symm4(MV[0][tx], MV[1][tx], MV[2][tx], MV[3][tx]) : bz_symm2(MV[1][tx], MV[2][tx]);
             FY[buf][0][tx] = vb * bz_up5y<WY>(V[0][tc], V[1][tc], V[2][tc], V[3][tc], V[4][tc], V[5][tc], vb > 0.0, Bc0);
         }
@@ -935,7 +879,7 @@ __global__ __launch_bounds__(64 * TY, ((MF && WY) ? 4 : BZ_LEAN_WAVES)) void k6_
 #pragma unroll
         for (int q = 0; q < HPT; ++q)
             if (hok[q]) frame_store(buf ^ 1, q, hnext[q], k + 1);
-        bz6_barrier();
+        __syncthreads();
         {
             if constexpr (MF) {
                 nb = __shfl_down(fx, 1);
@@ -1132,7 +1076,7 @@ __global__ __launch_bounds__(64 * TY, BZ6_W_WAVES) void k6_w(DevGrid g, Lean5 L,
         const double vt = (Bf == 3) ? bz_symm4(qv[0], qv[1], qv[2], qv[3]) : bz_symm2(qv[1], qv[2]);
         const double fy = vt * bz_up5y<WY>(Tk[ty][tc], Tk[ty + 1][tc], Tk[ty + 2][tc], w0, Tk[ty + 4][tc], Tk[ty + 5][tc], vt > 0.0, by5_face<WY>(g, __builtin_amdgcn_readfirstlane(j)));
         FY[buf][ty][tx] = fy;
-        if (top && !(BZ_KO & 4096)) {
+        if (top) {
             const double v2 = (Bf == 3) ? bz_symm4(qt[0], qt[1], qt[2], qt[3]) : bz_symm2(qt[1], qt[2]);
             FY[buf][TY][tx] = v2 * bz_up5y<WY>(Tk[TY][tc], Tk[TY + 1][tc], Tk[TY + 2][tc], Tk[TY + 3][tc], Tk[TY + 4][tc], Tk[TY + 5][tc], v2 > 0.0,
                                                by5_face<WY>(g, j0 + TY));
@@ -1151,7 +1095,7 @@ __global__ __launch_bounds__(64 * TY, BZ6_W_WAVES) void k6_w(DevGrid g, Lean5 L,
         else if constexpr (BM == 2) { b_hi = Tcur - g.p_r[k]; r_hi = rqcur - g.rho[k]; }
         T[buf ^ 1][ty + 3][tc] = wr[4];
         if (hok) T[buf ^ 1][hr][hc] = ST ? p_h : bz_cdiv(p_h, LV.rho_f(k + 1), LV.rrho_f(k + 1));
-        bz6_barrier();
+        __syncthreads();
         {
             const double dy = FY[buf][ty + 1][tx] - fy;
             const double adv = -((ST ? g.Vinv_f[k] : LV.Vinv_f(k)) * (dx + dy + (fz_hi - fz_lo)));

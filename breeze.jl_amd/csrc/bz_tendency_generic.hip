@@ -62,16 +62,6 @@
 BZ_WENO_GENERIC(4)
 BZ_WENO_GENERIC(5)
 
-// timing experiments only (results are then WRONG): BZ_KOG bit 0: every z-stencil load reads the target level (what a register ring would
-// leave of the loads), bit 1: the same for y stencils, bit 2: the order-7 / 9 reconstruction arithmetic is stubbed
-#ifndef BZ_GENERIC_CLUSTER
-#define BZ_GENERIC_CLUSTER 1
-#endif
-#ifndef BZ_KOG
-#define BZ_KOG 0
-#endif
-#define BZ_KOG_OFF(off, s) ((((BZ_KOG & 1) && (s) > 8192) || ((BZ_KOG & 2) && (s) > 1 && (s) <= 8192)) ? 0 : (off))
-
 // largest buffer B <= R usable at index idx of the Bounded z direction (face target: B <= idx <= N-B; centre: B-1 <= idx <= N-B)
 template <int R>
 __device__ __forceinline__ int buf_face(int idx, int N)
@@ -108,7 +98,7 @@ template <int B>
 __device__ __forceinline__ void load_wide_g(double (&q)[2 * B], const double *__restrict__ p, long long s, int first)
 {
 #pragma unroll
-    for (int j = 0; j < 2 * B; ++j) q[j] = p[BZ_KOG_OFF(j + first, s) * s];
+    for (int j = 0; j < 2 * B; ++j) q[j] = p[(j + first) * s];
 }
 template <int B>
 __device__ __forceinline__ double weno_wide_g(const double (&q)[2 * B], bool left)
@@ -117,7 +107,6 @@ __device__ __forceinline__ double weno_wide_g(const double (&q)[2 * B], bool lef
     double v[2 * B - 1];
 #pragma unroll
     for (int j = 0; j < 2 * B - 1; ++j) v[j] = bz_sel(m, q[j], q[2 * B - 1 - j]);
-    if (BZ_KOG & 4) return q[B - 1] + 0.25 * (q[B] - q[B - 2]);      // reconstruction arithmetic stubbed
     if constexpr (B == 5) return bz_weno_r5(v);
     else return bz_weno_r4(v);
 }
@@ -155,7 +144,7 @@ __device__ __forceinline__ double symm_h(const double *__restrict__ M, long long
 {
     double q[2 * H];
 #pragma unroll
-    for (int m = 0; m < 2 * H; ++m) q[m] = (A.p ? A[k + first + m] : a0) * M[n + (long long)BZ_KOG_OFF(first + m, s) * s];
+    for (int m = 0; m < 2 * H; ++m) q[m] = (A.p ? A[k + first + m] : a0) * M[n + (long long)(first + m) * s];
     if constexpr (H == 1) return bz_symm2(q[0], q[1]);
     else if constexpr (H == 2) return bz_symm4(q[0], q[1], q[2], q[3]);
     else {
@@ -175,10 +164,10 @@ __device__ __forceinline__ double symm_g(const double *__restrict__ M, long long
 }
 
 // ---- two-pass evaluation ---------------------------------------------------------------------------------------------------------
-// A face flux belongs to two cells.  PASS 0 lets both of them evaluate it (one launch, 6 reconstructions per cell and field); the
-// shipped path is PASS 1 + PASS 2: every thread evaluates the three fluxes of its own index once and stores them in parent-shaped
-// scratch arrays (ctx->d_gflux), a second launch differences them.  Order-9 reconstructions cost ~700 instructions each, the scratch
-// traffic (3 words written, 6 read per cell) is noise beside that.  Bit-identical to PASS 0: the same expressions, evaluated once.
+// A face flux belongs to two cells.  PASS 1: every thread evaluates the three fluxes of its own index once and stores them in parent-shaped
+// scratch arrays (ctx->d_gflux); PASS 2, a second launch, differences them.  Order-9 reconstructions cost ~700 instructions each, the scratch
+// traffic (3 words written, 6 read per cell) is noise beside that (a one-launch form in which both cells evaluate the flux did twice the
+// reconstructions for the same bits).
 struct FluxBuf {
     double *x, *y, *z;
     // optional SSP-RK3 epilogue of the divergence pass (fused-RK tier of the whole-step seam): instead of the tendency G the kernel
@@ -203,13 +192,7 @@ __device__ __forceinline__ double rk_out(const FluxBuf &F, double G, long long n
 // 512 cells — gave every XCD a tile COLUMN, its x neighbours behind another L2.  Here XCD c owns the band [c gy/8, (c+1) gy/8) of the grid's
 // y extent and walks it x fastest, then y, then z (bz_fused.hip: bz_stream_block; bz_acoustic_kernels.h: k_ac_column_forward).  Grids whose y
 // extent is not a multiple of 8 keep launch order.  The indices are wave-uniform (column tables stay scalar loads).
-#ifndef GEN_XCD
-#define GEN_XCD 1
-#endif
-#ifndef GEN_XCD_MARCH
-#define GEN_XCD_MARCH 0      // the marching kernels measured equal (momentum) or 1 % slower (theta) in band order: they keep launch order
-#endif
-__device__ __forceinline__ void generic_block(int &bx, int &by, int &bz, bool bands = GEN_XCD != 0)
+__device__ __forceinline__ void generic_block(int &bx, int &by, int &bz, bool bands = true)
 {
     bx = blockIdx.x; by = blockIdx.y; bz = blockIdx.z;
     const unsigned gx = gridDim.x, gy = gridDim.y;
@@ -263,7 +246,6 @@ __global__ __launch_bounds__(256) void k_scalar_tendency_g(DevGrid g, double *__
     };
     if (PASS == 1) {
         const bool cj = IN(j, 0, g.Ny - 1);
-#if BZ_GENERIC_CLUSTER
         // interior rows and levels of a grid without walls in x / y (the block is one row of one level: wave-uniform): the thirty stencil
         // values and the three velocities are requested before the first reconstruction starts — one memory latency per cell instead of
         // three (the calls below issue their loads behind the row / level conditions, where the compiler cannot hoist them)
@@ -278,15 +260,12 @@ __global__ __launch_bounds__(256) void k_scalar_tendency_g(DevGrid g, double *__
             F.z[n] = g.rho_f[k] * ((g.Az * wt) * weno_wide_g<R>(qz, wt > 0.0));
             return;
         }
-#endif
         if (cj) F.x[n] = fx(n, i);
         if (!g.flat_y && IN(j, 0, g.Ny - (ext_y ? 0 : 1))) F.y[n] = fy(n, j);
         if (cj) F.z[n] = fz(n, k);
         return;
     }
-    double dx, dy, dz;
-    if (PASS == 2) { dx = (W.xwall ? 0.0 : F.x[n + W.xp]) - F.x[n]; dy = g.flat_y ? 0.0 : F.y[n + W.yp] - F.y[n]; dz = (W.top ? 0.0 : F.z[n + sz]) - F.z[n]; }
-    else { dx = fx(n + 1, i + 1) - fx(n, i); dy = g.flat_y ? 0.0 : fy(n + sy, j + 1) - fy(n, j); dz = fz(n + sz, k + 1) - fz(n, k); }      // a Flat y has no faces
+    const double dx = (W.xwall ? 0.0 : F.x[n + W.xp]) - F.x[n], dy = g.flat_y ? 0.0 : F.y[n + W.yp] - F.y[n], dz = (W.top ? 0.0 : F.z[n + sz]) - F.z[n];      // a Flat y has no faces
     Gc[n] = rk_out(F, -(g.Vinv_c[k] * (dx + dy + dz)), n);
 }
 
@@ -324,9 +303,7 @@ __global__ __launch_bounds__(256) void k_u_tendency_g(DevGrid g, double *__restr
         return;
     }
     if (g.bounded_x && i == 0) return;      // the wall face is never updated
-    double a, b, c;
-    if (PASS == 2) { a = F.x[n] - F.x[n + W.xm]; b = g.flat_y ? 0.0 : F.y[n + W.yp] - F.y[n]; c = (W.top ? 0.0 : F.z[n + sz]) - F.z[n]; }
-    else { a = FUu(n, i) - FUu(n - 1, i - 1); b = g.flat_y ? 0.0 : FVu(n + sy, j + 1) - FVu(n, j); c = FWu(n + sz, k + 1) - FWu(n, k); }
+    const double a = F.x[n] - F.x[n + W.xm], b = g.flat_y ? 0.0 : F.y[n + W.yp] - F.y[n], c = (W.top ? 0.0 : F.z[n + sz]) - F.z[n];
     Gu[n] = rk_out(F, -(g.Vinv_c[k] * (a + b + c)), n);
 }
 
@@ -364,9 +341,7 @@ __global__ __launch_bounds__(256) void k_v_tendency_g(DevGrid g, double *__restr
         return;
     }
     if (g.bounded_y && j == 0) return;      // the wall face is never updated
-    double a, b, c;
-    if (PASS == 2) { a = (W.xwall ? 0.0 : F.x[n + W.xp]) - F.x[n]; b = g.flat_y ? 0.0 : F.y[n] - F.y[n + W.ym]; c = (W.top ? 0.0 : F.z[n + sz]) - F.z[n]; }
-    else { a = FUv(n + 1, i + 1) - FUv(n, i); b = g.flat_y ? 0.0 : FVv(n, j) - FVv(n - sy, j - 1); c = FWv(n + sz, k + 1) - FWv(n, k); }
+    const double a = (W.xwall ? 0.0 : F.x[n + W.xp]) - F.x[n], b = g.flat_y ? 0.0 : F.y[n] - F.y[n + W.ym], c = (W.top ? 0.0 : F.z[n + sz]) - F.z[n];
     Gv[n] = rk_out(F, -(g.Vinv_c[k] * (a + b + c)), n);
 }
 
@@ -408,9 +383,7 @@ __global__ __launch_bounds__(256) void k_w_tendency_g(DevGrid g, double *__restr
         if (cj) F.z[n] = FWw(n, k);
         return;
     }
-    double a, b, c;
-    if (PASS == 2) { a = (W.xwall ? 0.0 : F.x[n + W.xp]) - F.x[n]; b = g.flat_y ? 0.0 : F.y[n + W.yp] - F.y[n]; c = F.z[n] - F.z[n - sz]; }
-    else { a = FUw(n + 1, i + 1) - FUw(n, i); b = g.flat_y ? 0.0 : FVw(n + sy, j + 1) - FVw(n, j); c = FWw(n, k) - FWw(n - sz, k - 1); }
+    const double a = (W.xwall ? 0.0 : F.x[n + W.xp]) - F.x[n], b = g.flat_y ? 0.0 : F.y[n + W.yp] - F.y[n], c = F.z[n] - F.z[n - sz];
     const double adv = -(g.Vinv_f[k] * (a + b + c));
     if (BUOY) Gw[n] = rk_out(F, adv + 0.5 * (bz_buoyancy(g, T, qv, n - sz, k - 1) + bz_buoyancy(g, T, qv, n, k)), n);
     else Gw[n] = adv;
@@ -443,9 +416,7 @@ __global__ __launch_bounds__(256) void k_scalar_tendency_rho3d_g(DevGrid g, doub
         if (cj) F.z[n] = fz(n, k);
         return;
     }
-    double dx, dy, dz;
-    if (PASS == 2) { dx = (W.xwall ? 0.0 : F.x[n + W.xp]) - F.x[n]; dy = g.flat_y ? 0.0 : F.y[n + W.yp] - F.y[n]; dz = (W.top ? 0.0 : F.z[n + sz]) - F.z[n]; }
-    else { dx = fx(n + 1) - fx(n); dy = g.flat_y ? 0.0 : fy(n + sy) - fy(n); dz = fz(n + sz, k + 1) - fz(n, k); }
+    const double dx = (W.xwall ? 0.0 : F.x[n + W.xp]) - F.x[n], dy = g.flat_y ? 0.0 : F.y[n + W.yp] - F.y[n], dz = (W.top ? 0.0 : F.z[n + sz]) - F.z[n];
     Gc[n] = -(g.Vinv_c[k] * (dx + dy + dz));
     if (Grho) {
         const double Ax = g.Ax[k], Ay = g.Ay[k];
@@ -459,7 +430,7 @@ __global__ __launch_bounds__(256) void k_scalar_tendency_rho3d_g(DevGrid g, doub
 
 // ---- single pass, marching in z (round 4) ----------------------------------------------------------------------------------------
 // The two-pass path above writes three flux arrays per field and reads six values back in a second launch: measured on the reference's
-// benchmark case (CBL 512 x 512 x 256, Float32, order 9; tools/gpu_ko_generic.sh) the flux pass with its reconstruction arithmetic AND
+// benchmark case (CBL 512 x 512 x 256, Float32, order 9; knock-out builds) the flux pass with its reconstruction arithmetic AND
 // its stencil loads removed still takes 60 % of its time, and the divergence pass another 0.24 - 0.44 ms per field: the skeleton, not
 // the arithmetic, is the larger half.  Here a workgroup of 64 x MTY threads owns 64 x MTY columns and walks 64 levels: every thread
 // evaluates the three fluxes of its own index ONCE per level with the functions above (same expressions => same bits as the two-pass
@@ -472,14 +443,11 @@ __global__ __launch_bounds__(256) void k_scalar_tendency_rho3d_g(DevGrid g, doub
 //   z: the flux of the lower face / centre rides a register from the previous level.
 // No flux arrays, one launch per field, the SSP-RK3 epilogue as in PASS 2.  Periodic x, wrapped y (single GPU) with Nx a multiple of
 // 64 and Ny of MTY; everything else (walls, Flat, y-slabs) keeps the two-pass path.  BZ_NO_GENERIC_MARCH=1 restores it everywhere.
+// The z-momentum keeps the two passes: its marching form measured slower (2.16 against 1.82 ms per stage on the CBL case — its three fluxes
+// each carry the z-cascade of the Centered interpolation).
 #define MTY 4
-#ifndef MARCH_W
-#define MARCH_W 0
-#endif
-#ifndef MARCH_WAVES
 #define MARCH_WAVES 4
-#endif
-template <int R, int KIND>      // KIND 0: scalar c advected by (u, v, w) [passed in the ru, rv, rw slots]; 1, 2, 3: u, v, w momentum
+template <int R, int KIND>      // KIND 0: scalar c advected by (u, v, w) [passed in the ru, rv, rw slots]; 1, 2: u, v momentum
 struct MarchFlux {
     const DevGrid &g;
     const double *__restrict__ ru, *__restrict__ rv, *__restrict__ rw, *__restrict__ a;
@@ -487,27 +455,23 @@ struct MarchFlux {
     const ColPtr none;
     __device__ __forceinline__ MarchFlux(const DevGrid &g_, const double *ru_, const double *rv_, const double *rw_, const double *a_)
         : g(g_), ru(ru_), rv(rv_), rw(rw_), a(a_), sy(g_.Sx), sz(g_.Sxy), none(nullptr) {}
-    // flux through the x-face (KIND 0, 2, 3) / at the x-centre (KIND 1) of index m, level k
+    // flux through the x-face (KIND 0, 2) / at the x-centre (KIND 1) of index m, level k
     __device__ __forceinline__ double X(long long m, int k) const
     {
         if (KIND == 0) { const double ut = ru[m]; return g.rho[k] * ((g.Ax[k] * ut) * biased_face_g(a + m, 1, ut > 0.0, R)); }
         if (KIND == 1) { const double ut = symm_g(ru, m, 1, R, -(R - 2), none, 0, g.Ax[k]); return ut * biased_center_g(a + m, 1, ut > 0.0, R); }
-        if (KIND == 2) { const double ut = symm_g(ru, m, sy, R, -(R - 1), none, 0, g.Ax[k]); return ut * biased_face_g(a + m, 1, ut > 0.0, R); }
-        const int Bf = buf_face<R>(k, g.Nz), h = Bf > 2 ? Bf - 1 : 1;
-        const double ut = symm_g(ru, m, sz, Bf, -h, g.Ax, k, 0.0);
+        const double ut = symm_g(ru, m, sy, R, -(R - 1), none, 0, g.Ax[k]);
         return ut * biased_face_g(a + m, 1, ut > 0.0, R);
     }
-    // y-face (KIND 0, 1, 3) / y-centre (KIND 2)
+    // y-face (KIND 0, 1) / y-centre (KIND 2)
     __device__ __forceinline__ double Y(long long m, int k) const
     {
         if (KIND == 0) { const double vt = rv[m]; return g.rho[k] * ((g.Ay[k] * vt) * biased_face_g(a + m, sy, vt > 0.0, R)); }
         if (KIND == 1) { const double vt = symm_g(rv, m, 1, R, -(R - 1), none, 0, g.Ay[k]); return vt * biased_face_g(a + m, sy, vt > 0.0, R); }
-        if (KIND == 2) { const double vt = symm_g(rv, m, sy, R, -(R - 2), none, 0, g.Ay[k]); return vt * biased_center_g(a + m, sy, vt > 0.0, R); }
-        const int Bf = buf_face<R>(k, g.Nz), h = Bf > 2 ? Bf - 1 : 1;
-        const double vt = symm_g(rv, m, sz, Bf, -h, g.Ay, k, 0.0);
-        return vt * biased_face_g(a + m, sy, vt > 0.0, R);
+        const double vt = symm_g(rv, m, sy, R, -(R - 2), none, 0, g.Ay[k]);
+        return vt * biased_center_g(a + m, sy, vt > 0.0, R);
     }
-    // z-face kf, in two halves (KIND 0, 1, 2): the advecting factor at the face (m = index of the cell above it) and the flux from it and
+    // z-face kf, in two halves: the advecting factor at the face (m = index of the cell above it) and the flux from it and
     // the reconstructed value — Z(m, kf) == Zfin(Zmass(m), biased_face_g(a + m, sz, Zmass(m) > 0, buf_face(kf)), kf), which the marching
     // kernel evaluates with the z stencil in a register ring
     __device__ __forceinline__ double Zmass(long long m) const
@@ -521,15 +485,13 @@ struct MarchFlux {
         if (KIND == 0) return g.rho_f[kf] * ((g.Az * wt) * rec);
         return wt * rec;
     }
-    // z-face kf (KIND 0, 1, 2) / z-centre kf (KIND 3)
+    // z-face kf
     __device__ __forceinline__ double Z(long long m, int kf) const
     {
         if (KIND == 0) { const double wt = rw[m]; return g.rho_f[kf] * ((g.Az * wt) * biased_face_g(a + m, sz, wt > 0.0, buf_face<R>(kf, g.Nz))); }
         if (KIND == 1) { const double wt = symm_g(rw, m, 1, R, -(R - 1), none, 0, g.Az); return wt * biased_face_g(a + m, sz, wt > 0.0, buf_face<R>(kf, g.Nz)); }
-        if (KIND == 2) { const double wt = symm_g(rw, m, sy, R, -(R - 1), none, 0, g.Az); return wt * biased_face_g(a + m, sz, wt > 0.0, buf_face<R>(kf, g.Nz)); }
-        const int B = buf_center<R>(kf, g.Nz), h = B > 2 ? B - 1 : 1;
-        const double wt = symm_g(rw, m, sz, B, -(h - 1), none, 0, g.Az);
-        return wt * biased_center_g(a + m, sz, wt > 0.0, B);
+        const double wt = symm_g(rw, m, sy, R, -(R - 1), none, 0, g.Az);
+        return wt * biased_face_g(a + m, sz, wt > 0.0, buf_face<R>(kf, g.Nz));
     }
 };
 
@@ -558,7 +520,9 @@ __device__ __forceinline__ double bz_sub_rounded(double a, double b)
     return a - b;
 }
 
-// grid (Nx / 64, Ny / MTY, ceil(levels / 64)), block (64, MTY).  KIND 3: levels = faces 1 .. Nz-1; BUOY as k_w_tendency_g.
+// grid (Nx / 64, Ny / MTY, ceil(levels / 64)), block (64, MTY).  BUOY, T and qv belonged to the retired z-momentum form (KIND 3) and are
+// not read: they stay in the signature because the kernel's name and argument block are what tools/accounting.py and the recorded
+// profiles match.
 // (The level loop inside a group is NOT unrolled and the per-level partial results live in LDS slots of their own thread: unrolled, the
 // sixteen inlined order-9 reconstructions of a group made 50 - 90 KB of code and 110 VGPRs, and the kernel was slower than two passes.)
 template <int R, int KIND, bool BUOY>
@@ -568,15 +532,15 @@ __global__ __launch_bounds__(64 * MTY, MARCH_WAVES) void k_tendency_m(DevGrid g,
                                                          const double *__restrict__ qv, FluxBuf F, int kchunk)
 {
     if (F.skip_if_dry && __builtin_amdgcn_readfirstlane(*F.skip_if_dry) == 1) return;
-    constexpr bool XC = (KIND == 1), YC = (KIND == 2), ZC = (KIND == 3);
+    static_assert(KIND >= 0 && KIND <= 2, "scalar, x-momentum or y-momentum");
+    constexpr bool XC = (KIND == 1), YC = (KIND == 2);
     __shared__ double FY[2][MTY][MTY + 1][64];
     __shared__ double AX[MTY][MTY][64], AZ[MTY][MTY][64];
     const int tx = threadIdx.x, ty = threadIdx.y;
     int bx, by, bz;
-    generic_block(bx, by, bz, GEN_XCD_MARCH != 0);
+    generic_block(bx, by, bz, false);      // launch order: in band order the march measured equal (momentum) or 1 % slower (theta)
     const int i0 = bx * 64, j0 = by * MTY, i = i0 + tx, j = j0 + ty;
-    const int k0 = ZC ? 1 : 0, k1 = g.Nz;                    // levels [k0, k1)
-    const int kbeg = k0 + bz * kchunk, kend = min(kbeg + kchunk, k1);      // kchunk <= 64: one edge flux per lane
+    const int kbeg = bz * kchunk, kend = min(kbeg + kchunk, g.Nz);      // kchunk <= 64: one edge flux per lane
     if (kbeg >= kend) return;
     const long long sz = g.Sxy;
     const MarchFlux<R, KIND> Fl(g, ru, rv, rw, a);
@@ -592,18 +556,16 @@ __global__ __launch_bounds__(64 * MTY, MARCH_WAVES) void k_tendency_m(DevGrid g,
     const int jx = YC ? j0 - 1 : j0 + MTY;
     const long long nx0 = g.idx(i, jx, kbeg);
     const int yown = ty + (YC ? 1 : 0), yext = YC ? 0 : MTY;
-    // z: flux of the lower face (centre below for KIND 3) of the first level
-    double zlo = ZC ? Fl.Z(n - sz, kbeg - 1) : Fl.Z(n, kbeg);
-    // z stencil of the advected field around the upper face of the current level, in registers (KIND 0, 1, 2): one load per level
+    // z: flux of the lower face of the first level
+    double zlo = Fl.Z(n, kbeg);
+    // z stencil of the advected field around the upper face of the current level, in registers: one load per level
     // instead of 2 R (the stencil loads are what the L1 path of a CU spends its cycles on: 58 four-byte requests per cell and level in
     // the x-momentum kernel, 64 bytes per clock)
     double zr[2 * R];
     const int ktop = g.Nz + g.Hz - 1;                         // last level a parent array holds
     auto lev = [&](int kk) { return (long long)(max(min(kk, ktop), -g.Hz) - kbeg) * sz; };      // offset of level kk from n at chunk start, clamped to the array
-    if (!ZC) {
 #pragma unroll
-        for (int q = 0; q < 2 * R; ++q) zr[q] = a[n + lev(kbeg + 1 - R + q)];
-    }
+    for (int q = 0; q < 2 * R; ++q) zr[q] = a[n + lev(kbeg + 1 - R + q)];
     int buf = 0;
     for (int k = kbeg; k < kend; k += MTY, n += MTY * sz) {
         const int nl = min(MTY, kend - k);
@@ -623,18 +585,15 @@ __global__ __launch_bounds__(64 * MTY, MARCH_WAVES) void k_tendency_m(DevGrid g,
             for (int rep = 0; rep < reps; ++rep)
                 FY[buf][l][rep ? yext : yown][tx] = Fl.Y(rep ? nx0 + (long long)(kl - kbeg) * sz : m, kl);
             double zhi;
-            if (ZC) zhi = Fl.Z(m, kl);
+            if (kl + 1 >= g.Nz) zhi = 0.0;
             else {
-                if (kl + 1 >= g.Nz) zhi = 0.0;
-                else {
-                    const double wt = Fl.Zmass(m + sz);
-                    zhi = Fl.Zfin(wt, ring_face_g<R>(zr, wt > 0.0, buf_face<R>(kl + 1, g.Nz)), kl + 1);
-                }
-                const double znew = a[m + (long long)(min(kl + 1 + R, ktop) - kl) * sz];      // level kl + 1 + R: top of the next face's ring
-#pragma unroll
-                for (int q = 0; q < 2 * R - 1; ++q) zr[q] = zr[q + 1];
-                zr[2 * R - 1] = znew;
+                const double wt = Fl.Zmass(m + sz);
+                zhi = Fl.Zfin(wt, ring_face_g<R>(zr, wt > 0.0, buf_face<R>(kl + 1, g.Nz)), kl + 1);
             }
+            const double znew = a[m + (long long)(min(kl + 1 + R, ktop) - kl) * sz];      // level kl + 1 + R: top of the next face's ring
+#pragma unroll
+            for (int q = 0; q < 2 * R - 1; ++q) zr[q] = zr[q + 1];
+            zr[2 * R - 1] = znew;
             AZ[l][ty][tx] = bz_sub_rounded(zhi, zlo);
             zlo = zhi;
         }
@@ -645,11 +604,7 @@ __global__ __launch_bounds__(64 * MTY, MARCH_WAVES) void k_tendency_m(DevGrid g,
             const long long m = n + l * sz;
             const double fy = FY[buf][l][yown][tx];
             const double dy = YC ? bz_sub_rounded(fy, FY[buf][l][ty][tx]) : bz_sub_rounded(FY[buf][l][ty + 1][tx], fy);
-            const double adv = -((ZC ? g.Vinv_f[kl] : g.Vinv_c[kl]) * (AX[l][ty][tx] + dy + AZ[l][ty][tx]));
-            if (ZC) {
-                if (BUOY) G[m] = rk_out(F, adv + 0.5 * (bz_buoyancy(g, T, qv, m - sz, kl - 1) + bz_buoyancy(g, T, qv, m, kl)), m);
-                else G[m] = adv;
-            } else G[m] = rk_out(F, adv, m);
+            G[m] = rk_out(F, -(g.Vinv_c[kl] * (AX[l][ty][tx] + dy + AZ[l][ty][tx])), m);
         }
         buf ^= 1;
     }
@@ -667,24 +622,20 @@ static int generic_flux_buffers(bz_ctx *ctx, FluxBuf &F)
     return BZ_OK;
 }
 
-// launch `kernel<R, PASS>`(args..., F): one pass with BZ_GENERIC_ONEPASS=1, else flux pass over the extended box + divergence pass
+// launch `kernel<R, PASS>`(args..., F): flux pass over the extended box + divergence pass
 #define GENERIC_LAUNCH(KERNEL, TARGS, k0, nk, ...)                                                                                  \
     do {                                                                                                                            \
         const dim3 block(256);                                                                                                      \
-        if (onepass) {                                                                                                              \
-            hipLaunchKernelGGL((KERNEL<R, 0 TARGS>), dim3((g.Nx + 255) / 256, g.Ny, (nk)), block, 0, ctx->stream, g, __VA_ARGS__, F);  \
-        } else {                                                                                                                    \
-            hipLaunchKernelGGL((KERNEL<R, 1 TARGS>), dim3((g.Nx + 255) / 256, g.Ny + ((!g.wrap_y && !g.flat_y) ? 2 : 0), g.Nz), block, 0, \
-                               ctx->stream, g, __VA_ARGS__, F);                                                                     \
-            hipLaunchKernelGGL((KERNEL<R, 2 TARGS>), dim3((g.Nx + 255) / 256, g.Ny, (nk)), block, 0, ctx->stream, g, __VA_ARGS__, F);  \
-        }                                                                                                                           \
+        hipLaunchKernelGGL((KERNEL<R, 1 TARGS>), dim3((g.Nx + 255) / 256, g.Ny + ((!g.wrap_y && !g.flat_y) ? 2 : 0), g.Nz), block, 0, \
+                           ctx->stream, g, __VA_ARGS__, F);                                                                         \
+        hipLaunchKernelGGL((KERNEL<R, 2 TARGS>), dim3((g.Nx + 255) / 256, g.Ny, (nk)), block, 0, ctx->stream, g, __VA_ARGS__, F);   \
     } while (0)
 #define COMMA_FALSE , false
 // the single-pass marching kernel where the grid allows it (see k_tendency_m), else the two passes
 static bool generic_march_ok(const bz_ctx *ctx)
 {
     const DevGrid &g = ctx->dg;
-    return !ctx->tune.generic_onepass && !ctx->tune.no_generic_march && g.wrap_y && !g.flat_y && !g.bounded_x && !g.bounded_y &&
+    return !ctx->tune.no_generic_march && g.wrap_y && !g.flat_y && !g.bounded_x && !g.bounded_y &&
            g.Nx % 64 == 0 && g.Ny % MTY == 0 && g.Nz > 1;
 }
 // levels per workgroup of the march: 64 where that leaves >= 8 wavefronts per SIMD, else shorter chunks (every chunk pays one edge flux
@@ -708,11 +659,11 @@ static int launch_generic(bz_ctx *ctx, const bz_state *s, const bz_prognostic *G
                           const bz_prognostic *U0 = nullptr)
 {
     const DevGrid &g = ctx->dg;
-    const bool onepass = ctx->tune.generic_onepass, march = generic_march_ok(ctx);
+    const bool march = generic_march_ok(ctx);
     const int mkc = march_chunk(g);
     FluxBuf F{};
     int rc;
-    if (!onepass && !(march && MARCH_W) && (rc = generic_flux_buffers(ctx, F))) return rc;
+    if ((rc = generic_flux_buffers(ctx, F))) return rc;      // the z-momentum takes the two passes in either case
     const double *nul = nullptr;
     auto epi = [&](double *u0, const double *uold) {
         if (!E) return;
@@ -733,11 +684,7 @@ static int launch_generic(bz_ctx *ctx, const bz_state *s, const bz_prognostic *G
     if (g.Nz > 1) {
         ProfileScope ps(ctx, E ? "z_momentum_tendency+rk3" : "z_momentum_tendency");
         epi(U0 ? U0->rho_w : nullptr, s->rho_w);
-        // (the marching kernel of the z-momentum measured slower than the two passes: 2.16 against 1.82 ms per stage on the CBL case — its
-        // three fluxes each carry the z-cascade of the Centered interpolation; MARCH_W=1 builds select it)
-        if (MARCH_W && march && buoyancy) MARCH_LAUNCH(3, true, g.Nz - 1, G->rho_w, s->rho_u, s->rho_v, s->rho_w, s->w, (const double *)s->T, (const double *)s->q);
-        else if (MARCH_W && march) MARCH_LAUNCH(3, false, g.Nz - 1, G->rho_w, s->rho_u, s->rho_v, s->rho_w, s->w, nul, nul);
-        else if (buoyancy) GENERIC_LAUNCH(k_w_tendency_g, , 1, g.Nz - 1, G->rho_w, s->rho_u, s->rho_v, s->rho_w, s->w, s->T, s->q);
+        if (buoyancy) GENERIC_LAUNCH(k_w_tendency_g, , 1, g.Nz - 1, G->rho_w, s->rho_u, s->rho_v, s->rho_w, s->w, s->T, s->q);
         else GENERIC_LAUNCH(k_w_tendency_g, COMMA_FALSE, 1, g.Nz - 1, G->rho_w, s->rho_u, s->rho_v, s->rho_w, s->w, (const double *)nullptr,
                             (const double *)nullptr);
     }
@@ -786,10 +733,9 @@ static int launch_rho3d(bz_ctx *ctx, double *Gc, double *Grho, const double *rho
                         const double *c, const double *ru, const double *rv, const double *rw)
 {
     const DevGrid &g = ctx->dg;
-    const bool onepass = ctx->tune.generic_onepass;
     FluxBuf F{};
     int rc;
-    if (!onepass && (rc = generic_flux_buffers(ctx, F))) return rc;
+    if ((rc = generic_flux_buffers(ctx, F))) return rc;
     GENERIC_LAUNCH(k_scalar_tendency_rho3d_g, , 0, g.Nz, Gc, Grho, rho, u, v, w, c, ru, rv, rw);
     BZ_LAUNCH_CHECK();
     return BZ_OK;
@@ -808,7 +754,7 @@ template <int R>
 static int launch_scalar(bz_ctx *ctx, double *Gc, const double *u, const double *v, const double *w, const double *c)
 {
     const DevGrid &g = ctx->dg;
-    const bool onepass = ctx->tune.generic_onepass, march = generic_march_ok(ctx);
+    const bool march = generic_march_ok(ctx);
     const int mkc = march_chunk(g);
     FluxBuf F{};
     int rc;
@@ -818,7 +764,7 @@ static int launch_scalar(bz_ctx *ctx, double *Gc, const double *u, const double 
         BZ_LAUNCH_CHECK();
         return BZ_OK;
     }
-    if (!onepass && (rc = generic_flux_buffers(ctx, F))) return rc;
+    if ((rc = generic_flux_buffers(ctx, F))) return rc;
     GENERIC_LAUNCH(k_scalar_tendency_g, , 0, g.Nz, Gc, u, v, w, c);
     BZ_LAUNCH_CHECK();
     return BZ_OK;

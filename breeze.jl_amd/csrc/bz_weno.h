@@ -158,9 +158,7 @@ __device__ __forceinline__ double bz_weno5(double a, double b, double c, double 
 #if BZ_WENO_FT2
     return bz_weno5_ft2(a, b, c, d, e);
 #endif
-#ifdef BZ_WENO_STUB      // timing experiments only: keeps every input live, no WENO arithmetic
-    return 0.2 * (a + b + c + d + e);
-#elif BZ_WENO_ONE_DIVISION == 2
+#if BZ_WENO_ONE_DIVISION == 2
     return bz_weno5_diff(a, b, c, d, e);
 #elif BZ_WENO_ONE_DIVISION
     return bz_weno5_fast(a, b, c, d, e);
@@ -236,9 +234,7 @@ __device__ __forceinline__ R bz_sel(unsigned long long m, R a, R b)
 __device__ __forceinline__ unsigned long long bz_lanes(bool p) { return __builtin_amdgcn_ballot_w64(p); }
 // Wave-uniform upwind shortcut (bz_up5): on in the Float64 build.  Measured at 512^3: Float64 41.35 -> 40.95 ms/step; in the Float32
 // build the three inlined copies of the reconstruction push the 80-VGPR kernels into spills (25.7 -> 29.3 ms/step), so it stays off.
-#ifndef BZ_UPWIND_UNIFORM
-#define BZ_UPWIND_UNIFORM (sizeof(double) == 8)
-#endif
+constexpr bool BZ_UPWIND_UNIFORM = sizeof(double) == 8;
 
 #ifdef BZ_CENTERED2
 // libbreeze_hip_centered2.so: advection = Centered(order = 2), the AtmosphereModel constructor's default

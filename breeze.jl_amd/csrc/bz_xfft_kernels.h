@@ -24,9 +24,6 @@
 
 typedef double xf_pair2 __attribute__((ext_vector_type(2), aligned(sizeof(double))));      // two consecutive reals, element-aligned
 #define XF_RB 8        // rows of y per workgroup: a transposed store / load moves XF_RB consecutive complex numbers (128 B) per kx
-#ifndef XF_XCD
-#define XF_XCD 1
-#endif
 
 // Block order of the two x transforms.  blockIdx.x counts groups of XF_RB rows, and consecutive workgroup ids go round-robin to the 8 XCDs: in
 // launch order the groups j0 and j0 + XF_RB — which in Float32 share every 128-byte line of the transposed spectrum (XF_RB complex numbers of
@@ -37,7 +34,7 @@ __device__ __forceinline__ void xf_block(int &bj, int &bk)
 {
     bj = blockIdx.x; bk = blockIdx.y;
     const unsigned gx = gridDim.x;
-    if (XF_XCD && (gx & 7u) == 0) {
+    if ((gx & 7u) == 0) {
         const unsigned w = blockIdx.y * gx + blockIdx.x, c = w & 7u, r = w >> 3, band = gx >> 3;
         bj = (int)(c * band + r % band);
         bk = (int)(r / band);
