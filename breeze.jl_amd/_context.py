@@ -176,6 +176,37 @@ def check_microphysics(microphysics, message, instantaneous_precipitation_refuse
     return isinstance(microphysics, DCMIP2016KesslerMicrophysics)
 
 
+def is_mixed_phase(microphysics):
+    from .microphysics import MixedPhaseEquilibrium
+    return isinstance(getattr(microphysics, "equilibrium", None), MixedPhaseEquilibrium)
+
+
+def refuse_mixed_phase(microphysics, where, why):
+    """SaturationAdjustment(equilibrium = MixedPhaseEquilibrium()) runs on the single-device anelastic AtmosphereModel (potential-temperature
+    formulation, Clausius-Clapeyron constants); every other place says so here, where the microphysics type is checked."""
+    if is_mixed_phase(microphysics):
+        raise NotImplementedError(f"{where}: SaturationAdjustment(equilibrium = MixedPhaseEquilibrium()) is not implemented ({why}); "
+                                  "pass equilibrium = WarmPhaseEquilibrium()")
+
+
+def check_mixed_phase_model(microphysics, thermodynamic_constants, forcing, boundary_conditions):
+    """What a mixed-phase anelastic model does not attach: Tetens constants (its ice coefficients are not mirrored) and the attachments whose
+    kernels form cᵖᵐ from qᵛ and qˡ alone: energy-keyed column forcings, a bottom energy flux, bulk surface fluxes and the surface layer."""
+    if not is_mixed_phase(microphysics):
+        return
+    from .forcings import _bulk_conditions, _key
+    from .microphysics import TetensFormula
+    where = "AtmosphereModel"
+    if isinstance(getattr(thermodynamic_constants, "saturation_vapor_pressure", None), TetensFormula):
+        refuse_mixed_phase(microphysics, where, "TetensFormula constants: the ice coefficients of the Tetens formula are not mirrored")
+    if any(_key(name) == "e" for name in (forcing or {})):
+        refuse_mixed_phase(microphysics, where, "a forcing keyed `e`: the energy-to-θ conversion forms cᵖᵐ without qⁱ")
+    if any(True for _ in _bulk_conditions(boundary_conditions)):
+        refuse_mixed_phase(microphysics, where, "bulk surface fluxes and the surface layer form cᵖᵐ without qⁱ")
+    if any(_key(name) == "ρe" for name in (boundary_conditions or {})):
+        refuse_mixed_phase(microphysics, where, "a bottom flux keyed ρe: the energy-to-θ conversion forms cᵖᵐ without qⁱ")
+
+
 def check_kessler_constants(thermodynamic_constants):
     """validate_microphysics (dcmip2016_kessler.jl:196-207)"""
     from .microphysics import TetensFormula
@@ -211,13 +242,21 @@ def attach_kessler(model, standard_pressure):
 
 
 def attach_saturation_adjustment(model, fld):
-    """materialize_microphysical_fields(::WarmPhaseSaturationAdjustment): (qᵛ, qˡ, qᵉ); qᵉ is the specific moisture slot."""
+    """materialize_microphysical_fields(::WarmPhaseSaturationAdjustment): (qᵛ, qˡ, qᵉ); (::MixedPhaseSaturationAdjustment): (qᵛ, qˡ, qⁱ, qᵉ)
+    (saturation_adjustment.jl:118-119); qᵉ is the specific moisture slot."""
     c, solver = model.thermodynamic_constants, model.microphysics.solver
-    μ = model.microphysical_fields = {"qᵛ": fld("ccc"), "qˡ": fld("ccc"), "qᵉ": model.specific_moisture}
+    mixed = is_mixed_phase(model.microphysics)
+    μ = model.microphysical_fields = {"qᵛ": fld("ccc"), "qˡ": fld("ccc"), **({"qⁱ": fld("ccc")} if mixed else {}), "qᵉ": model.specific_moisture}
     sa = model._T.bz_saturation_adjustment(c.liquid_reference_latent_heat, c.liquid_heat_capacity, c.energy_reference_temperature,
                                            c.triple_point_temperature, c.triple_point_pressure, solver.abstol, solver.maxiter, 0)
     model._check(model._lib.bz_set_saturation_adjustment(model._ctx, C.byref(sa), C.c_void_p(μ["qᵛ"].ptr()), C.c_void_p(μ["qˡ"].ptr())),
                  "bz_set_saturation_adjustment")
+    if mixed:
+        eq = model.microphysics.equilibrium
+        mp = model._T.bz_mixed_phase_equilibrium(eq.freezing_temperature, eq.homogeneous_ice_nucleation_temperature,
+                                                 c.ice_reference_latent_heat, c.ice_heat_capacity)
+        model._check(model._lib.bz_set_mixed_phase_equilibrium(model._ctx, C.byref(mp), C.c_void_p(μ["qⁱ"].ptr())),
+                     "bz_set_mixed_phase_equilibrium")
 
 
 def attach_instantaneous_precipitation(model, fld):

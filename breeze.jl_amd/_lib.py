@@ -58,6 +58,11 @@ class bz_saturation_adjustment(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+class bz_mixed_phase_equilibrium(C.Structure):
+    _fields_ = [(n, C.c_double) for n in ("freezing_temperature", "homogeneous_ice_nucleation_temperature", "ice_latent_heat",
+                                          "ice_heat_capacity")]
+
+
 class bz_bulk_surface_fluxes(C.Structure):
     _fields_ = [(n, C.c_double) for n in (
         "drag_coefficient", "drag_gustiness", "drag_surface_temperature",
@@ -226,6 +231,7 @@ SYMBOLS = {
     "bz_destroy": (None, [_ctx]),
     "bz_set_formulation": (C.c_int, [_ctx, C.c_int]),
     "bz_set_saturation_adjustment": (C.c_int, [_ctx, C.POINTER(bz_saturation_adjustment), C.c_void_p, C.c_void_p]),
+    "bz_set_mixed_phase_equilibrium": (C.c_int, [_ctx, C.POINTER(bz_mixed_phase_equilibrium), C.c_void_p]),
     "bz_set_stream": (C.c_int, [_ctx, C.c_void_p]),
     "bz_graph_enable": (C.c_int, [_ctx, C.c_int]),
     "bz_graph_info": (C.c_int, [_ctx, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),

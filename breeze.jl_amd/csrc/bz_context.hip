@@ -159,13 +159,15 @@ extern "C" int bz_set_saturation_adjustment(bz_ctx *ctx, const bz_saturation_adj
     if (ctx) ++ctx->config_epoch;      // captured steps (bz_graph.hip) belong to one configuration
     if (!ctx) return BZ_ERR_INVALID;
     DevGrid &g = ctx->dg;
-    if (!params) { g.microphysics = 0; g.qv_field = g.ql_field = nullptr; return BZ_OK; }
+    if (!params) { g.microphysics = 0; g.qv_field = g.ql_field = nullptr; bzi_clear_mixed_phase(g); return BZ_OK; }
     if (!q_vapor || !q_liquid || params->maxiter < 0) return BZ_ERR_INVALID;
     if (g.formulation != 0) {
         ctx->last_error = "saturation adjustment is implemented for the potential-temperature formulation";
         return BZ_ERR_UNSUPPORTED;
     }
     g.microphysics = 1;
+    bzi_clear_mixed_phase(g);      // a fresh attachment is warm-phase until bz_set_mixed_phase_equilibrium says otherwise
+    ctx->sa_energy_reference_temperature = params->energy_reference_temperature;
     g.sa_Ll = params->liquid_latent_heat;
     g.sa_cl = params->liquid_heat_capacity;
     g.sa_dc = ctx->constants.vapor_heat_capacity - params->liquid_heat_capacity;
@@ -176,6 +178,36 @@ extern "C" int bz_set_saturation_adjustment(bz_ctx *ctx, const bz_saturation_adj
     g.sa_maxiter = params->maxiter;
     g.qv_field = q_vapor;
     g.ql_field = q_liquid;
+    return BZ_OK;
+}
+
+// equilibrium = MixedPhaseEquilibrium(T^f, T^h) of the attached SaturationAdjustment (src/Thermodynamics/vapor_saturation.jl:146-176,
+// src/Microphysics/saturation_adjustment.jl:92-100,128-149): the anelastic kernels take their mixed instantiation (DevGrid::sa_mixed),
+// which diagnoses q^i into `q_ice` and loads the buoyancy with q^l + q^i.  params == NULL: back to the warm phase.
+extern "C" int bz_set_mixed_phase_equilibrium(bz_ctx *ctx, const bz_mixed_phase_equilibrium *params, double *q_ice)
+{
+    if (ctx) ++ctx->config_epoch;      // captured steps (bz_graph.hip) belong to one configuration
+    if (!ctx) return BZ_ERR_INVALID;
+    DevGrid &g = ctx->dg;
+    if (!params) { bzi_clear_mixed_phase(g); return BZ_OK; }
+    const char *why = ctx->compressible  ? "CompressibleDynamics contexts run the density-based adjustment, whose mixed-phase form is not built"
+                      : (ctx->slab_mode || ctx->comm) ? "y-slab contexts exchange the halos of q^v and q^l only"
+                      : ctx->kinematic   ? "the kinematic driver diagnoses q^v and q^l only"
+                      : g.microphysics != 1 ? "no SaturationAdjustment is attached (call bz_set_saturation_adjustment first)"
+                                         : nullptr;
+    if (why) {
+        ctx->last_error = std::string("bz_set_mixed_phase_equilibrium: ") + why;
+        return BZ_ERR_UNSUPPORTED;
+    }
+    if (!q_ice || !(params->freezing_temperature > params->homogeneous_ice_nucleation_temperature)) return BZ_ERR_INVALID;
+    g.sa_mixed = 1;
+    g.sa_Tf = params->freezing_temperature;
+    g.sa_Th = params->homogeneous_ice_nucleation_temperature;
+    g.sa_Li = params->ice_latent_heat;
+    g.sa_ci = params->ice_heat_capacity;
+    g.sa_dci = ctx->constants.vapor_heat_capacity - params->ice_heat_capacity;
+    g.sa_L0i = params->ice_latent_heat - g.sa_dci * ctx->sa_energy_reference_temperature;
+    g.qi_field = q_ice;
     return BZ_OK;
 }
 
@@ -358,6 +390,7 @@ int bzi_create(bz_ctx **out, const bz_grid *grid, const bz_constants *constants,
     g.formulation = 0;
     g.microphysics = 0; g.sa_maxiter = 0; g.qv_field = nullptr; g.ql_field = nullptr;
     g.sa_Ll = g.sa_cl = g.sa_dc = g.sa_L0 = g.sa_Ttr = g.sa_ptr = g.sa_abstol = 0.0;
+    bzi_clear_mixed_phase(g);
     g.Ax = dcol(C_AX); g.Ay = dcol(C_AY);
     g.Vinv_c = dcol(C_VIC); g.Vinv_f = dcol(C_VIF);
     g.rho = dcol(C_RHO); g.rho_f = dcol(C_RHOF);

@@ -135,7 +135,7 @@ struct PDFields {
     long long lsum_P;
 };
 
-template <int SA>       // 0: no microphysics, 1: warm-phase saturation adjustment, 2: Kessler condensate species
+template <int SA>       // 0: no microphysics, 1: warm-phase saturation adjustment, 2: Kessler condensate species, 3: mixed-phase saturation adjustment
 __global__ __launch_bounds__(256) void k_project_diagnose(DevGrid g, PDFields F, double dt, int gx, int nk)
 {
     int bx, j, k;
@@ -175,6 +175,7 @@ __global__ __launch_bounds__(256) void k_project_diagnose(DevGrid g, PDFields F,
     const double Rm = qd * g.Rd + q * g.Rv;
     const double cpm = qd * g.cpd + q * g.cpv;
     double T, qvv = 0.0, qll = 0.0;
+    [[maybe_unused]] double qii = 0.0;      // SA == 3
     double qcl = 0.0, qr = 0.0;
     if (SA == 2) {
         T = bz_kessler_T(g, th, q, g.qcl_field[n] + g.qr_field[n], g.p_r[k]);   // lagged condensate, as the reference (see k_thermo)
@@ -182,6 +183,7 @@ __global__ __launch_bounds__(256) void k_project_diagnose(DevGrid g, PDFields F,
         qr = g.rqr_field[n] / rc;
         qvv = q;
     } else if (SA == 1) T = bz_sa_diagnose(g, th, q, g.p_r[k], qvv, qll);
+    else if (SA == 3) T = bz_mp_diagnose(g, th, q, g.p_r[k], qvv, qll, qii);
     else T = (g.formulation == 1) ? (th - g.g * g.zc[k]) / cpm : bz_exner_factor(g, k, q, cpm) * th;
 
     if (F.lsum) {      // the stage's horizontal sums ride on the values in registers (a separate pass reads the four arrays again)
@@ -205,10 +207,11 @@ __global__ __launch_bounds__(256) void k_project_diagnose(DevGrid g, PDFields F,
     st_img(F.theta, n, th, ox, oy);
     st_img(F.q, n, q, ox, oy);
     st_img(F.T, n, T, ox, oy);
-    if (SA == 1) {
+    if (SA == 1 || SA == 3) {
         st_img(g.qv_field, n, qvv, ox, oy);
         st_img(g.ql_field, n, qll, ox, oy);
     }
+    if (SA == 3) st_img(g.qi_field, n, qii, ox, oy);
     if (SA == 2) {
         st_img(g.qv_field, n, qvv, ox, oy);
         st_img(g.qcl_field, n, qcl, ox, oy);
@@ -239,10 +242,11 @@ __global__ __launch_bounds__(256) void k_project_diagnose(DevGrid g, PDFields F,
         st_img(F.theta, n + h, th, ox, oy);
         st_img(F.q, n + h, q, ox, oy);
         st_img(F.T, n + h, T, ox, oy);
-        if (SA == 1) {
+        if (SA == 1 || SA == 3) {
             st_img(g.qv_field, n + h, qvv, ox, oy);
             st_img(g.ql_field, n + h, qll, ox, oy);
         }
+        if (SA == 3) st_img(g.qi_field, n + h, qii, ox, oy);
         if (SA == 2) {
             st_img(g.qv_field, n + h, qvv, ox, oy);
             st_img(g.qcl_field, n + h, qcl, ox, oy);
@@ -507,6 +511,8 @@ int bzi_project_diagnose(bz_ctx *ctx, const bz_state *s, double dt, const double
     dim3 grid((unsigned)((long long)gx * g.Ny * nk)), block(256);
     if (g.microphysics == 2)
         hipLaunchKernelGGL((k_project_diagnose<2>), grid, block, 0, ctx->stream, g, F, dt, gx, nk);
+    else if (g.microphysics == 1 && g.sa_mixed)
+        hipLaunchKernelGGL((k_project_diagnose<3>), grid, block, 0, ctx->stream, g, F, dt, gx, nk);
     else if (g.microphysics == 1)
         hipLaunchKernelGGL((k_project_diagnose<1>), grid, block, 0, ctx->stream, g, F, dt, gx, nk);
     else

@@ -62,11 +62,24 @@ struct DevGrid {
     int bounded_y;         // 1: topology (Periodic, Bounded, Bounded): walls in y (wrap_y = 0: y neighbours are halo rows — a no-flux row for
                            // fields that are centres in y, impenetrable wall faces j = 0, Ny for rho v and v; WENO / Centered buffers by row;
                            // cosine transform along y in the pressure solve; per-operator kernels only)
+    // SaturationAdjustment(equilibrium = MixedPhaseEquilibrium(T^f, T^h)) (bz_set_mixed_phase_equilibrium; microphysics stays 1): all zero /
+    // null on warm-phase contexts.  The hosts select the mixed INSTANTIATION of a kernel by sa_mixed; no warm kernel reads these members.
+    int sa_mixed;
+    double sa_Tf, sa_Th, sa_Li, sa_ci, sa_dci, sa_L0i;               // dci = cpv - ci, L0i = Li - dci * T_energy
+    double *qi_field;                                                // model.microphysical_fields.q^i (parent)
 
     __host__ __device__ inline long long idx(int i, int j, int k) const {
         return (long long)(i + Hx) + (long long)Sx * ((long long)(j + Hy)) + Sxy * (long long)(k + Hz);
     }
 };
+
+// back to the warm phase: what bz_set_mixed_phase_equilibrium(NULL), a detached or re-attached adjustment and a Kessler attach leave behind
+inline void bzi_clear_mixed_phase(DevGrid &g)
+{
+    g.sa_mixed = 0;
+    g.sa_Tf = g.sa_Th = g.sa_Li = g.sa_ci = g.sa_dci = g.sa_L0i = 0.0;
+    g.qi_field = nullptr;
+}
 
 // Optional SSP-RK3 epilogue of a tendency kernel (ssp_runge_kutta_3.jl:167-173): instead of storing the tendency G,
 // store  u_new = (1-alpha) u0 + alpha (u_old + dt G).  mode 0: store G;  1: first stage (alpha = 1; also writes
@@ -216,11 +229,14 @@ __device__ __forceinline__ double bz_exner_factor(const DevGrid &g, int k, doubl
 // ---- moist thermodynamics shared by the diagnosis and buoyancy kernels -----------------------------------------------
 // anelastic buoyancy -g rho' with rho' = rho_r (R_m,r T_r / (R_m T) - 1)  (anelastic_buoyancy.jl:36-72); the moisture
 // fractions come from grid_moisture_fractions: (q, 0) without microphysics, (q^v, q^l) fields with saturation adjustment.
+// MIX: the mixed-phase instantiation (grid_moisture_fractions(::MPSA), saturation_adjustment.jl:144-149): the condensate is q^l + q^i.
+template <bool MIX = false>
 __device__ __forceinline__ double bz_buoyancy(const DevGrid &g, const double *__restrict__ T, const double *__restrict__ q,
                                               long long n, int k)
 {
     double qv, ql = 0.0;
-    if (g.microphysics == 1) { qv = g.qv_field[n]; ql = g.ql_field[n]; }
+    if constexpr (MIX) { qv = g.qv_field[n]; ql = g.ql_field[n] + g.qi_field[n]; }
+    else if (g.microphysics == 1) { qv = g.qv_field[n]; ql = g.ql_field[n]; }
     else if (g.microphysics == 2) { qv = q[n]; ql = g.qcl_field[n] + g.qr_field[n]; }
     else qv = q[n];
     const double Rm = (1.0 - (qv + ql)) * g.Rd + qv * g.Rv;
@@ -282,6 +298,72 @@ __device__ __forceinline__ double bz_sa_diagnose(const DevGrid &g, double th, do
     }
     bz_sa_adjust(g, x2, qt, pr, qv, ql);
     return bz_sa_T(g, th, qv, ql, pr);
+}
+// Mixed-phase saturation adjustment (equilibrium = MixedPhaseEquilibrium(T^f, T^h)): the inversion above on the temperature-dependent
+// surface.  equilibrated_surface (vapor_saturation.jl:170-176): lambda(T) = (clamp(T, T^h, T^f) - T^h) / (T^f - T^h), taken at the
+// temperature of EACH saturation evaluation; PlanarMixedPhaseSurface (vapor_saturation.jl:14-35 with clausius_clapeyron.jl:59-68): one
+// Clausius-Clapeyron expression with dc = lambda dc_l + (1 - lambda) dc_i and L0 = lambda L0_l + (1 - lambda) L0_i — one pow and one exp,
+// as in the warm phase; equilibrated_moisture_mass_fractions (saturation_adjustment.jl:92-100); T of the state with ice
+// (dynamic_states.jl:29-58); second guess from both latent heats (saturation_adjustment.jl:214-222).
+__device__ __forceinline__ double bz_mp_lambda(const DevGrid &g, double T)
+{
+    const double Tc = T > g.sa_Tf ? g.sa_Tf : (T < g.sa_Th ? g.sa_Th : T);
+    return (Tc - g.sa_Th) / (g.sa_Tf - g.sa_Th);
+}
+__device__ __forceinline__ double bz_mp_psat(const DevGrid &g, double T, double lam)
+{
+    const double dc = lam * g.sa_dc + (1.0 - lam) * g.sa_dci;
+    const double L0 = lam * g.sa_L0 + (1.0 - lam) * g.sa_L0i;
+    return g.sa_ptr * pow(T / g.sa_Ttr, dc / g.Rv) * exp((1.0 / g.sa_Ttr - 1.0 / T) * L0 / g.Rv);
+}
+__device__ __forceinline__ double bz_mp_cpm(const DevGrid &g, double qv, double ql, double qi)
+{
+    return (1.0 - (qv + ql + qi)) * g.cpd + qv * g.cpv + ql * g.sa_cl + qi * g.sa_ci;
+}
+__device__ __forceinline__ double bz_mp_T(const DevGrid &g, double th, double qv, double ql, double qi, double pr)
+{
+    const double qd = 1.0 - (qv + ql + qi);
+    const double cpm = qd * g.cpd + qv * g.cpv + ql * g.sa_cl + qi * g.sa_ci;
+    return pow(pr / g.pst, (qd * g.Rd + qv * g.Rv) / cpm) * th + (g.sa_Ll * ql + g.sa_Li * qi) / cpm;
+}
+__device__ __forceinline__ void bz_mp_adjust(const DevGrid &g, double T, double qt, double pr, double &qv, double &ql, double &qi)
+{
+    const double lam = bz_mp_lambda(g, T);
+    const double ps = bz_mp_psat(g, T, lam);
+    const double qs = (g.Rd / g.Rv) * (1.0 - qt) * ps / (pr - ps);
+    const double qc = fmax(0.0, qt - qs);
+    qv = qt - qc;
+    ql = lam * qc;
+    qi = (1.0 - lam) * qc;
+}
+__device__ __forceinline__ double bz_mp_residual(const DevGrid &g, double T, double th, double qt, double pr)
+{
+    double qv, ql, qi;
+    bz_mp_adjust(g, T, qt, pr, qv, ql, qi);
+    return T - bz_mp_T(g, th, qv, ql, qi, pr);
+}
+__device__ __forceinline__ double bz_mp_diagnose(const DevGrid &g, double th, double qt, double pr, double &qv, double &ql, double &qi)
+{
+    qv = qt; ql = 0.0; qi = 0.0;
+    const double T1 = bz_sa_T(g, th, qt, 0.0, pr);
+    if (th == 0.0) return T1;
+    const double rho1 = pr / (((1.0 - qt) * g.Rd + qt * g.Rv) * T1);
+    if (qt <= bz_mp_psat(g, T1, bz_mp_lambda(g, T1)) / (rho1 * g.Rv * T1)) return T1;
+    double qv1, ql1, qi1;
+    bz_mp_adjust(g, T1, qt, pr, qv1, ql1, qi1);
+    const double dT = (g.sa_Ll * ql1 + g.sa_Li * qi1) / bz_mp_cpm(g, qv1, ql1, qi1);
+    double x1 = T1, x2 = T1 + fmax(0.01, dT / 2.0);
+    double r1 = bz_mp_residual(g, x1, th, qt, pr), r2 = bz_mp_residual(g, x2, th, qt, pr);
+    for (int it = 0; it < g.sa_maxiter && fabs(r2) > g.sa_abstol; ++it) {
+        double s = (x2 - x1) / (r2 - r1);
+        const bool valid = isfinite(s);
+        s = valid ? s : 0.0;
+        x1 = x2; r1 = r2;
+        x2 -= r2 * s;
+        r2 = valid ? bz_mp_residual(g, x2, th, qt, pr) : 0.0;
+    }
+    bz_mp_adjust(g, x2, qt, pr, qv, ql, qi);
+    return bz_mp_T(g, th, qv, ql, qi, pr);
 }
 // ---- density-based liquid-ice potential temperature state of CompressibleDynamics (LiquidIceDensityState) ----------------------------
 // temperature(::LiquidIceDensityState): Newton on T = (rho R_m T / p_st)^kappa theta + L  (dynamic_states.jl:197-232)
@@ -515,6 +597,7 @@ struct bz_ctx {
     // InstantaneousPrecipitation attached to a compressible context (bz_set_instantaneous_precipitation, bz_instant_precip.hip): dg.microphysics
     // stays 0 (a stage is the vapour-only stage), dg.sa_* hold the wrapped SaturationAdjustment for bz_ds_adjust
     bool has_instant_precip = false;
+    double sa_energy_reference_temperature = 0.0;      // of the attached SaturationAdjustment: bz_set_mixed_phase_equilibrium forms L0_i with it
     double *ip_precipitation_rate = nullptr;      // mu.precipitation_rate (caller-owned centre field)
     // forcing / Coriolis / bottom-flux stack (bz_set_forcings, bz_forcing.hip)
     bool has_relaxation = false;      // bz_set_relaxation: [rate target](u v w theta q), Nz + 1 entries each

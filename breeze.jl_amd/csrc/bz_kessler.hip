@@ -215,6 +215,7 @@ extern "C" int bz_set_kessler_microphysics(bz_ctx *ctx, const bz_kessler_microph
     ctx->kessler = *f;
     ctx->kessler_pst = standard_pressure;
     g.microphysics = 2;
+    bzi_clear_mixed_phase(g);
     g.sa_Ll = params->liquid_latent_heat;
     g.sa_cl = params->liquid_heat_capacity;
     g.qv_field = f->vapor_mass_fraction;

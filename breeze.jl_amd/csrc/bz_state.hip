@@ -24,6 +24,7 @@ __global__ __launch_bounds__(TX *TY) void k_velocities(DevGrid g, double *__rest
 
 // ---- _compute_auxiliary_thermodynamic_variables! (:256-292) with
 // potential_temperature_formulation.jl:115-145 and Thermodynamics/dynamic_states.jl:31-58.
+template <bool MIX = false>      // MIX: the mixed-phase instantiation (bz_set_mixed_phase_equilibrium), selected by the host
 __global__ __launch_bounds__(TX *TY) void k_thermo(DevGrid g, double *__restrict__ theta,
                                                   double *__restrict__ qv, double *__restrict__ T,
                                                   const double *__restrict__ rtheta,
@@ -56,7 +57,11 @@ __global__ __launch_bounds__(TX *TY) void k_thermo(DevGrid g, double *__restrict
     }
     if (g.microphysics == 1) {      // maybe_adjust_thermodynamic_state(SaturationAdjustment) + update_microphysical_fields!
         double qvv, qll;
-        T[n] = bz_sa_diagnose(g, th, q, g.p_r[k], qvv, qll);
+        if constexpr (MIX) {
+            double qii;
+            T[n] = bz_mp_diagnose(g, th, q, g.p_r[k], qvv, qll, qii);
+            g.qi_field[n] = qii;
+        } else T[n] = bz_sa_diagnose(g, th, q, g.p_r[k], qvv, qll);
         g.qv_field[n] = qvv;
         g.ql_field[n] = qll;
         return;
@@ -163,13 +168,17 @@ extern "C" int bz_compute_auxiliary_thermodynamic_variables(bz_ctx *ctx, const b
     const DevGrid &g = ctx->dg;
     {
         ProfileScope ps(ctx, "compute_auxiliary_thermodynamic_variables");
-        hipLaunchKernelGGL(k_thermo, cell_grid(g, g.Nz), dim3(TX, TY), 0, ctx->stream, g, s->theta, s->q, s->T,
-                           s->rho_theta, s->rho_q);
+        if (g.sa_mixed)
+            hipLaunchKernelGGL(k_thermo<true>, cell_grid(g, g.Nz), dim3(TX, TY), 0, ctx->stream, g, s->theta, s->q, s->T,
+                               s->rho_theta, s->rho_q);
+        else
+            hipLaunchKernelGGL(k_thermo<false>, cell_grid(g, g.Nz), dim3(TX, TY), 0, ctx->stream, g, s->theta, s->q, s->T,
+                               s->rho_theta, s->rho_q);
         BZ_LAUNCH_CHECK();
     }
-    double *f[6] = {s->T, s->q, s->theta, g.qv_field, g.microphysics == 2 ? g.qcl_field : g.ql_field, g.qr_field};
+    double *f[6] = {s->T, s->q, s->theta, g.qv_field, g.microphysics == 2 ? g.qcl_field : g.ql_field, g.microphysics == 2 ? g.qr_field : g.qi_field};
     int kd[6] = {0, 0, 0, 0, 0, 0};
-    int rch = bzi_fill_halos_multi(ctx, f, kd, g.microphysics == 2 ? 6 : (g.microphysics ? 5 : 3));
+    int rch = bzi_fill_halos_multi(ctx, f, kd, (g.microphysics == 2 || g.sa_mixed) ? 6 : (g.microphysics ? 5 : 3));
     if (rch) return rch;
     return bzi_tracer_specific(ctx);       // tracer_density_to_specific! (update_atmosphere_model_state.jl:43)
 }

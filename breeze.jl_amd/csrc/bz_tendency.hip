@@ -243,7 +243,7 @@ __device__ __forceinline__ double flux_Ww(const DevGrid &g, const double *__rest
     return wt * wR;
 }
 
-template <bool BUOY = true>
+template <bool BUOY = true, bool MIX = false>      // MIX: the mixed-phase instantiation of the buoyancy (condensate q^l + q^i)
 __global__ __launch_bounds__(64 * TYB) void k_w_tendency(DevGrid g, double *__restrict__ Gw,
                                                         const double *__restrict__ ru,
                                                         const double *__restrict__ rv,
@@ -264,12 +264,12 @@ __global__ __launch_bounds__(64 * TYB) void k_w_tendency(DevGrid g, double *__re
     // ring of w around centre k-1 (faces k-3 .. k+2) to start; centre k needs faces k-2..k+3
     double zm3 = w[n - 3 * sz], zm2 = w[n - 2 * sz], zm1 = w[n - sz], z0 = w[n], zp1 = w[n + sz], zp2 = w[n + 2 * sz];
     double Fz_lo = flux_Ww(g, rw, n - sz, k0 - 1, zm3, zm2, zm1, z0, zp1, zp2);
-    double b_lo = BUOY ? bz_buoyancy(g, T, qv, n - sz, k0 - 1) : 0.0;
+    double b_lo = BUOY ? bz_buoyancy<MIX>(g, T, qv, n - sz, k0 - 1) : 0.0;
 
     for (int k = k0; k < k1; ++k, n += sz) {
         double zp3 = w[n + 3 * sz];
         double Fz_hi = flux_Ww(g, rw, n, k, zm2, zm1, z0, zp1, zp2, zp3);
-        double b_hi = BUOY ? bz_buoyancy(g, T, qv, n, k) : 0.0;
+        double b_hi = BUOY ? bz_buoyancy<MIX>(g, T, qv, n, k) : 0.0;
         const int Bf = bz_buffer_face(k, g.Nz);
 
         // x: F_Uw at x-faces i (lo), i+1 (hi): advecting flux = centred-in-z of Ax(k)*rho_u to face k
@@ -376,7 +376,8 @@ static int momentum_tendencies_gen1(bz_ctx *ctx, const bz_state *s, const bz_pro
     if (!Ein && g.Nz > 1) {
         ProfileScope ps(ctx, "z_momentum_tendency");
         const Gen1Launch Lw(g, g.Nz - 1);
-        hipLaunchKernelGGL(k_w_tendency<true>, Lw.grid, Lw.block, 0, ctx->stream, g, G->rho_w, s->rho_u, s->rho_v, s->rho_w, s->w, s->T, s->q, Lw.kc);
+        if (g.sa_mixed) hipLaunchKernelGGL((k_w_tendency<true, true>), Lw.grid, Lw.block, 0, ctx->stream, g, G->rho_w, s->rho_u, s->rho_v, s->rho_w, s->w, s->T, s->q, Lw.kc);
+        else hipLaunchKernelGGL(k_w_tendency<true>, Lw.grid, Lw.block, 0, ctx->stream, g, G->rho_w, s->rho_u, s->rho_v, s->rho_w, s->w, s->T, s->q, Lw.kc);
     }
     BZ_LAUNCH_CHECK();
     return BZ_OK;

@@ -79,13 +79,14 @@ int bzi_w_tendency_lds(bz_ctx *ctx, const bz_state *s, const bz_prognostic *G, c
                        const RKEpilogue *Ein, int buoyancy_mode)
 {
     const DevGrid &g = ctx->dg;
-    const int bm = (buoyancy_mode == 0 && g.microphysics) ? 3 : buoyancy_mode;
+    const int bm = (buoyancy_mode == 0 && g.microphysics) ? (g.sa_mixed ? 5 : 3) : buoyancy_mode;      // 5: the mixed-phase instantiation of 3
     if (bzi_k6_stored_ok(ctx)) return bzi_k6_stored(ctx, 2, s, G, U0, Ein, bm);
     ProfileScope ps(ctx, Ein ? "z_momentum_tendency+rk3" : "z_momentum_tendency");
     const RKEpilogue E = momentum_epilogue(Ein, U0 ? U0->rho_w : nullptr);
     const Tend3Fields F = momentum_fields(s, s->w, G->rho_w);
     const TileLaunch L(g, g.Nz - 1);
     if (bm == 3) hipLaunchKernelGGL((k_w_tend_lds<8, 3>), L.grid, L.block, 0, ctx->stream, g, F, L.kc, E);
+    else if (bm == 5) hipLaunchKernelGGL((k_w_tend_lds<8, 5>), L.grid, L.block, 0, ctx->stream, g, F, L.kc, E);
     else if (bm == 0) hipLaunchKernelGGL((k_w_tend_lds<8>), L.grid, L.block, 0, ctx->stream, g, F, L.kc, E);
     else if (bm == 1) hipLaunchKernelGGL((k_w_tend_lds<8, 1>), L.grid, L.block, 0, ctx->stream, g, F, L.kc, E);
     else hipLaunchKernelGGL((k_w_tend_lds<8, 2>), L.grid, L.block, 0, ctx->stream, g, F, L.kc, E);

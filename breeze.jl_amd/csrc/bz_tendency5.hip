@@ -261,6 +261,7 @@ int bzi_k6_stored(bz_ctx *ctx, int comp, const bz_state *s, const bz_prognostic 
         if (bm == 0) hipLaunchKernelGGL((k6_w<TY, false, false, false, 0>), grid, block, 0, ctx->stream, g, L, kc, E);
         else if (bm == 1) hipLaunchKernelGGL((k6_w<TY, false, false, false, 1>), grid, block, 0, ctx->stream, g, L, kc, E);
         else if (bm == 2) hipLaunchKernelGGL((k6_w<TY, false, false, false, 2>), grid, block, 0, ctx->stream, g, L, kc, E);
+        else if (bm == 5) hipLaunchKernelGGL((k6_w<TY, false, false, false, 5>), grid, block, 0, ctx->stream, g, L, kc, E);
         else hipLaunchKernelGGL((k6_w<TY, false, false, false, 3>), grid, block, 0, ctx->stream, g, L, kc, E);
     }
     BZ_LAUNCH_CHECK();

@@ -956,7 +956,7 @@ __device__ __forceinline__ double buoyancy5(const DevGrid &g, double rth, double
 // ---------------------------------------------------------------------------------------------------------------------
 // BM: 4 the lean seam (w and the buoyancy inputs derived from the prognostic fields); 0 .. 3 the STORED-velocity instantiations (see Lean5 / k6_u)
 // with the buoyancy modes of k_w_tend_lds (bz_tendency4_kernels.h), which they replace: 0 anelastic buoyancy from the stored T, q;
-// 3 the same with the diagnosed q^v, q^l of saturation adjustment / the Kessler species; 1 none; 2 the compressible slow vertical
+// 3 the same with the diagnosed q^v, q^l of saturation adjustment / the Kessler species; 5 its mixed-phase instantiation (q^l + q^i); 1 none; 2 the compressible slow vertical
 // momentum G^s = G_adv - dz(p - p_r) - g Iz(rho - rho_r) with Lean5::bT = pressure, bq = total density (acoustic_substepping.jl:727-752)
 template <int TY, bool WY = false, bool DRYQ = false, bool GUARD = true, int BM = 4>      // DRYQ: rho q identically zero (see k5_scalar_pair): its loads are skipped, every wavefront takes the dry Exner factor
 __global__ __launch_bounds__(64 * TY, BZ6_W_WAVES) void k6_w(DevGrid g, Lean5 L, int kchunk, RKEpilogue E)
@@ -1028,6 +1028,7 @@ __global__ __launch_bounds__(64 * TY, BZ6_W_WAVES) void k6_w(DevGrid g, Lean5 L,
         if constexpr (BM == 4) b_lo = buoyancy5<dryq>(g, pa[n - sz], dryq ? 0.0 : pb[n - sz], kbeg - 1, LV.rho(kbeg - 1), LV.rrho(kbeg - 1), LV.pi(kbeg - 1), LV.T_r(kbeg - 1));
         else if constexpr (BM == 0) b_lo = buoyancy3(g, bT[n - sz], bq[n - sz], kbeg - 1);
         else if constexpr (BM == 3) b_lo = bz_buoyancy(g, bT, bq, (long long)(n - sz), kbeg - 1);
+        else if constexpr (BM == 5) b_lo = bz_buoyancy<true>(g, bT, bq, (long long)(n - sz), kbeg - 1);
         else if constexpr (BM == 2) { b_lo = bT[n - sz] - g.p_r[kbeg - 1]; r_lo = bq[n - sz] - g.rho[kbeg - 1]; }
         else b_lo = 0.0;
     }
@@ -1092,6 +1093,7 @@ __global__ __launch_bounds__(64 * TY, BZ6_W_WAVES) void k6_w(DevGrid g, Lean5 L,
         if constexpr (BM == 4) b_hi = buoyancy5<dryq>(g, Tcur, rqcur, k, LV.rho(k), LV.rrho(k), LV.pi(k), LV.T_r(k));
         else if constexpr (BM == 0) b_hi = buoyancy3(g, Tcur, rqcur, k);
         else if constexpr (BM == 3) b_hi = bz_buoyancy(g, bT, bq, (long long)n, k);
+        else if constexpr (BM == 5) b_hi = bz_buoyancy<true>(g, bT, bq, (long long)n, k);
         else if constexpr (BM == 2) { b_hi = Tcur - g.p_r[k]; r_hi = rqcur - g.rho[k]; }
         T[buf ^ 1][ty + 3][tc] = wr[4];
         if (hok) T[buf ^ 1][hr][hc] = ST ? p_h : bz_cdiv(p_h, LV.rho_f(k + 1), LV.rrho_f(k + 1));

@@ -346,7 +346,7 @@ __global__ __launch_bounds__(256) void k_v_tendency_g(DevGrid g, double *__restr
 }
 
 // faces k = 1 .. Nz-1; + Iz(buoyancy) unless !BUOY (slow tendency of the split-explicit compressible model)
-template <int R, int PASS, bool BUOY = true>
+template <int R, int PASS, bool BUOY = true, bool MIX = false>      // MIX: the mixed-phase instantiation of the buoyancy (condensate q^l + q^i)
 __global__ __launch_bounds__(256) void k_w_tendency_g(DevGrid g, double *__restrict__ Gw, const double *__restrict__ ru,
                                                       const double *__restrict__ rv, const double *__restrict__ rw,
                                                       const double *__restrict__ w, const double *__restrict__ T,
@@ -385,7 +385,7 @@ __global__ __launch_bounds__(256) void k_w_tendency_g(DevGrid g, double *__restr
     }
     const double a = (W.xwall ? 0.0 : F.x[n + W.xp]) - F.x[n], b = g.flat_y ? 0.0 : F.y[n + W.yp] - F.y[n], c = F.z[n] - F.z[n - sz];
     const double adv = -(g.Vinv_f[k] * (a + b + c));
-    if (BUOY) Gw[n] = rk_out(F, adv + 0.5 * (bz_buoyancy(g, T, qv, n - sz, k - 1) + bz_buoyancy(g, T, qv, n, k)), n);
+    if (BUOY) Gw[n] = rk_out(F, adv + 0.5 * (bz_buoyancy<MIX>(g, T, qv, n - sz, k - 1) + bz_buoyancy<MIX>(g, T, qv, n, k)), n);
     else Gw[n] = adv;
 }
 
@@ -631,6 +631,7 @@ static int generic_flux_buffers(bz_ctx *ctx, FluxBuf &F)
         hipLaunchKernelGGL((KERNEL<R, 2 TARGS>), dim3((g.Nx + 255) / 256, g.Ny, (nk)), block, 0, ctx->stream, g, __VA_ARGS__, F);   \
     } while (0)
 #define COMMA_FALSE , false
+#define COMMA_TRUE_TRUE , true, true
 // the single-pass marching kernel where the grid allows it (see k_tendency_m), else the two passes
 static bool generic_march_ok(const bz_ctx *ctx)
 {
@@ -684,7 +685,8 @@ static int launch_generic(bz_ctx *ctx, const bz_state *s, const bz_prognostic *G
     if (g.Nz > 1) {
         ProfileScope ps(ctx, E ? "z_momentum_tendency+rk3" : "z_momentum_tendency");
         epi(U0 ? U0->rho_w : nullptr, s->rho_w);
-        if (buoyancy) GENERIC_LAUNCH(k_w_tendency_g, , 1, g.Nz - 1, G->rho_w, s->rho_u, s->rho_v, s->rho_w, s->w, s->T, s->q);
+        if (buoyancy && g.sa_mixed) GENERIC_LAUNCH(k_w_tendency_g, COMMA_TRUE_TRUE, 1, g.Nz - 1, G->rho_w, s->rho_u, s->rho_v, s->rho_w, s->w, s->T, s->q);
+        else if (buoyancy) GENERIC_LAUNCH(k_w_tendency_g, , 1, g.Nz - 1, G->rho_w, s->rho_u, s->rho_v, s->rho_w, s->w, s->T, s->q);
         else GENERIC_LAUNCH(k_w_tendency_g, COMMA_FALSE, 1, g.Nz - 1, G->rho_w, s->rho_u, s->rho_v, s->rho_w, s->w, (const double *)nullptr,
                             (const double *)nullptr);
     }

@@ -60,6 +60,9 @@ class _Operation(_Arithmetic):
     uses_model_pressure = False      # the potential temperatures: dynamics_pressure_for_potential_temperature
 
     def __init__(self, model):
+        from ._context import refuse_mixed_phase
+        # the diagnostic kernels form Rᵐ, cᵖᵐ and the latent term from qᵛ and qˡ and saturate over the liquid surface
+        refuse_mixed_phase(getattr(model, "microphysics", None), type(self).__name__, "the diagnostic kernels know no qⁱ and no mixed-phase surface")
         self.model = model
         self.code = _lib.BZ_DIAG[self.kind]
 

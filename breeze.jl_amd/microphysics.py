@@ -1,5 +1,5 @@
 """Host-side mirror of Breeze.Microphysics.SaturationAdjustment (src/Microphysics/saturation_adjustment.jl:20-60) and the
-solver vocabulary of Breeze.Solvers (src/Solvers.jl:55-136): warm-phase equilibrium with the secant iteration."""
+solver vocabulary of Breeze.Solvers (src/Solvers.jl:55-136): warm-phase and mixed-phase equilibrium with the secant iteration."""
 
 
 class WarmPhaseEquilibrium:
@@ -7,8 +7,18 @@ class WarmPhaseEquilibrium:
 
 
 class MixedPhaseEquilibrium:
-    def __init__(self, *a, **k):
-        raise NotImplementedError("MixedPhaseEquilibrium is not implemented in the HIP path (warm phase only)")
+    """MixedPhaseEquilibrium(; freezing_temperature=273.15, homogeneous_ice_nucleation_temperature=233.15)
+    (src/Thermodynamics/vapor_saturation.jl:146-176): the equilibrium liquid fraction of the condensate falls linearly from 1 at Tᶠ to 0 at Tʰ."""
+
+    def __init__(self, freezing_temperature=273.15, homogeneous_ice_nucleation_temperature=233.15):
+        if freezing_temperature < homogeneous_ice_nucleation_temperature:
+            raise ValueError("`freezing_temperature` must be greater than `homogeneous_ice_nucleation_temperature`")
+        if freezing_temperature == homogeneous_ice_nucleation_temperature:
+            # the reference accepts this and divides 0 by 0 in equilibrated_surface: λ = (clamp(T, Tʰ, Tᶠ) - Tʰ) / (Tᶠ - Tʰ)
+            raise ValueError("`freezing_temperature` must be greater than `homogeneous_ice_nucleation_temperature`: with equal temperatures the "
+                             "liquid fraction (T - Tʰ) / (Tᶠ - Tʰ) is 0 / 0")
+        self.freezing_temperature = float(freezing_temperature)
+        self.homogeneous_ice_nucleation_temperature = float(homogeneous_ice_nucleation_temperature)
 
 
 class SecantSolver:
@@ -19,13 +29,20 @@ class SecantSolver:
 
 
 class SaturationAdjustment:
-    """SaturationAdjustment(; solver = SecantSolver(abstol=1e-4, maxiter=20), equilibrium)."""
+    """SaturationAdjustment(; solver = SecantSolver(abstol=1e-4, maxiter=20), equilibrium = MixedPhaseEquilibrium())
+    (saturation_adjustment.jl:55-70).  The mixed-phase equilibrium runs on the anelastic AtmosphereModel; every other model refuses it by name."""
 
     def __init__(self, solver=None, equilibrium=None):
-        if equilibrium is None or not isinstance(equilibrium, WarmPhaseEquilibrium):
-            raise NotImplementedError("the HIP path implements SaturationAdjustment(equilibrium = WarmPhaseEquilibrium())")
+        if equilibrium is None:
+            equilibrium = MixedPhaseEquilibrium()
+        if not isinstance(equilibrium, (WarmPhaseEquilibrium, MixedPhaseEquilibrium)):
+            raise NotImplementedError("the HIP path implements SaturationAdjustment(equilibrium = WarmPhaseEquilibrium() | MixedPhaseEquilibrium())")
         self.equilibrium = equilibrium
         self.solver = solver or SecantSolver()
+
+    @property
+    def mixed_phase(self):
+        return isinstance(self.equilibrium, MixedPhaseEquilibrium)
 
 
 class InstantaneousPrecipitation:
@@ -35,6 +52,9 @@ class InstantaneousPrecipitation:
     and the condensate leaves as precipitation.  The prognostic moisture is ρqᵛ; there are no condensate fields.  CompressibleDynamics only."""
 
     def __init__(self, equilibrium=None, solver=None):
+        if isinstance(equilibrium, MixedPhaseEquilibrium):
+            raise NotImplementedError("InstantaneousPrecipitation(equilibrium = MixedPhaseEquilibrium()): the density-based mixed-phase adjustment "
+                                      "of CompressibleDynamics is not implemented; WarmPhaseEquilibrium() is")
         self.saturation_adjustment = SaturationAdjustment(solver=solver, equilibrium=WarmPhaseEquilibrium() if equilibrium is None else equilibrium)
 
 

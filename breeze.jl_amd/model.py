@@ -186,6 +186,7 @@ def _check_kinematic_options(model_type, grid, dynamics, advection, formulation,
         no(f"the {str(formulation).lstrip(':')} formulation is")
     if microphysics is not None and not isinstance(microphysics, SaturationAdjustment):
         no(f"microphysics {type(microphysics).__name__} (Kessler) is")
+    _context.refuse_mixed_phase(microphysics, "AtmosphereModel(dynamics = PrescribedDynamics(...))", "the kinematic driver diagnoses qᵛ and qˡ only")
     if closure is not None:
         no("a closure is")
     if forcing is not None or coriolis is not None:
@@ -352,6 +353,9 @@ class AtmosphereModel(_context.ContextOwner):
                                                     "(CompressibleAtmosphereModel); not on the anelastic AtmosphereModel, the kinematic driver or their y-slab models")
         if microphysics is not None and formulation != "LiquidIcePotentialTemperature":
             raise NotImplementedError("microphysics is implemented for the potential-temperature formulation")
+        if any("Slab" in k.__name__ for k in type(self).__mro__):      # the y-slab models of distributed.py
+            _context.refuse_mixed_phase(microphysics, type(self).__name__, "the halo exchanges of y-slab models carry qᵛ and qˡ only")
+        _context.check_mixed_phase_model(microphysics, thermodynamic_constants, forcing, boundary_conditions)
         self.microphysics = microphysics
         if self._kessler:
             _context.check_kessler_constants(thermodynamic_constants)
@@ -667,6 +671,8 @@ def set_(model, enforce_mass_conservation=True, **kw):
         if key in ("T", "ℋ") and (model.formulation != "LiquidIcePotentialTemperature" or getattr(model, "_kessler", False)):
             raise NotImplementedError(f"set!(model; {name}) is implemented for the potential-temperature formulation "
                                       "(microphysics nothing or SaturationAdjustment)")
+        if key in ("T", "ℋ"):      # both conversions below know the liquid phase only
+            _context.refuse_mixed_phase(model.microphysics, f"set!(model; {name})", "θ from T and qᵛ⁺ from ℋ are formed without qⁱ and over the liquid surface")
         if key == "T":
             # set_thermodynamic_variable!(model, Val(:T), value) (potential_temperature_tendency.jl:202-250): theta^li from the
             # in-situ temperature with the current moisture fractions, theta = (T - L q^l / c_pm) / Pi

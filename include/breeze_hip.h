@@ -131,6 +131,20 @@ typedef struct bz_saturation_adjustment {
     int32_t reserved;
 } bz_saturation_adjustment;
 int bz_set_saturation_adjustment(bz_ctx *ctx, const bz_saturation_adjustment *params, double *q_vapor, double *q_liquid);
+/* equilibrium = MixedPhaseEquilibrium(freezing_temperature, homogeneous_ice_nucleation_temperature) of the SaturationAdjustment attached
+ * by bz_set_saturation_adjustment (src/Thermodynamics/vapor_saturation.jl:146-176, src/Microphysics/saturation_adjustment.jl:92-100,
+ * 128-149,193-231), called AFTER it: the condensate q^c = max(0, q^t - q^v+) is split q^l = lambda q^c, q^i = (1 - lambda) q^c with
+ * lambda(T) = (clamp(T, T^h, T^f) - T^h) / (T^f - T^h), the saturation surface is the PlanarMixedPhaseSurface(lambda) of the temperature it is
+ * evaluated at, T carries both latent heats, q^i is diagnosed into model.microphysical_fields.q^i (device parent array given here) and the
+ * buoyancy reads q^l + q^i as condensate.  Constants: the ice CondensedPhase of ThermodynamicConstants.  params == NULL returns the context
+ * to the warm phase; bz_set_saturation_adjustment (NULL or a new attachment) and bz_set_kessler_microphysics clear the ice state too.
+ * Anelastic single-device contexts only: BZ_ERR_UNSUPPORTED, bz_last_error naming the reason, on CompressibleDynamics, y-slab and
+ * kinematic contexts and on a context without an attached SaturationAdjustment.  Every call invalidates recorded steps. */
+typedef struct bz_mixed_phase_equilibrium {
+    double freezing_temperature, homogeneous_ice_nucleation_temperature;
+    double ice_latent_heat, ice_heat_capacity;
+} bz_mixed_phase_equilibrium;
+int bz_set_mixed_phase_equilibrium(bz_ctx *ctx, const bz_mixed_phase_equilibrium *params, double *q_ice);
 int bz_set_stream(bz_ctx *ctx, void *hip_stream);
 int bz_sync(bz_ctx *ctx);
 const char *bz_last_error(const bz_ctx *ctx);
