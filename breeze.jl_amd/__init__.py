@@ -20,6 +20,8 @@ from .compressible import (AcousticRungeKutta3, AcousticSubstepper, Compressible
                            LinearRamp, CubicRamp, Sin2Ramp, NormalFlowBoundaryCondition)
 from .compressible import HydrostaticallyBalancedDensity, set_to_mean_  # noqa: F401,E402
 from .microphysics import InstantaneousPrecipitation, MixedPhaseEquilibrium, SaturationAdjustment, SecantSolver, WarmPhaseEquilibrium  # noqa: F401,E402
+from .microphysics import BulkMicrophysics, NonEquilibriumCloudFormation, SpeciesBorrowing, VerticalBorrowing  # noqa: F401,E402
+from .model import fix_negative_moisture_  # noqa: F401,E402
 from .model import cell_advection_timescale, diagnostics_stale, many_time_steps_, nan_checker  # noqa: F401,E402
 from .model import PrescribedDynamics, PrescribedVelocityFields, compute_kinematic_tendencies_  # noqa: F401,E402
 from .microphysics import (DCMIP2016KesslerMicrophysics, KesslerMicrophysicalFields, TetensFormula,  # noqa: F401,E402

@@ -177,8 +177,16 @@ def check_microphysics(microphysics, message, instantaneous_precipitation_refuse
 
 
 def is_mixed_phase(microphysics):
-    from .microphysics import MixedPhaseEquilibrium
-    return isinstance(getattr(microphysics, "equilibrium", None), MixedPhaseEquilibrium)
+    from .microphysics import MixedPhaseEquilibrium, cloud_formation
+    return isinstance(getattr(cloud_formation(microphysics), "equilibrium", None), MixedPhaseEquilibrium)      # (through a BulkMicrophysics)
+
+
+def refuse_bulk_microphysics(microphysics, where, why):
+    """BulkMicrophysics(...) runs on the single-device anelastic AtmosphereModel; every other model says so here, by name, before its
+    generic microphysics type check."""
+    from .microphysics import BulkMicrophysics
+    if isinstance(microphysics, BulkMicrophysics):
+        raise NotImplementedError(f"{where}: BulkMicrophysics is not implemented ({why}); it runs on the single-device anelastic AtmosphereModel")
 
 
 def refuse_mixed_phase(microphysics, where, why):
@@ -244,19 +252,35 @@ def attach_kessler(model, standard_pressure):
 def attach_saturation_adjustment(model, fld):
     """materialize_microphysical_fields(::WarmPhaseSaturationAdjustment): (qᵛ, qˡ, qᵉ); (::MixedPhaseSaturationAdjustment): (qᵛ, qˡ, qⁱ, qᵉ)
     (saturation_adjustment.jl:118-119); qᵉ is the specific moisture slot."""
-    c, solver = model.thermodynamic_constants, model.microphysics.solver
-    mixed = is_mixed_phase(model.microphysics)
+    from .microphysics import cloud_formation
+    adjustment = cloud_formation(model.microphysics)
+    c, solver = model.thermodynamic_constants, adjustment.solver
+    mixed = is_mixed_phase(adjustment)
     μ = model.microphysical_fields = {"qᵛ": fld("ccc"), "qˡ": fld("ccc"), **({"qⁱ": fld("ccc")} if mixed else {}), "qᵉ": model.specific_moisture}
     sa = model._T.bz_saturation_adjustment(c.liquid_reference_latent_heat, c.liquid_heat_capacity, c.energy_reference_temperature,
                                            c.triple_point_temperature, c.triple_point_pressure, solver.abstol, solver.maxiter, 0)
     model._check(model._lib.bz_set_saturation_adjustment(model._ctx, C.byref(sa), C.c_void_p(μ["qᵛ"].ptr()), C.c_void_p(μ["qˡ"].ptr())),
                  "bz_set_saturation_adjustment")
     if mixed:
-        eq = model.microphysics.equilibrium
+        eq = adjustment.equilibrium
         mp = model._T.bz_mixed_phase_equilibrium(eq.freezing_temperature, eq.homogeneous_ice_nucleation_temperature,
                                                  c.ice_reference_latent_heat, c.ice_heat_capacity)
         model._check(model._lib.bz_set_mixed_phase_equilibrium(model._ctx, C.byref(mp), C.c_void_p(μ["qⁱ"].ptr())),
                      "bz_set_mixed_phase_equilibrium")
+
+
+def attach_negative_moisture_correction(model):
+    """negative_moisture_correction(microphysics) of a BulkMicrophysics -> bz_set_negative_moisture_correction.  The non-precipitating scheme
+    has no species (correction_moisture_fields, correction_number_mass_pairs and correction_number_fields are empty tuples): the lists of
+    the descriptor stay empty, and SpeciesBorrowing() without vertical borrowing launches nothing."""
+    from .microphysics import SpeciesBorrowing, vertical_borrowing
+    correction = getattr(model.microphysics, "negative_moisture_correction", None)
+    if correction is None:
+        return
+    d = _lib.bz_negative_moisture_correction()
+    d.species_borrowing = 1 if isinstance(correction, SpeciesBorrowing) else 0
+    d.vertical_borrowing = 1 if vertical_borrowing(correction) else 0
+    model._check(model._lib.bz_set_negative_moisture_correction(model._ctx, C.byref(d)), "bz_set_negative_moisture_correction")
 
 
 def attach_instantaneous_precipitation(model, fld):

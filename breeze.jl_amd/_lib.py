@@ -63,6 +63,14 @@ class bz_mixed_phase_equilibrium(C.Structure):
                                           "ice_heat_capacity")]
 
 
+class bz_negative_moisture_correction(C.Structure):
+    """Descriptor of bz_set_negative_moisture_correction: the two phases, the species chain (heaviest first), the (number, mass) pairs and the
+    clamped number fields, every array a device parent array.  Pointers and counts only: one struct for both precisions."""
+    _fields_ = [("species_borrowing", C.c_int32), ("vertical_borrowing", C.c_int32),
+                ("n_mass", C.c_int32), ("n_pairs", C.c_int32), ("n_clamp", C.c_int32), ("reserved", C.c_int32),
+                ("mass", C.c_void_p * 4), ("number", C.c_void_p * 4), ("pair_mass", C.c_void_p * 4), ("clamp", C.c_void_p * 4)]
+
+
 class bz_bulk_surface_fluxes(C.Structure):
     _fields_ = [(n, C.c_double) for n in (
         "drag_coefficient", "drag_gustiness", "drag_surface_temperature",
@@ -232,6 +240,8 @@ SYMBOLS = {
     "bz_set_formulation": (C.c_int, [_ctx, C.c_int]),
     "bz_set_saturation_adjustment": (C.c_int, [_ctx, C.POINTER(bz_saturation_adjustment), C.c_void_p, C.c_void_p]),
     "bz_set_mixed_phase_equilibrium": (C.c_int, [_ctx, C.POINTER(bz_mixed_phase_equilibrium), C.c_void_p]),
+    "bz_set_negative_moisture_correction": (C.c_int, [_ctx, C.POINTER(bz_negative_moisture_correction)]),
+    "bz_fix_negative_moisture": (C.c_int, [_ctx, C.POINTER(bz_state)]),
     "bz_set_stream": (C.c_int, [_ctx, C.c_void_p]),
     "bz_graph_enable": (C.c_int, [_ctx, C.c_int]),
     "bz_graph_info": (C.c_int, [_ctx, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),

@@ -422,6 +422,7 @@ class CompressibleAtmosphereModel(_context.ContextOwner):
                       else "InstantaneousPrecipitation: not implemented on y-slab (distributed) compressible models"
                       if type(self) is not CompressibleAtmosphereModel
                       else "InstantaneousPrecipitation: not implemented on a compressible model with a Flat y" if Flat in grid.topology else None)
+        _context.refuse_bulk_microphysics(microphysics, type(self).__name__, "the moisture update of CompressibleDynamics is fused into the acoustic stage epilogue")
         _context.refuse_mixed_phase(microphysics, type(self).__name__, "the density-based mixed-phase adjustment of CompressibleDynamics is the follow-up")
         self._kessler = _context.check_microphysics(microphysics, "compressible microphysics: DCMIP2016KesslerMicrophysics() and "
                                                                   "SaturationAdjustment(equilibrium = WarmPhaseEquilibrium()) are implemented",

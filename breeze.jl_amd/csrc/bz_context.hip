@@ -79,6 +79,7 @@ void bzi_read_tuning(bz_tuning &t)
     t.comm_no_overlap = on("BZ_COMM_NO_OVERLAP");
     t.comm_self_messages = on("BZ_COMM_SELF_MESSAGES");
     t.comm_no_side_scalar = on("BZ_COMM_NO_SIDE_SCALAR");
+    t.nmc_store_always = on("BZ_NMC_STORE_ALWAYS");
     t.graph = num("BZ_GRAPH", -1);
     t.graph_debug = on("BZ_GRAPH_DEBUG");
 }
@@ -159,7 +160,7 @@ extern "C" int bz_set_saturation_adjustment(bz_ctx *ctx, const bz_saturation_adj
     if (ctx) ++ctx->config_epoch;      // captured steps (bz_graph.hip) belong to one configuration
     if (!ctx) return BZ_ERR_INVALID;
     DevGrid &g = ctx->dg;
-    if (!params) { g.microphysics = 0; g.qv_field = g.ql_field = nullptr; bzi_clear_mixed_phase(g); return BZ_OK; }
+    if (!params) { g.microphysics = 0; g.qv_field = g.ql_field = nullptr; bzi_clear_mixed_phase(g); ctx->has_nmc = false; return BZ_OK; }
     if (!q_vapor || !q_liquid || params->maxiter < 0) return BZ_ERR_INVALID;
     if (g.formulation != 0) {
         ctx->last_error = "saturation adjustment is implemented for the potential-temperature formulation";

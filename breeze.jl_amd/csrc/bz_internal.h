@@ -469,6 +469,7 @@ struct bz_tuning {
     bool comm_no_overlap = false;     // BZ_COMM_NO_OVERLAP
     bool comm_self_messages = false;  // BZ_COMM_SELF_MESSAGES: world 1 sends every message to itself
     bool comm_no_side_scalar = false; // BZ_COMM_NO_SIDE_SCALAR
+    bool nmc_store_always = false;    // BZ_NMC_STORE_ALWAYS: k_fix_negative_moisture stores every cell instead of the cells whose bits changed
     int graph = -1;                   // BZ_GRAPH (-1: unset)
     bool graph_debug = false;         // BZ_GRAPH_DEBUG
 };
@@ -599,6 +600,10 @@ struct bz_ctx {
     bool has_instant_precip = false;
     double sa_energy_reference_temperature = 0.0;      // of the attached SaturationAdjustment: bz_set_mixed_phase_equilibrium forms L0_i with it
     double *ip_precipitation_rate = nullptr;      // mu.precipitation_rate (caller-owned centre field)
+    // negative_moisture_correction of BulkMicrophysics (bz_set_negative_moisture_correction, bz_negative_moisture.hip): runs at the head of every
+    // update_state! while a SaturationAdjustment is attached (dg.microphysics == 1)
+    bool has_nmc = false;
+    bz_negative_moisture_correction nmc;
     // forcing / Coriolis / bottom-flux stack (bz_set_forcings, bz_forcing.hip)
     bool has_relaxation = false;      // bz_set_relaxation: [rate target](u v w theta q), Nz + 1 entries each
     double *d_relax = nullptr;
@@ -764,6 +769,8 @@ int bzi_cmp_water_closure(bz_ctx *ctx, const bz_compressible_state *s, const bz_
 // implicit_step! of every prognostic field: momentum and the two scalar densities from the arguments, species and tracers from the context
 int bzi_implicit_step(bz_ctx *ctx, double *ru, double *rv, double *rw, double *rth, double *rq, double dtau);
 int bzi_kessler_rk3(bz_ctx *ctx, double dt, double alpha, bool first);
+// fix_negative_moisture!(model) on rho_q where a correction is attached (bz_negative_moisture.hip): the head of the reference's update_state!
+int bzi_fix_negative_moisture(bz_ctx *ctx, double *rho_q);
 // column part of microphysics_model_update! on the attached species; density / pressure: 3-D parents of a compressible context, nullptr = reference columns
 int bzi_kessler_columns(bz_ctx *ctx, double *theta, double *rho_theta, double *rho_q, const double *density, const double *pressure, double dt);
 int bzi_kessler_update(bz_ctx *ctx, const bz_state *s, const bz_prognostic *G, double dt);

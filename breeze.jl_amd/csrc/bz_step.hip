@@ -16,6 +16,7 @@ extern "C" int bz_update_state(bz_ctx *ctx, const bz_state *s, const bz_prognost
     ctx->diagnostics_stale = false;
     if (ctx->d_qstate) BZ_HIP(hipMemsetAsync(ctx->d_qstate, 0, sizeof(int), ctx->stream));      // the moisture may have been set!: unknown (= moist) until the next scan
     bzi_moisture_unknown(ctx);
+    if ((rc = bzi_fix_negative_moisture(ctx, s->rho_q))) return rc;      // fix_negative_moisture!(model)  (:42)
     // fill_halo_regions!(prognostic_fields(model))  (:48) — momentum halos are filled inside bz_compute_velocities (:135-136), the scalars here.
     double *sf[4] = {s->rho_theta, s->rho_q, ctx->dg.rqcl_field, ctx->dg.rqr_field};
     int sk[4] = {0, 0, 0, 0};
@@ -240,6 +241,8 @@ static int step_fused_rk(bz_ctx *ctx, const bz_state *s, const bz_prognostic *U0
         // pressure_anomaly is a diagnostic nobody reads inside the step: only the last stage scatters it
         // (the horizontal sums of the u, v, theta, q it stores ride along: the next stage's subsidence profiles, bz_forcing.hip)
         const bool ride = bzi_level_sums_ride(ctx) && ctx->d_lsum_rows;
+        // fix_negative_moisture! of the stage's update_state! (:42): the RK update wrote rho q in place, the projection touches momentum only
+        if ((rc = bzi_fix_negative_moisture(ctx, s->rho_q))) return rc;
         if ((rc = bzi_project_diagnose(ctx, s, alpha * dt, nullptr, nullptr, G, stage == 2, nullptr, nullptr, ride))) return rc;
         ctx->lsum_fresh = ride;
         if ((rc = bzi_tracer_specific(ctx))) return rc;
@@ -265,6 +268,7 @@ static int step_fused(bz_ctx *ctx, const bz_state *s, const bz_prognostic *U0, c
         if ((rc = bzi_tracer_rk3(ctx, dt, alpha, stage == 0))) return rc;
         if ((rc = bz_implicit_step(ctx, s, alpha * dt))) return rc;
         if ((rc = bzi_poisson_from_momentum(ctx, s, alpha * dt, nullptr))) return rc;
+        if ((rc = bzi_fix_negative_moisture(ctx, s->rho_q))) return rc;      // fix_negative_moisture! of the stage's update_state! (:42)
         if ((rc = bzi_project_diagnose(ctx, s, alpha * dt))) return rc;
         if ((rc = bzi_tracer_specific(ctx))) return rc;
         if ((rc = bzi_surface_layer_stage(ctx, s, stage, dt))) return rc;

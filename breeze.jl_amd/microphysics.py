@@ -59,6 +59,73 @@ class InstantaneousPrecipitation:
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# BulkMicrophysics and its negative moisture correction (src/Microphysics/bulk_microphysics.jl:26-40,208-265,
+# src/AtmosphereModels/negative_moisture_correction.jl)
+# ---------------------------------------------------------------------------------------------------------------------
+class VerticalBorrowing:
+    """VerticalBorrowing() (negative_moisture_correction.jl:45-60): a cell of the moisture prognostic with qᵛ < 0 is filled from the cell below
+    (top to bottom, the mass deficit carried down the column), then the bottom cell borrows from the one above it."""
+
+
+class SpeciesBorrowing:
+    """SpeciesBorrowing(; vertical_borrowing = nothing) (negative_moisture_correction.jl:62-90): at every level a negative species borrows from the
+    next lighter one, the lightest from the moisture prognostic; optionally followed by the vertical redistribution.  The non-precipitating
+    scheme has no species: SpeciesBorrowing() alone has nothing to do."""
+
+    def __init__(self, vertical_borrowing=None):
+        if vertical_borrowing is not None and not isinstance(vertical_borrowing, VerticalBorrowing):
+            raise TypeError("SpeciesBorrowing(vertical_borrowing = ...): nothing or VerticalBorrowing()")
+        self.vertical_borrowing = vertical_borrowing
+
+
+class NonEquilibriumCloudFormation:
+    """NonEquilibriumCloudFormation(liquid, ice = nothing) (bulk_microphysics.jl:73-80): prognostic cloud condensate.  A name the host mirror
+    knows in order to refuse it: no model here runs it."""
+
+    def __init__(self, liquid=None, ice=None):
+        self.liquid, self.ice = liquid, ice
+
+
+class BulkMicrophysics:
+    """BulkMicrophysics(; categories = nothing, cloud_formation = SaturationAdjustment(), precipitation_boundary_condition = nothing,
+    negative_moisture_correction = nothing) (bulk_microphysics.jl:208-265).  Without categories this is the reference's non-precipitating bulk
+    scheme: the wrapped SaturationAdjustment (warm or mixed phase) with, optionally, the negative moisture correction at the head of every
+    update_state!.  Runs on the single-device anelastic AtmosphereModel; every other model refuses it by name."""
+
+    def __init__(self, categories=None, cloud_formation=None, precipitation_boundary_condition=None, negative_moisture_correction=None):
+        if categories is not None:
+            raise NotImplementedError("BulkMicrophysics(categories = ...): precipitating categories (the CloudMicrophysics extension) are not "
+                                      "implemented; categories = nothing is")
+        if isinstance(cloud_formation, NonEquilibriumCloudFormation):
+            raise NotImplementedError("BulkMicrophysics(cloud_formation = NonEquilibriumCloudFormation(...)) is not implemented; "
+                                      "cloud_formation = SaturationAdjustment(...) is")
+        if cloud_formation is None:
+            cloud_formation = SaturationAdjustment()
+        if not isinstance(cloud_formation, SaturationAdjustment):
+            raise NotImplementedError("BulkMicrophysics(cloud_formation = ...): SaturationAdjustment(...) is implemented")
+        if precipitation_boundary_condition is not None:
+            raise NotImplementedError("BulkMicrophysics(precipitation_boundary_condition = ...): there are no precipitating categories whose "
+                                      "sedimentation it would bound; precipitation_boundary_condition = nothing is implemented")
+        if negative_moisture_correction is not None and not isinstance(negative_moisture_correction, (VerticalBorrowing, SpeciesBorrowing)):
+            raise TypeError("BulkMicrophysics(negative_moisture_correction = ...): nothing, VerticalBorrowing() or SpeciesBorrowing(...)")
+        self.cloud_formation = cloud_formation
+        self.categories = None
+        self.precipitation_boundary_condition = None
+        self.negative_moisture_correction = negative_moisture_correction
+
+
+def cloud_formation(microphysics):
+    """The scheme that forms cloud: a BulkMicrophysics' cloud_formation, anything else is its own.  Every place that asks for the
+    SaturationAdjustment, its solver or its equilibrium goes through here, so the wrapper is looked through everywhere alike."""
+    return microphysics.cloud_formation if isinstance(microphysics, BulkMicrophysics) else microphysics
+
+
+def vertical_borrowing(correction):
+    """Whether a negative moisture correction redistributes vertically."""
+    return isinstance(correction, VerticalBorrowing) or (isinstance(correction, SpeciesBorrowing) and correction.vertical_borrowing is not None)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # DCMIP2016 Kessler warm-rain microphysics: the operator-split column update (src/Microphysics/dcmip2016_kessler.jl)
 # ---------------------------------------------------------------------------------------------------------------------
 class TetensFormula:

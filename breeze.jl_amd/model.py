@@ -159,6 +159,7 @@ def _check_kinematic_options(model_type, grid, dynamics, advection, formulation,
     potential-temperature formulation, microphysics nothing or warm-phase saturation adjustment, tracers, one GPU.  Everything else of the
     reference's kinematic driver says so here, by name."""
     from .microphysics import SaturationAdjustment
+    _context.refuse_bulk_microphysics(microphysics, "AtmosphereModel(dynamics = PrescribedDynamics(...))", "the kinematic driver runs no negative moisture correction")
 
     def no(what):
         raise NotImplementedError(f"AtmosphereModel(dynamics = PrescribedDynamics(...)): {what} not implemented")
@@ -347,7 +348,10 @@ class AtmosphereModel(_context.ContextOwner):
                                       "(Bounded x / Bounded y)")
         self.closure = closure
         self.coriolis, self.forcing, self.boundary_conditions = coriolis, forcing, boundary_conditions
-        self._kessler = _context.check_microphysics(microphysics, "microphysics: SaturationAdjustment(equilibrium = WarmPhaseEquilibrium()) and "
+        if any("Slab" in k.__name__ for k in type(self).__mro__):      # the y-slab models of distributed.py
+            _context.refuse_bulk_microphysics(microphysics, type(self).__name__, "y-slab models run no negative moisture correction")
+        from .microphysics import cloud_formation
+        self._kessler = _context.check_microphysics(cloud_formation(microphysics), "microphysics: SaturationAdjustment(equilibrium = WarmPhaseEquilibrium()) and "
                                                                   "DCMIP2016KesslerMicrophysics() are implemented",
                                                     instantaneous_precipitation_refused="InstantaneousPrecipitation: implemented on CompressibleDynamics "
                                                     "(CompressibleAtmosphereModel); not on the anelastic AtmosphereModel, the kinematic driver or their y-slab models")
@@ -431,6 +435,7 @@ class AtmosphereModel(_context.ContextOwner):
             _context.attach_kessler(self, ref.standard_pressure)
         elif microphysics is not None:
             _context.attach_saturation_adjustment(self, fld)
+            _context.attach_negative_moisture_correction(self)      # of a BulkMicrophysics
         if self.tracers:
             arr = (_lib.bz_tracer_fields * len(self.tracers))()
             for t, n in enumerate(self.tracers):
@@ -584,6 +589,12 @@ def fill_halo_regions_(model, field, kind=None):
 def update_state_(model, compute_tendencies=True):
     model._check(model._lib.bz_update_state(model._ctx, C.byref(model._state), C.byref(model._G),
                                             1 if compute_tendencies else 0), "bz_update_state")
+
+
+def fix_negative_moisture_(model):
+    """fix_negative_moisture!(model) (negative_moisture_correction.jl:170-193): the attached correction once on the moisture density.  The
+    whole steps and update_state_ run it themselves; this is the operator alone."""
+    model._check(model._lib.bz_fix_negative_moisture(model._ctx, C.byref(model._state)), "bz_fix_negative_moisture")
 
 
 def compute_tendencies_(model):

@@ -145,6 +145,38 @@ typedef struct bz_mixed_phase_equilibrium {
     double ice_latent_heat, ice_heat_capacity;
 } bz_mixed_phase_equilibrium;
 int bz_set_mixed_phase_equilibrium(bz_ctx *ctx, const bz_mixed_phase_equilibrium *params, double *q_ice);
+/* negative_moisture_correction of BulkMicrophysics (src/Microphysics/bulk_microphysics.jl:26-40; src/AtmosphereModels/
+ * negative_moisture_correction.jl:199-347): fix_negative_moisture!(model), the first call of update_state!
+ * (update_atmosphere_model_state.jl:42), on the moisture prognostic rho_q and a species chain.  Per column, k = 1 the bottom, rho the
+ * reference density column:
+ *   species_borrowing: at every level, along mass[0] (heaviest) .. mass[n_mass - 1] -> rho_q, each neighbouring pair (h, l):
+ *     sink = q_h < 0 ? min(-q_h, max(0, q_l)) : 0 with q = rho q / rho;  rho q_h += rho sink, rho q_l -= rho sink.  Then number[p] = 0 where
+ *     pair_mass[p] <= 0 (after the borrowing), then clamp[c] = max(0, clamp[c]).  The lists are used under species_borrowing only.
+ *   vertical_borrowing (rho_q only): for k = Nz .. 2: deficit = rho_q[k] / rho[k] < 0 ? -rho_q[k] dz[k] : 0, rho_q[k] += deficit / dz[k],
+ *     rho_q[k - 1] -= deficit / dz[k - 1]; then the bottom borrows from level 2: dq = (q[1] < 0 & q[2] > 0) ? min(-rho_q[1] dz[1],
+ *     rho_q[2] dz[2]) : 0, rho_q[1] += dq / dz[1], rho_q[2] -= dq / dz[2].
+ * The operations are IEEE +, -, *, / in this order, uncontracted; a NaN passes through.  Interior cells only: the halo fill of
+ * bz_update_state or the projection + diagnosis kernel of a whole step writes the images afterwards.
+ * Every array is a DEVICE centre parent array of the grid; SpeciesBorrowing() of the non-precipitating scheme has empty lists.
+ * While attached, the correction runs once per update_state! of the reference: at the head of bz_update_state and, in the whole-step
+ * tiers, before the projection + diagnosis of every stage (profile slot "fix_negative_moisture"); nothing is launched when the scheme has
+ * nothing to do (no vertical borrowing and empty lists).  The tier a step takes does not depend on it.  c == NULL detaches.
+ * BZ_ERR_UNSUPPORTED, bz_last_error naming the function and the reason: CompressibleDynamics, kinematic and y-slab contexts and contexts
+ * without an attached SaturationAdjustment (bz_set_saturation_adjustment first; detaching it detaches the correction).  BZ_ERR_INVALID:
+ * a count outside 0 .. 4, a null array, an array given twice in a list or in two lists that may not share it (number fields may also be
+ * clamped, pair_mass may name a member of mass), a non-empty list with neither phase selected.  An array equal to the rho_q it is run on
+ * is refused by the run (BZ_ERR_INVALID).  Every call invalidates recorded steps. */
+typedef struct bz_negative_moisture_correction {
+    int32_t species_borrowing, vertical_borrowing;
+    int32_t n_mass, n_pairs, n_clamp, reserved;
+    double *mass[4];
+    double *number[4], *pair_mass[4];
+    double *clamp[4];
+} bz_negative_moisture_correction;
+int bz_set_negative_moisture_correction(bz_ctx *ctx, const bz_negative_moisture_correction *c);
+/* The attached correction once on s->rho_q (only that member of s is read): the per-operator entry point.  BZ_ERR_INVALID with a message
+ * when nothing is attached. */
+int bz_fix_negative_moisture(bz_ctx *ctx, const bz_state *s);
 int bz_set_stream(bz_ctx *ctx, void *hip_stream);
 int bz_sync(bz_ctx *ctx);
 const char *bz_last_error(const bz_ctx *ctx);

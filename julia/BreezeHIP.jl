@@ -559,6 +559,53 @@ function AtmosphereModels.microphysics_model_update!(::Breeze.Microphysics.Insta
     return nothing
 end
 
+# negative_moisture_correction of a bulk scheme (src/AtmosphereModels/negative_moisture_correction.jl): the descriptor of
+# bz_set_negative_moisture_correction.  Pointers and counts only: the same struct binds both precisions.
+struct BzNegativeMoistureCorrection
+    species_borrowing::Int32; vertical_borrowing::Int32
+    n_mass::Int32; n_pairs::Int32; n_clamp::Int32; reserved::Int32
+    mass::NTuple{4, Ptr{Cvoid}}
+    number::NTuple{4, Ptr{Cvoid}}
+    pair_mass::NTuple{4, Ptr{Cvoid}}
+    clamp::NTuple{4, Ptr{Cvoid}}
+end
+
+pad4(ptrs) = ntuple(i -> i <= length(ptrs) ? Ptr{Cvoid}(ptrs[i]) : Ptr{Cvoid}(C_NULL), 4)
+
+"""
+Attach negative_moisture_correction(model.microphysics) to an anelastic context with an attached SaturationAdjustment (after
+bz_set_saturation_adjustment): the species chain correction_moisture_fields (heaviest first; the lightest borrows from model.moisture_density),
+correction_number_mass_pairs and correction_number_fields, at most four each.  `nothing` detaches.  The one- and two-moment schemes of the
+CloudMicrophysics extension keep their own kernels; this call hands their fields to the column kernel.
+"""
+function attach_negative_moisture_correction!(ctx, model)
+    μp, μ = model.microphysics, model.microphysical_fields
+    correction = AtmosphereModels.negative_moisture_correction(μp)
+    if correction === nothing
+        check(ccall((:bz_set_negative_moisture_correction, libbreeze_hip), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), ctx, C_NULL),
+              "bz_set_negative_moisture_correction", ctx)
+        return nothing
+    end
+    species = correction isa AtmosphereModels.SpeciesBorrowing
+    vertical = correction isa AtmosphereModels.VerticalBorrowing || (species && correction.vertical_borrowing !== nothing)
+    mass = species ? map(devptr, AtmosphereModels.correction_moisture_fields(μp, μ)) : ()
+    pairs = species ? AtmosphereModels.correction_number_mass_pairs(μp, μ) : ()
+    clamp = species ? map(devptr, AtmosphereModels.correction_number_fields(μp, μ)) : ()
+    max(length(mass), length(pairs), length(clamp)) <= 4 || error("BreezeHIP: at most four species, pairs and clamped number fields")
+    D = BzNegativeMoistureCorrection(Int32(species), Int32(vertical), Int32(length(mass)), Int32(length(pairs)), Int32(length(clamp)), Int32(0),
+                                     pad4(mass), pad4(map(p -> devptr(p[1]), pairs)), pad4(map(p -> devptr(p[2]), pairs)), pad4(clamp))
+    check(ccall((:bz_set_negative_moisture_correction, libbreeze_hip), Cint, (Ptr{Cvoid}, Ref{BzNegativeMoistureCorrection}), ctx, D),
+          "bz_set_negative_moisture_correction", ctx)
+    return nothing
+end
+
+"fix_negative_moisture!(model) as its own launch (update_state! and the whole steps of the library run it themselves)."
+function fix_negative_moisture!(model::HIPModel)
+    ctx = context(model)
+    check(ccall((:bz_fix_negative_moisture, libbreeze_hip), Cint, (Ptr{Cvoid}, Ref{BzState}), ctx, state(model)), "bz_fix_negative_moisture", ctx)
+    return nothing
+end
+
 "Field(Integral(field, dims = 3)) into `out`, a device array of (Nx + 2Hx) × (Ny + 2Hy) reals (interior positions are written)."
 function column_integral!(out, model::HIPAcousticModel, field)
     ctx = ccontext(model)
