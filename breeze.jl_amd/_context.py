@@ -92,6 +92,13 @@ class ContextOwner:
         self._check(self._lib.bz_graph_info(self._ctx, C.byref(en), C.byref(cap), C.byref(rep)), "bz_graph_info")
         return bool(en.value), cap.value, rep.value
 
+    def closure_marches(self):
+        """Whether the SmagorinskyLilly kernels of this context run as the z-marching LDS-tiled kernels (whole 64 x 8 tiles) rather than
+        cell per thread: the verdict of the library's one dispatch predicate (bz_closure_march_info).  Same bits either way."""
+        m = C.c_int32()
+        self._check(self._lib.bz_closure_march_info(self._ctx, C.byref(m)), "bz_closure_march_info")
+        return bool(m.value)
+
     def profile_enable(self, on=True):
         self._check(self._lib.bz_profile_enable(self._ctx, 1 if on else 0), "bz_profile_enable")
 

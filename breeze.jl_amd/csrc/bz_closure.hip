@@ -589,6 +589,31 @@ static ClosureFields closure_fields(bz_ctx *ctx, const bz_state *s)
     return F;
 }
 
+// THE dispatch rule of the closure kernels, anelastic and compressible alike: whole 64 x CL_TY tiles of a grid that is periodic in x and
+// periodic (or a y-slab) in y run the z-marching LDS-tiled kernels (k_smagorinsky_march, k_closure_march); walls, Flat y, ragged grids,
+// columns of fewer than four levels and BZ_NO_CLOSURE_MARCH=1 keep the cell-per-thread ones.  bz_closure_march_info reports it.
+constexpr int CL_TY = 8;
+static bool closure_march(const bz_ctx *ctx)
+{
+    const DevGrid &g = ctx->dg;
+    return !ctx->tune.no_closure_march && !g.flat_y && !g.bounded_x && !g.bounded_y && g.Nx % 64 == 0 && g.Ny % CL_TY == 0 && g.Nz >= 4 && g.Hx >= 1 &&
+           g.Hy >= 1 && g.Hz >= 2;
+}
+static int closure_march_chunk(const DevGrid &g)      // chunks of >= 16 levels, enough workgroups to fill the chip (every chunk restages three levels)
+{
+    const long long tiles = (long long)(g.Nx / 64) * (g.Ny / CL_TY);
+    int nch = (int)((CL_NCH + tiles - 1) / tiles);
+    if (nch > g.Nz / 16) nch = g.Nz / 16;
+    if (nch < 1) nch = 1;
+    return (g.Nz + nch - 1) / nch;
+}
+extern "C" int bz_closure_march_info(bz_ctx *ctx, int32_t *marches)
+{
+    if (!ctx || !marches) return BZ_ERR_INVALID;
+    *marches = (ctx->has_closure && closure_march(ctx)) ? 1 : 0;
+    return BZ_OK;
+}
+
 // compute_closure_fields!(model.closure_fields, model.closure, model): nu_e on the interior
 extern "C" int bz_compute_closure_fields(bz_ctx *ctx, const bz_state *s)
 {
@@ -602,17 +627,12 @@ extern "C" int bz_compute_closure_fields(bz_ctx *ctx, const bz_state *s)
     ClosureFields F = closure_fields(ctx, s);
     // y-slabs: one more row on each side (u, v, w, T, q^v carry Hy >= 2 exchanged rows there), so nu_e needs no exchange of its own
     F.jofs = ctx->slab_mode ? -1 : 0;
-    constexpr int CTY = 8;
-    const bool march = !ctx->tune.no_closure_march && !g.flat_y && !g.bounded_x && !g.bounded_y && g.Nx % 64 == 0 && g.Ny % CTY == 0 && g.Nz >= 4 &&
-                       g.Hx >= 1 && g.Hy >= 1 && g.Hz >= 2;
+    constexpr int CTY = CL_TY;
+    const bool march = closure_march(ctx);
     const double *delta2 = ctx->d_closure_ipi + (g.Nz + 2) + 1;
     const ExnerColumn ipi{ctx->d_closure_ipi + 1};
     if (march) {
-        const long long tiles = (long long)(g.Nx / 64) * (g.Ny / CTY);
-        int nch = (int)((CL_NCH + tiles - 1) / tiles);
-        if (nch > g.Nz / 16) nch = g.Nz / 16;
-        if (nch < 1) nch = 1;
-        const int kc = (g.Nz + nch - 1) / nch;
+        const int kc = closure_march_chunk(g);
         F.jofs = 0;
         hipLaunchKernelGGL((k_smagorinsky_march<CTY, ExnerColumn>), dim3(g.Nx / 64, g.Ny / CTY, (g.Nz + kc - 1) / kc), dim3(64, CTY), 0, ctx->stream, g, F,
                            s->T, qv, ipi, delta2, ctx->closure_nu, kc);
@@ -648,16 +668,10 @@ int bzi_apply_closure(bz_ctx *ctx, const bz_state *s, double *Gu, double *Gv, do
     const DevGrid &g = ctx->dg;
     ProfileScope ps(ctx, "closure_tendencies");
     // the z-marching LDS-tiled kernel on whole tiles of a periodic (or y-slab) grid; walls, Flat y and ragged grids keep the cell-per-thread one
-    constexpr int CTY = 8;
-    const bool march = !ctx->tune.no_closure_march && !g.flat_y && !g.bounded_x && !g.bounded_y && g.Nx % 64 == 0 && g.Ny % CTY == 0 && g.Nz >= 4 &&
-                       g.Hx >= 1 && g.Hy >= 1 && g.Hz >= 2;
+    constexpr int CTY = CL_TY;
+    const bool march = closure_march(ctx);
     if (march) {
-        // chunks of >= 16 levels, enough workgroups to fill the chip (every chunk restages three levels)
-        const long long tiles = (long long)(g.Nx / 64) * (g.Ny / CTY);
-        int nch = (int)((CL_NCH + tiles - 1) / tiles);
-        if (nch > g.Nz / 16) nch = g.Nz / 16;
-        if (nch < 1) nch = 1;
-        const int kc = (g.Nz + nch - 1) / nch;
+        const int kc = closure_march_chunk(g);
         hipLaunchKernelGGL((k_closure_march<CTY, RhoColumn>), dim3(g.Nx / 64, g.Ny / CTY, (g.Nz + kc - 1) / kc), dim3(64, CTY), 0, ctx->stream, g,
                            closure_fields(ctx, s), RhoColumn(), Gu, Gv, Gw, Gth, Gq, scale, kc);
     } else
@@ -676,21 +690,7 @@ int bzi_apply_closure(bz_ctx *ctx, const bz_state *s, double *Gu, double *Gv, do
 
 // ---- CompressibleDynamics + SplitExplicitTimeDiscretization ----------------------------------------------------------------------
 // whole 64 x 8 tiles of a periodic grid: the z-marching LDS-tiled kernels (the rule of the anelastic pair); ragged grids: cell per thread
-constexpr int CMP_CTY = 8;
-static bool cmp_closure_march(const bz_ctx *ctx)
-{
-    const DevGrid &g = ctx->dg;
-    return !ctx->tune.no_closure_march && !g.flat_y && !g.bounded_x && !g.bounded_y && g.Nx % 64 == 0 && g.Ny % CMP_CTY == 0 && g.Nz >= 4 && g.Hx >= 1 &&
-           g.Hy >= 1 && g.Hz >= 2;
-}
-static int closure_march_chunk(const DevGrid &g)      // chunks of >= 16 levels, enough workgroups to fill the chip (bzi_apply_closure)
-{
-    const long long tiles = (long long)(g.Nx / 64) * (g.Ny / CMP_CTY);
-    int nch = (int)((CL_NCH + tiles - 1) / tiles);
-    if (nch > g.Nz / 16) nch = g.Nz / 16;
-    if (nch < 1) nch = 1;
-    return (g.Nz + nch - 1) / nch;
-}
+constexpr int CMP_CTY = CL_TY;
 // compute_closure_fields! at the end of compute_auxiliary_variables! (update_atmosphere_model_state.jl:218): nu_e from the velocities, T and
 // the 3-D pressure the update_state! before it left (halos included), q^v = specific_humidity(model); then the halos of nu_e (periodic in
 // x / y, zero gradient in z), which the water-scalar kernel reads.  ScalarDiffusivity closures have no closure fields: only the halos of a
@@ -700,7 +700,7 @@ int bzi_cmp_closure_fields(bz_ctx *ctx, const bz_compressible_state *s)
     if (ctx->has_diffusivity) return bzi_diffusivity_halos(ctx);
     if (!ctx->has_closure) return BZ_OK;
     const DevGrid &g = ctx->dg;
-    const bool march = cmp_closure_march(ctx);
+    const bool march = closure_march(ctx);
     ProfileScope ps(ctx, march ? "smagorinsky_march" : "smagorinsky_viscosity");
     const double *qv = (g.microphysics == 1) ? g.qv_field : s->q;      // specific_humidity(model): the vapour fraction (Kessler: q is q^v)
     bz_state a;
@@ -726,7 +726,7 @@ int bzi_cmp_closure_slow(bz_ctx *ctx, const bz_compressible_state *s, const bz_c
     if (ctx->has_diffusivity) return bzi_cmp_diffusivity_slow(ctx, s, G);
     if (!ctx->has_closure) return BZ_OK;
     const DevGrid &g = ctx->dg;
-    const bool march = cmp_closure_march(ctx);
+    const bool march = closure_march(ctx);
     ProfileScope ps(ctx, march ? "closure_march" : "closure_tendencies");
     bz_state a;
     std::memset(&a, 0, sizeof(a));

@@ -883,6 +883,12 @@ typedef struct bz_smagorinsky_lilly {
 } bz_smagorinsky_lilly;
 int bz_set_closure(bz_ctx *ctx, const bz_smagorinsky_lilly *closure, double *eddy_viscosity);   /* NULL detaches */
 int bz_compute_closure_fields(bz_ctx *ctx, const bz_state *s);
+/* Which kernels the closure of this context launches (read-only; no reference counterpart).  *marches = 1: the z-marching LDS-tiled
+ * kernels (k_smagorinsky_march, k_closure_march) — SmagorinskyLilly attached, x periodic, y periodic or a y-slab, Nx a multiple of 64, the
+ * (local) Ny a multiple of 8, Nz >= 4, Hz >= 2, and BZ_NO_CLOSURE_MARCH unset when the context was created; 0: the cell-per-thread kernels
+ * (or no SmagorinskyLilly closure).  Both compute the same expressions in the same order: the choice changes no bit of nu_e or of a
+ * tendency.  It is the verdict of the one host predicate every launch site of csrc/bz_closure.hip asks. */
+int bz_closure_march_info(bz_ctx *ctx, int32_t *marches);
 
 /* ---- closure = ScalarDiffusivity(...) / VerticalScalarDiffusivity(...), explicit or vertically implicit (csrc/bz_diffusivity.hip) ----
  * Breeze's part is followed line by line: dynamic fluxes = rho_r at the flux location x Oceananigans' kinematic flux, with the

@@ -269,7 +269,9 @@ def test_marching_closure_kernels_on_whole_tiles(oracle, bz, moist, monkeypatch)
     """Round 5: on grids of whole 64 x 8 tiles the eddy viscosity and the five closure divergences run as z-marching LDS-tiled kernels
     (csrc/bz_closure.hip: k_smagorinsky_march, k_closure_march; the grids of the tests above are narrower than a tile and keep the
     cell-per-thread kernels).  Same expressions in the same order: nu_e and every tendency carry the BITS of the cell-per-thread kernels
-    (BZ_NO_CLOSURE_MARCH=1), and both match the oracle as above.  Three chunks of levels, so chunk seams are crossed."""
+    (BZ_NO_CLOSURE_MARCH=1), and both match the oracle as above.  Three chunks of 16 levels on a UNIFORM z and one tile in x: a chunk seam is
+    crossed, but every vertical metric reads the same number at every level, so a metric index that is off by a level passes here.
+    Stretched z, tile seams, ragged chunks and the XCD block order are in tests/test_closure_march.py."""
     size = (64, 16, 48)
 
     def run(no_march):

@@ -168,13 +168,26 @@ def test_rccl_transport_with_one_rank(bz, oracle, self_messages, monkeypatch):
     assert np.max(np.abs(got - want)) / np.max(np.abs(want)) < 1e-9
 
 
-@pytest.mark.parametrize("world,order", [(1, 5), (2, 5), (4, 5), (2, 9)])
-def test_bomex_physics_on_library_slabs_matches_the_oracle(bz, oracle, world, order):
+@pytest.mark.parametrize("world,order,size", [pytest.param(1, 5, (32, 32, 16), id="1-5"), pytest.param(2, 5, (32, 32, 16), id="2-5"),
+                                              pytest.param(4, 5, (32, 32, 16), id="4-5"), pytest.param(2, 9, (32, 32, 16), id="2-9"),
+                                              # rows of whole 64-cell tiles: local Ny = 32, 16, 8 rows are 4, 2, 1 tile rows, so every rank
+                                              # runs the z-marching closure kernels and their y-slab branch (below)
+                                              pytest.param(1, 5, (64, 32, 16), id="1-5-64x32x16"), pytest.param(2, 5, (64, 32, 16), id="2-5-64x32x16"),
+                                              pytest.param(4, 5, (64, 32, 16), id="4-5-64x32x16")])
+def test_bomex_physics_on_library_slabs_matches_the_oracle(bz, oracle, world, order, size, monkeypatch):
     """The physics list of BASELINE configs[2] — WENO5 + saturation adjustment + SmagorinskyLilly + Coriolis / geostrophic /
     subsidence / profile forcings + bottom fluxes — decomposed into y-slabs with the library-owned communicator (fused-RK tier with
     halo exchanges, horizontal averages all-reduced over the ranks, viscosity kernel covering the rows next to the slab), against
     the single-process oracle: 2e-9 of the field scale after three steps, the tolerance of the single-GPU test of the same physics
-    (tests/test_closure.py::test_bomex_stack_time_steps_match_oracle)."""
+    (tests/test_closure.py::test_bomex_stack_time_steps_match_oracle).
+
+    64 x 32 x 16: the slab branch of the z-marching closure kernels (csrc/bz_closure.hip: bz_compute_closure_fields, `if (ctx->slab_mode)`):
+    k_smagorinsky_march covers the slab's own rows and two one-row launches of the cell-per-thread kernel the rows -1 and Ny, which
+    k_closure_march reads unwrapped.  With four ranks a slab is a single tile row whose two outer rows both come from the neighbours.  Every
+    rank reports the march (closure_marches()); the prognostic fields, and nu_e on rows -1 .. Ny of every rank, carry the bits of the same run
+    with BZ_NO_CLOSURE_MARCH=1, whose one cell-per-thread launch covers the Ny + 2 rows with the same expressions.  (A profile record is one
+    per bracketed group, however many kernels it covers, so the profile counts one `smagorinsky_viscosity` per evaluation in both runs: the
+    rows themselves are the evidence that the edge launches ran — a row never written keeps the zeros of its allocation.)"""
     import sys
     import os
     import torch
@@ -183,7 +196,6 @@ def test_bomex_physics_on_library_slabs_matches_the_oracle(bz, oracle, world, or
     from oracle.closure import SmagorinskyLilly
     from test_closure import _turbulent_ic
     from test_forcings import EXTENT as FEXT, _hip_forcing_kwargs, _oracle_forcings
-    size = (32, 32, 16)
     halo = (3, 3, 3) if order == 5 else (5, 5, 5)      # order 9 (examples/bomex.jl:204): the operator-by-operator distributed step
     og = oracle.Grid(size, x=FEXT[0], y=FEXT[1], z=FEXT[2], halo=halo)
     om = oracle.OracleModel(og, surface_pressure=101500.0, potential_temperature=299.1, microphysics="SaturationAdjustment",
@@ -193,35 +205,41 @@ def test_bomex_physics_on_library_slabs_matches_the_oracle(bz, oracle, world, or
     for _ in range(3):
         om.time_step(3.0)
     G = bz.RectilinearGrid(size, x=FEXT[0], y=FEXT[1], z=FEXT[2], halo=halo)
-    group = "local:" + uuid.uuid4().hex
     Ny = size[1] // world
-    models, errors = [None] * world, []
 
-    def run(rank):
-        try:
-            torch.cuda.set_device(0)
-            with torch.cuda.stream(torch.cuda.Stream()):
-                m = bz_dist.LibrarySlabAtmosphereModel(G, rank, world, transport=group, surface_pressure=101500.0,
-                                                       potential_temperature=299.1, advection=bz.WENO(order=order), device="cuda:0",
-                                                       closure=bz.SmagorinskyLilly(),
-                                                       microphysics=bz.SaturationAdjustment(equilibrium=bz.WarmPhaseEquilibrium()),
-                                                       **_hip_forcing_kwargs(bz))
-                sl = slice(rank * Ny, (rank + 1) * Ny)
-                m.set(θ=ic["theta"][:, sl, :], qᵗ=ic["qt"][:, sl, :], u=ic["u"][:, sl, :], v=ic["v"][:, sl, :])
-                for _ in range(3):
-                    m.time_step(3.0)
-                m.synchronize()
-            models[rank] = m
-        except Exception as e:      # noqa: BLE001
-            import traceback
-            errors.append((rank, repr(e), traceback.format_exc()))
+    def run_ranks():
+        group = "local:" + uuid.uuid4().hex
+        models, errors = [None] * world, []
 
-    threads = [threading.Thread(target=run, args=(r,)) for r in range(world)]
-    for t in threads:
-        t.start()
-    for t in threads:
-        t.join()
-    assert not errors, errors
+        def run(rank):
+            try:
+                torch.cuda.set_device(0)
+                with torch.cuda.stream(torch.cuda.Stream()):
+                    m = bz_dist.LibrarySlabAtmosphereModel(G, rank, world, transport=group, surface_pressure=101500.0,
+                                                           potential_temperature=299.1, advection=bz.WENO(order=order), device="cuda:0",
+                                                           closure=bz.SmagorinskyLilly(),
+                                                           microphysics=bz.SaturationAdjustment(equilibrium=bz.WarmPhaseEquilibrium()),
+                                                           **_hip_forcing_kwargs(bz))
+                    sl = slice(rank * Ny, (rank + 1) * Ny)
+                    m.set(θ=ic["theta"][:, sl, :], qᵗ=ic["qt"][:, sl, :], u=ic["u"][:, sl, :], v=ic["v"][:, sl, :])
+                    for _ in range(3):
+                        m.time_step(3.0)
+                    m.synchronize()
+                models[rank] = m
+            except Exception as e:      # noqa: BLE001
+                import traceback
+                errors.append((rank, repr(e), traceback.format_exc()))
+
+        threads = [threading.Thread(target=run, args=(r,)) for r in range(world)]
+        for t in threads:
+            t.start()
+        for t in threads:
+            t.join()
+        assert not errors, errors
+        return models
+
+    monkeypatch.delenv("BZ_NO_CLOSURE_MARCH", raising=False)
+    models = run_ranks()
     mom = max(np.abs(og.interior(getattr(om, n), zface=(n == "rw"))).max() for n in ("ru", "rv", "rw"))
     for name in ("ru", "rv", "rw", "rtheta", "rq", "T"):
         got = np.concatenate([FIELDS[name](m).interior_cpu() for m in models], axis=1)
@@ -230,6 +248,24 @@ def test_bomex_physics_on_library_slabs_matches_the_oracle(bz, oracle, world, or
         assert np.abs(got - want).max() / scale < (2e-9 if order == 5 else 2e-8), (name, np.abs(got - want).max() / scale)
     ql = np.concatenate([m.microphysical_fields["qˡ"].interior_cpu() for m in models], axis=1)
     assert np.abs(ql - og.interior(om.ql)).max() < 1e-9
+    assert [m.closure_marches() for m in models] == [size[0] % 64 == 0] * world
+    if size[0] % 64:
+        return
+    monkeypatch.setenv("BZ_NO_CLOSURE_MARCH", "1")          # read when a context is created
+    try:
+        plain = run_ranks()
+    finally:
+        monkeypatch.delenv("BZ_NO_CLOSURE_MARCH", raising=False)
+    assert not any(m.closure_marches() for m in plain)
+    for name in ("ru", "rv", "rw", "rtheta", "rq"):
+        got = np.concatenate([FIELDS[name](m).interior_cpu() for m in models], axis=1)
+        assert np.array_equal(got, np.concatenate([FIELDS[name](m).interior_cpu() for m in plain], axis=1)), name
+    H = halo[0]
+    for r, (m, p) in enumerate(zip(models, plain)):
+        rows = slice(H - 1, H + Ny + 1)                         # rows -1 .. Ny of the slab
+        nu, nu_plain = (x.closure_fields["νₑ"].cpu()[H:H + size[2], rows, H:H + size[0]] for x in (m, p))
+        assert np.array_equal(nu, nu_plain), r
+        assert nu[:, 0].max() > 0 and nu[:, -1].max() > 0, r     # the rows beyond the slab were written
 
 
 @pytest.mark.parametrize("world", [1, 2])
