@@ -105,6 +105,17 @@ class bz_surface_layer(C.Structure):
                  ("filter_stage_mask", C.c_int32), ("reserved", C.c_int32)])
 
 
+class bz_compressible_surface_flux(C.Structure):
+    _fields_ = [("enabled", C.c_int32), ("reserved", C.c_int32), ("coefficient", C.c_double), ("gustiness", C.c_double),
+                ("surface_temperature", C.c_double), ("surface_temperature_field", _dp)]
+
+
+class bz_compressible_surface_fluxes(C.Structure):
+    _fields_ = ([("drag", bz_compressible_surface_flux), ("heat", bz_compressible_surface_flux), ("vapor", bz_compressible_surface_flux)] +
+                [(n, C.c_double) for n in ("surface_pressure", "standard_pressure", "liquid_latent_heat", "liquid_heat_capacity",
+                                           "energy_reference_temperature", "triple_point_temperature", "triple_point_pressure")])
+
+
 class bz_tracer_fields(C.Structure):
     _fields_ = [("density", C.c_void_p), ("specific", C.c_void_p), ("U0", C.c_void_p), ("G", C.c_void_p)]
 
@@ -332,6 +343,8 @@ SYMBOLS = {
     "bz_surface_layer_update": (C.c_int, [_ctx, _sp, C.c_double]),
     "bz_surface_layer_get_filtered": (C.c_int, [_ctx, C.c_int, _dp]),
     "bz_surface_layer_set_filtered": (C.c_int, [_ctx, C.c_int, _dp]),
+    "bz_set_compressible_surface_fluxes": (C.c_int, [_ctx, C.POINTER(bz_compressible_surface_fluxes)]),
+    "bz_compressible_compute_flux_bc_tendencies": (C.c_int, [_ctx, _csp, _cpp]),
     "bz_set_forcings": (C.c_int, [_ctx, C.POINTER(bz_column_forcings)]),
     "bz_set_relaxation": (C.c_int, [_ctx, C.POINTER(bz_column_relaxation)]),
     "bz_set_field_forcing": (C.c_int, [_ctx, C.c_void_p, C.c_int]),

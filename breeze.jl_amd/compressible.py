@@ -360,7 +360,11 @@ class CompressibleAtmosphereModel(_context.ContextOwner):
     or VerticalScalarDiffusivity(ν, κ) with the explicit time discretisation (benchmarking/run_benchmarks.jl:111-119;
     validation/DCMIP2016_TC/dcmip2016_tc.jl:277-292) on single-GPU models that are periodic in x and y; microphysics = SaturationAdjustment,
     DCMIP2016KesslerMicrophysics or — on those single-GPU periodic models — InstantaneousPrecipitation (src/Microphysics/instantaneous_precipitation.jl):
-    microphysical_fields = {"qᵛ": the specific-moisture field, "precipitation_rate": a centre Field}, the once-per-step rain-out closes time_step."""
+    microphysical_fields = {"qᵛ": the specific-moisture field, "precipitation_rate": a centre Field}, the once-per-step rain-out closes time_step.
+    boundary_conditions = {"ρu": BulkDrag(...), "ρv": ..., "ρθ" | "ρe": BulkSensibleHeatFlux(...), "ρqᵛ" | "ρqᵉ" | "ρqᵗ": BulkVaporFlux(...)} — bottom
+    bulk surface fluxes with a numeric coefficient, a gustiness and a surface temperature that is a number, an (Ny, Nx) array or T₀(x, y), on the
+    single-GPU model that is periodic in x and y (validation/DCMIP2016_TC/dcmip2016_tc.jl:293-311): every stage adds them after its slow tendencies
+    (compute_flux_bc_tendencies_); on a walled grid the keyword carries the open lateral sides (NormalFlowBoundaryCondition)."""
 
     def __init__(self, grid, dynamics, advection=None, thermodynamic_constants=None, temperature_solver=None,
                  closure=None, coriolis=None, microphysics=None, forcing=None, device="cuda:0", substep_floattype=None,
@@ -382,8 +386,11 @@ class CompressibleAtmosphereModel(_context.ContextOwner):
         if not self.lateral_walls and grid.topology not in ((Periodic, Periodic, Bounded), (Periodic, Flat, Bounded)):
             raise NotImplementedError("the HIP path implements topology (Periodic, Periodic, Bounded) and (Periodic, Flat, Bounded)")
         self.boundary_conditions = boundary_conditions or {}
-        if self.boundary_conditions and not self.lateral_walls:
-            raise NotImplementedError("boundary_conditions: the open lateral boundaries of the acoustic substep loop on a Bounded x / y")
+        # bottom bulk surface fluxes (BulkDrag, BulkSensibleHeatFlux, BulkVaporFlux with a numeric coefficient) on the single-device model that
+        # is periodic in x and y; a lateral condition there, and every other flux condition, fails by name (forcings.py)
+        from .forcings import compressible_surface_flux_conditions
+        self._surface_fluxes = compressible_surface_flux_conditions(self.boundary_conditions, grid, type(self) is CompressibleAtmosphereModel,
+                                                                    self.lateral_walls)
         if grid.topology[1] == Flat and not (isinstance(advection, WENO) and advection.bounds is None):
             raise NotImplementedError("(Periodic, Flat, Bounded): the WENO(order = 5 | 7 | 9) model is implemented")
         if isinstance(advection, WENO) and advection.order != 5:      # examples/splitting_supercell.jl:279 uses WENO(order = 9)
@@ -505,6 +512,10 @@ class CompressibleAtmosphereModel(_context.ContextOwner):
         _context.attach_relaxation(self, self._relaxation, "LiquidIcePotentialTemperature")
         _context.attach_field_forcing(self, self._field_forcing, "LiquidIcePotentialTemperature")
         _context.attach_closure(self, fld)      # (explicit only: the vertically implicit discretisation was refused above)
+        if self._surface_fluxes:      # bulk surface fluxes: a stage adds them after its slow tendencies (bz_set_compressible_surface_fluxes)
+            from .forcings import materialize_compressible_surface_fluxes
+            Sf, self._surface_flux_arrays = materialize_compressible_surface_fluxes(grid, self._surface_fluxes, dynamics, c, T)
+            self._check(lib.bz_set_compressible_surface_fluxes(self._ctx, C.byref(Sf)), "bz_set_compressible_surface_fluxes")
         if self.lateral_walls:      # is_active_open_bc of the four sides (acoustic_substepping.jl:1339-1361)
             bu, bv = self.boundary_conditions.get("ρu"), self.boundary_conditions.get("ρv")
             sides = [is_active_open_bc(getattr(b, k, None)) and grid.topology[d] == Bounded
@@ -589,6 +600,20 @@ def seed_time_averaged_velocities_(model):
 def compute_slow_tendencies_(model):
     model._check(model._lib.bz_compute_slow_tendencies(model._ctx, C.byref(model._state), C.byref(model._G)),
                  "bz_compute_slow_tendencies")
+
+
+def compute_flux_bc_tendencies_(model):
+    """compute_flux_bc_tendencies!(model) of the compressible model (acoustic_runge_kutta_3.jl:190-193): the attached bulk surface fluxes are
+    ADDED to the first level of Gρu, Gρv, Gρθ and the moisture tendency — after compute_slow_tendencies_, which overwrites the first three.
+    acoustic_rk3_substep_ and time_step do this themselves, once per stage."""
+    model._check(model._lib.bz_compressible_compute_flux_bc_tendencies(model._ctx, C.byref(model._state), C.byref(model._G)),
+                 "bz_compressible_compute_flux_bc_tendencies")
+
+
+def detach_surface_fluxes_(model):
+    """bz_set_compressible_surface_fluxes(NULL): the model steps on as one built without bulk surface fluxes."""
+    model._check(model._lib.bz_set_compressible_surface_fluxes(model._ctx, None), "bz_set_compressible_surface_fluxes")
+    model._surface_fluxes = {}
 
 
 def acoustic_rk3_substep_loop_(model, Δt, β):

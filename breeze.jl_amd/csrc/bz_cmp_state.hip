@@ -290,6 +290,7 @@ void bzi_compressible_teardown(bz_ctx *ctx)
     if (ctx->d_Gp_rv) (void)hipFree(ctx->d_Gp_rv);
     ctx->d_Gp_ru = ctx->d_Gp_rv = nullptr;
     ctx->d_Clin = ctx->d_tfac_ac = ctx->d_up2 = ctx->d_vp2 = ctx->d_sponge = nullptr;
+    bzi_cmp_surface_flux_teardown(ctx);
 }
 
 // update_state! with the linearisation refresh of the next stage optionally folded in

@@ -97,6 +97,8 @@ extern "C" int bz_acoustic_rk3_substep(bz_ctx *ctx, const bz_compressible_state 
     if (rc) return rc;
     rc = bz_compute_slow_tendencies(ctx, s, G);
     if (rc) return rc;
+    // compute_flux_bc_tendencies! (acoustic_runge_kutta_3.jl:190-193): after the slow tendencies, which overwrite G, and before the loop
+    if ((rc = bzi_cmp_surface_fluxes(ctx, s, G))) return rc;
     rc = bzi_acoustic_substep_loop(ctx, s, U0, G, sub, dt, beta, true, true);
     if (rc || !ctx->dg.bounded_y) return rc;
     return fill_walled_averages(ctx, sub);
@@ -196,6 +198,10 @@ static int compressible_step_body(bz_ctx *ctx, const bz_compressible_state *s, c
         const bz_compressible_state *s_next = !rotate ? s : (st == 2 ? s_step : &sB);
         rc = bz_compute_slow_tendencies(ctx, s, G);
         if (rc) return rc;
+        // compute_flux_bc_tendencies! (acoustic_runge_kutta_3.jl:190-193) on both stage paths: G_rho_u, G_rho_v, G_rho_theta are complete
+        // before the stage's first sweeps fold the gradient of p^L into them, and G_rho_q — left by the previous update_state! (the diagnostics
+        // u, v, theta, q of `s` do not rotate) — before the stage epilogue forms U0_rho_q + dt G_rho_q
+        if ((rc = bzi_cmp_surface_fluxes(ctx, s, G))) return rc;
         if (!fuse_end) {
             rc = bzi_acoustic_substep_loop(ctx, s, U0, G, sub, dt, betas[st], true, false);
             if (rc) return rc;

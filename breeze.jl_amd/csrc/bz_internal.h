@@ -631,6 +631,11 @@ struct bz_ctx {
     bz_surface_layer sl;              // (the host pointers inside are not kept: the arrays were copied into d_sl)
     double *d_sl = nullptr;           // [T0 drag, T0 heat, T0 vapour, u^, v^, theta_v^, theta^, q^] (Ny x Nx) each
     bool sl_initialized = false;
+    // the same three conditions on a compressible context (bz_set_compressible_surface_fluxes, bz_cmp_surface_flux.hip): constant coefficients,
+    // a surface temperature per surface cell; a stage adds them after its slow tendencies
+    bool cmp_sf_on = false;
+    bz_compressible_surface_fluxes cmp_sf;      // (the host pointers inside are not kept: the arrays were copied into d_cmp_sf_T0)
+    double *d_cmp_sf_T0 = nullptr;    // [T0 drag, T0 heat, T0 vapour] (Ny x Nx) each
     // user tracers (bz_set_tracers, bz_tracers.hip)
     int n_tracers = 0;
     bz_tracer_fields tracers[BZ_MAX_TRACERS];
@@ -856,6 +861,9 @@ int bzi_tendencies_fused_rk(bz_ctx *ctx, const bz_state *s, const bz_prognostic 
 int bzi_create(bz_ctx **out, const bz_grid *grid, const bz_constants *constants, const bz_reference_state *ref,
                int weno_order, int y_nranks, int y_rank, bool slab_mode, bool compressible = false);
 void bzi_compressible_teardown(bz_ctx *ctx);
+// bz_cmp_surface_flux.hip: compute_flux_bc_tendencies! of a compressible context (a no-op without an attached set)
+int bzi_cmp_surface_fluxes(bz_ctx *ctx, const bz_compressible_state *s, const bz_compressible_prognostic *G);
+void bzi_cmp_surface_flux_teardown(bz_ctx *ctx);
 void bzi_balance_teardown(bz_ctx *ctx);
 int bzi_refresh_reference_columns(bz_ctx *ctx, const double *density, const double *pressure);      // bz_context.hip: the columns bzi_create derives from the reference
 bool bzi_k6_stored_ok(const bz_ctx *ctx);

@@ -37,6 +37,7 @@ static bool moisture_sources(const bz_ctx *ctx)
 {
     return ctx->tune.no_dry_shortcut || ctx->dg.microphysics != 0 || ctx->has_bulk || ctx->has_relaxation || ctx->field_forcing != nullptr ||
            (ctx->has_forcings && (ctx->forcing_flux_q != 0.0 || (ctx->forcing_static_mask & 8) || (ctx->forcing_subsidence_mask & 8))) ||
+           (ctx->cmp_sf_on && ctx->cmp_sf.vapor.enabled) ||      // BulkVaporFlux on a compressible context: evaporation into a dry model
            (ctx->slab_mode && !ctx->comm);      // slabs driven from the host: the library cannot ask the other ranks, so nothing is skipped
 }
 

@@ -182,7 +182,9 @@ class FilteredSurfaceVelocities:
 
 
 def _coefficient(c):
-    return c if isinstance(c, PolynomialCoefficient) else float(c)
+    # (a function-valued coefficient — user code like the WindDependentDrag of validation/DCMIP2016_TC/dcmip2016_tc.jl — is kept as given: the
+    # model constructors refuse it by name)
+    return c if isinstance(c, PolynomialCoefficient) or callable(c) else float(c)
 
 
 def _surface_temperature(T0):
@@ -231,7 +233,8 @@ class FieldBoundaryConditions:
         """bottom: the surface flux conditions of the anelastic model; west / east / south / north: NormalFlowBoundaryCondition on the
         wall-normal momentum of a compressible model with a Bounded x / y (the open lateral boundaries of the acoustic substep loop)."""
         if top is not None:
-            raise NotImplementedError("only bottom flux boundary conditions are implemented")
+            raise NotImplementedError("only bottom flux boundary conditions are implemented (bulk surface fluxes and the constant fluxes are "
+                                      "bottom conditions; a top flux condition is not built)")
         self.bottom = bottom
         self.west, self.east, self.south, self.north = west, east, south, north
 
@@ -599,3 +602,103 @@ def _same_condition(a, b):
     same_T0 = Ta is Tb or (not callable(Ta) and not callable(Tb) and np.array_equal(Ta, Tb))
     same_C = a.coefficient is b.coefficient or (not isinstance(a.coefficient, PolynomialCoefficient) and a.coefficient == b.coefficient)
     return bool(same_T0 and same_C and a.gustiness == b.gustiness and a.filtered_velocities is b.filtered_velocities)
+
+
+# ---- bulk surface fluxes on CompressibleDynamics: bz_set_compressible_surface_fluxes -------------------------------------------------------
+_LATERAL_PINNED = "boundary_conditions: the open lateral boundaries of the acoustic substep loop on a Bounded x / y"
+
+
+def compressible_surface_flux_conditions(boundary_conditions, grid, single_device, lateral_walls):
+    """The `boundary_conditions` keyword of CompressibleAtmosphereModel, checked without a GPU -> {"drag" | "heat" | "vapor": condition}
+    (empty: nothing but the open lateral conditions of a walled model).  Bottom conditions of the three bulk types with a numeric
+    coefficient run on the single-device model that is periodic in x and y; everything else fails by name ("bulk surface fluxes").
+    Keys as materialize_bulk_fluxes: BulkDrag on ρu / ρv (one for both), BulkSensibleHeatFlux on ρθ — or ρe, moved to ρθ with the
+    potential-temperature difference (BoundaryConditions.jl:218-227) — and BulkVaporFlux on the moisture density."""
+    from .compressible import NormalFlowBoundaryCondition
+    from .grids import Flat
+    entries = [(_key(name), bcs) for name, bcs in (boundary_conditions or {}).items()]
+    laterals = [side for _, bcs in entries if isinstance(bcs, FieldBoundaryConditions)
+                for side in (bcs.west, bcs.east, bcs.south, bcs.north) if side is not None]
+    if not lateral_walls:
+        if any(isinstance(side, NormalFlowBoundaryCondition) for side in laterals):
+            raise NotImplementedError(_LATERAL_PINNED)
+        if laterals:
+            raise NotImplementedError("boundary_conditions: bulk surface fluxes are bottom conditions; a lateral flux condition is not implemented")
+    seen = {}
+    for k, bcs in entries:
+        bottom = bcs.bottom if isinstance(bcs, FieldBoundaryConditions) else bcs
+        if bottom is None:
+            continue
+        cond = bottom.condition if isinstance(bottom, FluxBoundaryCondition) else bottom
+        if not isinstance(cond, (BulkDrag, BulkSensibleHeatFlux, BulkVaporFlux)):
+            raise NotImplementedError(f"boundary_conditions[{k!r}]: CompressibleDynamics carries bulk surface fluxes (BulkDrag, BulkSensibleHeatFlux, "
+                                      f"BulkVaporFlux) at the bottom; a plain FluxBoundaryCondition ({type(cond).__name__}) is not implemented")
+        what = type(cond).__name__
+        if isinstance(cond.coefficient, PolynomialCoefficient):
+            raise NotImplementedError(f"{what}(coefficient = PolynomialCoefficient): bulk surface fluxes on CompressibleDynamics take a numeric coefficient")
+        if callable(cond.coefficient):
+            raise NotImplementedError(f"{what}: a function-valued coefficient is user code; bulk surface fluxes on CompressibleDynamics take a "
+                                      "numeric coefficient")
+        if cond.filtered_velocities is not None:
+            raise NotImplementedError(f"{what}(filtered_velocities = FilteredSurfaceVelocities): bulk surface fluxes on CompressibleDynamics read "
+                                      "the unfiltered first-level fields")
+        if isinstance(cond, BulkDrag):
+            if k not in ("ρu", "ρv"):
+                raise ValueError("BulkDrag is a momentum boundary condition (ρu, ρv)")
+            slot = "drag"
+        elif isinstance(cond, BulkSensibleHeatFlux):
+            if k not in ("ρθ", "ρe"):
+                raise ValueError("BulkSensibleHeatFlux belongs on ρθ (or ρe)")
+            slot = "heat"
+        else:
+            if k not in ("ρqe", "ρqv", "ρqt"):
+                raise ValueError("BulkVaporFlux belongs on the moisture density")
+            slot = "vapor"
+        if slot in seen:
+            if slot == "drag" and _same_condition(seen[slot], cond):
+                continue
+            if slot == "heat":      # validate_thermodynamic_bcs (BoundaryConditions.jl:200-209)
+                raise ValueError("Cannot specify boundary conditions on both ρθ and ρe")
+            raise NotImplementedError("ρu and ρv share one BulkDrag" if slot == "drag" else "one BulkVaporFlux per model")
+        seen[slot] = cond
+    if not seen:
+        return seen
+    if lateral_walls:
+        raise NotImplementedError("boundary_conditions: bulk surface fluxes are not implemented on a compressible model between walls (Bounded x / Bounded y)")
+    if Flat in grid.topology:
+        raise NotImplementedError("boundary_conditions: bulk surface fluxes are not implemented on a compressible model with a Flat y")
+    if not single_device:
+        raise NotImplementedError("boundary_conditions: bulk surface fluxes are not implemented on y-slab (distributed) compressible models")
+    if "drag" in seen and seen["drag"].surface_temperature is None:
+        # default_drag_surface_temperature(::CompressibleDynamics, ...) (compressible_dynamics.jl:520-525) has no profile to draw from: it throws
+        raise ValueError("BulkDrag under CompressibleDynamics requires `surface_temperature` to be provided explicitly: there is no default "
+                         "surface temperature for compressible dynamics (no reference profile to draw from)")
+    for cond in seen.values():
+        T0 = cond.surface_temperature
+        if not callable(T0) and np.ndim(T0) > 0 and np.shape(T0) != (grid.Ny, grid.Nx):
+            raise ValueError(f"surface_temperature has shape {np.shape(T0)}, expected {(grid.Ny, grid.Nx)}")
+    return seen
+
+
+def materialize_compressible_surface_fluxes(grid, conditions, dynamics, constants, T=None):
+    """{"drag" | "heat" | "vapor": condition} (compressible_surface_flux_conditions) -> (bz_compressible_surface_fluxes, keepalive arrays).
+    p₀ is the dynamics' surface_pressure; the surface temperature is a number, an (Ny, Nx) array or T₀(x) / T₀(x, y)."""
+    T = T or _lib.types(8)
+    S, keep = T.bz_compressible_surface_fluxes(), []
+    for slot, cond in conditions.items():
+        F = getattr(S, slot)
+        F.enabled, F.coefficient, F.gustiness = 1, cond.coefficient, cond.gustiness
+        T0 = cond.surface_temperature
+        if callable(T0) or np.ndim(T0) > 0:
+            a = np.ascontiguousarray(surface_temperature_field(grid, T0), dtype=T.np_real)
+            keep.append(a)
+            F.surface_temperature_field = a.ctypes.data_as(C.POINTER(T.real))
+            F.surface_temperature = float(a.flat[0])
+        else:
+            F.surface_temperature = float(T0)
+    S.surface_pressure, S.standard_pressure = dynamics.surface_pressure, dynamics.standard_pressure
+    c = constants
+    S.liquid_latent_heat, S.liquid_heat_capacity = c.liquid_reference_latent_heat, c.liquid_heat_capacity
+    S.energy_reference_temperature = c.energy_reference_temperature
+    S.triple_point_temperature, S.triple_point_pressure = c.triple_point_temperature, c.triple_point_pressure
+    return S, keep

@@ -827,6 +827,38 @@ int bz_surface_layer_update(bz_ctx *ctx, const bz_state *s, double epsilon);
 int bz_surface_layer_get_filtered(bz_ctx *ctx, int which, double *host);
 int bz_surface_layer_set_filtered(bz_ctx *ctx, int which, const double *host);
 
+/* ---- bulk surface fluxes on CompressibleDynamics (csrc/bz_cmp_surface_flux.hip; validation/DCMIP2016_TC/dcmip2016_tc.jl:293-311) ----
+ * The three bottom conditions of bz_bulk_surface_fluxes above — same formulas, same sources — with a constant coefficient, a gustiness
+ * and, per condition, a surface temperature that is a number or a HOST (Ny x Nx) centre array (row j, column i; copied by the call):
+ *   rho0 = p0 / (R^d T0), theta0 = T0 / (p0/p_st)^(R^d/c_pd), q^v+ = p^v+(T0) / (rho0 R^v T0) over a planar liquid surface, per cell;
+ *   the drag at an x or y face reads the centre array at its own index.  p0 is the dynamics' surface_pressure.  p^v+ is the
+ *   Clausius-Clapeyron form of the constants below; on a context with DCMIP2016 Kessler microphysics, whose constants carry a
+ *   TetensFormula, it is that formula with the attached scheme's parameters (src/Thermodynamics/tetens_formula.jl:110-117).
+ * Fields read: the first level of the state's u, v, theta and of q^v — the diagnosed vapour fraction while a SaturationAdjustment is
+ * attached, else the specific prognostic moisture s->q (InstantaneousPrecipitation, Kessler, no microphysics).  Neighbours of u, v by
+ * periodic wrap indexing.  Fluxes enter where the reference adds them (src/TimeSteppers/acoustic_runge_kutta_3.jl:187-196): after the slow
+ * tendencies of a stage and before its substep loop, once per stage, in bz_acoustic_rk3_substep and in every stage of
+ * bz_time_step_compressible — G_rho_u, G_rho_v, G_rho_theta and the moisture tendency the previous update_state! left take J / dz_1 at the
+ * first level, by ONE launch over the Nx x Ny surface (no allocation, no synchronisation; captured steps replay it).  While a vapour flux
+ * is attached the dry shortcut of the step (bz_moisture.hip) is off: evaporation into a dry model is a moisture source.
+ * bz_compressible_compute_flux_bc_tendencies is compute_flux_bc_tendencies!(model) alone, for per-operator drivers: it ADDS to G.
+ * BZ_ERR_UNSUPPORTED (bz_last_error names the function and the reason): anelastic and kinematic contexts, y-slab contexts, a Bounded x or
+ * y, a Flat y.  PolynomialCoefficient and FilteredSurfaceVelocities are not built on CompressibleDynamics (bz_set_surface_layer refuses). */
+typedef struct bz_compressible_surface_flux {
+    int32_t enabled, reserved;
+    double coefficient, gustiness;
+    double surface_temperature;              /* used when the field is NULL */
+    const double *surface_temperature_field; /* HOST (Ny x Nx), row j column i; copied by the call */
+} bz_compressible_surface_flux;
+typedef struct bz_compressible_surface_fluxes {
+    bz_compressible_surface_flux drag, heat, vapor;
+    double surface_pressure, standard_pressure;
+    /* liquid CondensedPhase + triple point of ThermodynamicConstants, for q^v+ of the vapour flux */
+    double liquid_latent_heat, liquid_heat_capacity, energy_reference_temperature, triple_point_temperature, triple_point_pressure;
+} bz_compressible_surface_fluxes;
+int bz_set_compressible_surface_fluxes(bz_ctx *ctx, const bz_compressible_surface_fluxes *fluxes);      /* NULL detaches */
+int bz_compressible_compute_flux_bc_tendencies(bz_ctx *ctx, const bz_compressible_state *s, const bz_compressible_prognostic *G);
+
 /* ---- user tracers of the anelastic model: AtmosphereModel(grid; tracers = (:a, :b)) ----
  * density = model.tracers.c (prognostic rho c), specific = c = rho c / rho_r (the reference converts in place around the tendency
  * evaluation, src/AtmosphereModels/update_atmosphere_model_state.jl:43,65,88-112; here it is a separate centre array), U0 / G the
