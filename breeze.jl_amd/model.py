@@ -125,6 +125,27 @@ def _split_advection(advection, tracer_names):
     return base, dict(bounded, lower=lo_hi[0], upper=lo_hi[1]), scalar_order, unnamed_differ
 
 
+def _check_bounded_clients(advection, tracer_names, species_names):
+    """The library limits scalars by class, one mask bit each for the moisture, the microphysical species and the tracers
+    (csrc/bz_bounded.hip: bz_set_bounds_preserving_advection): bounds on some scalars of a class would limit all of them, and bounds on a
+    species the model's microphysics does not carry would limit nothing.  Both are refused here, by name, before `_split_advection`
+    folds the names into the three flags.  `species_names`: the prognostic species of the model (`_SPECIES_KEYS` with Kessler, else none)."""
+    if not isinstance(advection, dict):
+        return
+    limited = {str(k).lstrip(":") for k, s in advection.items() if getattr(s, "bounds", None) is not None} - {"momentum", "scalars"}
+    for key in _SPECIES_KEYS:
+        if key in limited and key not in species_names:
+            raise ValueError(f"advection key {key!r} names no prognostic scalar of this model: its microphysics has no such species, "
+                             "and the scalar's bounds would be ignored")
+    unnamed = [k for k in species_names if k not in limited] if limited & set(species_names) else []
+    tracers_limited = [t for t in tracer_names if t in limited or "ρ" + t in limited]
+    if tracers_limited:
+        unnamed += [t for t in tracer_names if t not in tracers_limited]
+    if unnamed:
+        raise NotImplementedError("bounds-preserving advection is switched on for all microphysical species and for all tracers at once: "
+                                  f"give {unnamed} the same WENO(bounds = ...) too (or none of their class)")
+
+
 class AnelasticDynamics:
     """AnelasticDynamics(reference_state)  (src/AnelasticEquations/anelastic_dynamics.jl:5-8)."""
 
@@ -365,6 +386,7 @@ class AtmosphereModel(_context.ContextOwner):
             _context.check_kessler_constants(thermodynamic_constants)
         _named = set(str(k).lstrip(":") for k in advection) if isinstance(advection, dict) else set()
         _tracer_names = tuple(str(n).lstrip(":") for n in ((tracers,) if isinstance(tracers, str) else tracers))
+        _check_bounded_clients(advection, _tracer_names, _SPECIES_KEYS if self._kessler else ())
         advection, self._bounded_advection, self._scalar_order, _unnamed_differ = _split_advection(advection, _tracer_names)
         if _unnamed_differ:
             # scalar_advection was a NamedTuple: every scalar of the model it does not name takes Centered(order = 2) in the reference

@@ -8,7 +8,13 @@ the cell volume; the reference has no test that asserts a value of this operator
   * an independent numpy restatement of the 1-D formula agrees with the C oracle;
   * under a stirring bubble the overshoot of a sharp blob above its upper bound shrinks by more than 10x against plain WENO-5
     (the operator limits only a cell's own reconstructions, so it is not strictly bounds-preserving — see that test);
-and the device kernel (gpu) matches the oracle: tendencies 1e-12, three steps 1e-9, same overshoot suppression on the device."""
+and the device kernel (gpu) matches the oracle: tendencies 1e-12, three steps 1e-9, same overshoot suppression on the device.
+
+Pinned elsewhere, to an independent long-double statement of the formulas (tests/bounded_weno_reference.py,
+tests/test_bounded_weno_reference.py): the oracle's y and z directions, the wall stencils of z (order 5 / 3 / upwind), the face densities
+and stretched z, on rough states where both bounds bind.  tests/test_bounded_weno_clients.py runs the device kernel on those states for
+moisture, the Kessler species and user tracers.  What remains unpinned is the reference package itself: Oceananigans is not vendored, no
+value of this operator exists in the reference, and both statements could share one misreading of the published limiter."""
 import ctypes as C
 
 import numpy as np
@@ -191,6 +197,37 @@ def test_host_rejects_unsupported_bounded_requests(bz):
         _split_advection(bz.WENO(bounds=(0, 1)), ())
     with pytest.raises(ValueError):
         bz.WENO(bounds=(1, 0))
+
+
+def test_host_rejects_bounds_on_a_part_of_a_class(bz):
+    """one mask bit per class in the library: bounds on one tracer of two, or on one Kessler species, would limit the other as well"""
+    from breeze_jl_amd.model import _SPECIES_KEYS, _check_bounded_clients
+    W, B = bz.WENO(), bz.WENO(bounds=(0, 1))
+    _check_bounded_clients(W, ("a", "b"), _SPECIES_KEYS)
+    _check_bounded_clients({"momentum": W, "ρθ": W, "ρqᵉ": B}, ("a", "b"), _SPECIES_KEYS)          # moisture alone: no class is split
+    _check_bounded_clients({"momentum": W, "a": B, "ρb": B, "ρqᶜˡ": B, "ρqʳ": B}, ("a", "b"), _SPECIES_KEYS)
+    for advection, tracers, unnamed in (({"momentum": W, "a": B}, ("a", "b"), "b"), ({"momentum": W, "a": W, "ρb": B}, ("a", "b"), "a"),
+                                        ({"momentum": W, "ρqʳ": B}, (), "ρqᶜˡ"), ({"momentum": W, "ρqᶜˡ": B, "ρqʳ": W}, ("a",), "ρqʳ")):
+        with pytest.raises(NotImplementedError) as e:
+            _check_bounded_clients(advection, tracers, _SPECIES_KEYS)
+        assert repr(unnamed) in str(e.value), (unnamed, str(e.value))
+    grid = bz.RectilinearGrid((8, 8, 8), x=EXT[0], y=EXT[1], z=EXT[2])
+    with pytest.raises(NotImplementedError, match="'b'"):          # the constructor asks, before it needs a GPU
+        bz.AtmosphereModel(grid, advection={"momentum": W, "ρθ": W, "a": B}, tracers=("a", "b"))
+
+
+def test_host_rejects_bounds_on_species_the_model_does_not_carry(bz):
+    """the library limits the species of a Kessler model only: on any other model the request would be a silent plain WENO-5 run"""
+    from breeze_jl_amd.model import _check_bounded_clients
+    W, B = bz.WENO(), bz.WENO(bounds=(0, 1))
+    for key in ("ρqᶜˡ", "ρqʳ"):
+        with pytest.raises(ValueError, match=key):
+            _check_bounded_clients({"momentum": W, "ρqᵉ": B, key: B}, (), ())
+    _check_bounded_clients({"momentum": W, "ρqᶜˡ": W, "ρqʳ": W}, (), ())          # without bounds the key asks for nothing the library gates
+    grid = bz.RectilinearGrid((8, 8, 8), x=EXT[0], y=EXT[1], z=EXT[2])
+    for microphysics in (None, bz.SaturationAdjustment(equilibrium=bz.WarmPhaseEquilibrium())):
+        with pytest.raises(ValueError, match="ρqᶜˡ"):
+            bz.AtmosphereModel(grid, advection={"momentum": W, "ρθ": W, "ρqᶜˡ": B, "ρqʳ": B}, microphysics=microphysics)
 
 
 @pytest.mark.gpu
