@@ -87,14 +87,16 @@ static inline double weno_quot(double tau, double bpe) { return og_weno_ft2 == 1
  * Smoothness indicators are 3x Jiang-Shu (Oceananigans coefficient tables). */
 static inline double weno5(double a, double b, double c, double d, double e)
 {
-    double b0 = c * (10.0 * c - 31.0 * d + 11.0 * e) + d * (25.0 * d - 19.0 * e) + e * (4.0 * e);
-    double b1 = b * (4.0 * b - 13.0 * c + 5.0 * d) + c * (13.0 * c - 13.0 * d) + d * (4.0 * d);
-    double b2 = a * (4.0 * a - 19.0 * b + 11.0 * c) + b * (25.0 * b - 31.0 * c) + c * (10.0 * c);
-    double tau = fabs(b0 - b2);
-    double p0 = (1.0 / 3.0) * c + (5.0 / 6.0) * d - (1.0 / 6.0) * e;
-    double p1 = -(1.0 / 6.0) * b + (5.0 / 6.0) * c + (1.0 / 3.0) * d;
-    double p2 = (1.0 / 3.0) * a - (7.0 / 6.0) * b + (11.0 / 6.0) * c;
-    if (og_weno_ft2 == 2) {
+    /* The indicators and the candidates' increments do not change when a constant is added to the five cells, so they are evaluated
+     * on the cells minus the upwind cell c0 (the differences are exact or rounded once) and c0 is added back at the end.  On the cells
+     * themselves the expanded quadratic forms below square a 300 K mean and cancel it again: measured against the long-double
+     * reference of tests/advection_reference.py, G(rho theta) was 8e-13 off for order 5 and, where theta is nearly linear along
+     * a column (beta of the order of eps), 3e-9 off for order 9 (tests/test_advection_reference.py); the device kernels have used
+     * difference forms throughout (csrc/bz_weno.h, csrc/bz_tendency_generic.hip). */
+    if (og_weno_ft2 == 2) {      /* the FT2 hypothesis keeps the cells as they are: its Float32 indicators are what it is about */
+        const double p0 = (1.0 / 3.0) * c + (5.0 / 6.0) * d - (1.0 / 6.0) * e;
+        const double p1 = -(1.0 / 6.0) * b + (5.0 / 6.0) * c + (1.0 / 3.0) * d;
+        const double p2 = (1.0 / 3.0) * a - (7.0 / 6.0) * b + (11.0 / 6.0) * c;
         const float af = (float)a, bf = (float)b, cf = (float)c, df = (float)d, ef = (float)e;
         const float f0 = cf * (10.0f * cf - 31.0f * df + 11.0f * ef) + df * (25.0f * df - 19.0f * ef) + ef * (4.0f * ef);
         const float f1 = bf * (4.0f * bf - 13.0f * cf + 5.0f * df) + cf * (13.0f * cf - 13.0f * df) + df * (4.0f * df);
@@ -105,13 +107,22 @@ static inline double weno5(double a, double b, double c, double d, double e)
         const float sum = w0 + w1 + w2;
         return (double)(w0 / sum) * p0 + (double)(w1 / sum) * p1 + (double)(w2 / sum) * p2;
     }
+    const double c0 = c;
+    a -= c0; b -= c0; d -= c0; e -= c0; c = 0.0;
+    double b0 = c * (10.0 * c - 31.0 * d + 11.0 * e) + d * (25.0 * d - 19.0 * e) + e * (4.0 * e);
+    double b1 = b * (4.0 * b - 13.0 * c + 5.0 * d) + c * (13.0 * c - 13.0 * d) + d * (4.0 * d);
+    double b2 = a * (4.0 * a - 19.0 * b + 11.0 * c) + b * (25.0 * b - 31.0 * c) + c * (10.0 * c);
+    double tau = fabs(b0 - b2);
+    double p0 = (1.0 / 3.0) * c + (5.0 / 6.0) * d - (1.0 / 6.0) * e;
+    double p1 = -(1.0 / 6.0) * b + (5.0 / 6.0) * c + (1.0 / 3.0) * d;
+    double p2 = (1.0 / 3.0) * a - (7.0 / 6.0) * b + (11.0 / 6.0) * c;
     double r0 = weno_quot(tau, b0 + WENO_EPS);
     double r1 = weno_quot(tau, b1 + WENO_EPS);
     double r2 = weno_quot(tau, b2 + WENO_EPS);
     double a0 = (3.0 / 10.0) * (1.0 + r0 * r0);
     double a1 = (3.0 / 5.0) * (1.0 + r1 * r1);
     double a2 = (1.0 / 10.0) * (1.0 + r2 * r2);
-    return (a0 * p0 + a1 * p1 + a2 * p2) / (a0 + a1 + a2);
+    return c0 + (a0 * p0 + a1 * p1 + a2 * p2) / (a0 + a1 + a2);
 }
 
 /* 3rd order buffer scheme: cells (a,b,c), upwind cell b, face between b and c. */
@@ -141,13 +152,19 @@ static inline double weno3(double a, double b, double c)
 /* ---- orders 7 and 9 (WENO(order = 9) and its buffer cascade 9 -> 7 -> 5 -> 3 -> 1): tables derived in exact arithmetic by
  * tools/gen_weno_tables.py (they reproduce the order-5 table above and the Balsara & Shu (2000) tables for r = 4, 5 that
  * Oceananigans tabulates; WENO-Z with tau = |b0 + 3 b1 - 3 b2 - b3| (r = 4), |b0 + 2 b1 - 6 b2 + 2 b3 + b4| (r = 5): recalled from
- * Oceananigans.Advection, PARITY UNPINNED).  v[0 .. 2r-2], upwind cell v[r-1], value at the face between v[r-1] and v[r].
+ * Oceananigans.Advection.  Pinned by the independent long-double restatement of tests/advection_reference.py, together with the
+ * cascade (buffer_at, face and centre rule) and the Centered(2 (B - 1)) interpolation with its reduction (symm_*) below; still
+ * unpinned in that no number generated by Oceananigans itself is compared).  v[0 .. 2r-2], upwind cell v[r-1], value at the face between v[r-1] and v[r].
  * Same order of operations as weno5 above: nested upper-triangular smoothness sums, three-quotient WENO-Z weights, normalisation. */
 #include "weno_tables.h"
 #define OG_WENO_GENERIC(R)                                                                                    \
     static inline double weno_r##R(const double *v)                                                          \
     {                                                                                                        \
         double beta[R], p[R], tau = 0.0, num = 0.0, den = 0.0;                                               \
+        double sh[2 * R - 1];                                                                                \
+        const double c0 = (og_weno_ft2 == 2) ? 0.0 : v[R - 1];      /* cells minus the upwind cell, see weno5 */ \
+        for (int j = 0; j < 2 * R - 1; ++j) sh[j] = v[j] - c0;                                               \
+        v = sh;                                                                                              \
         for (int s = 0; s < R; ++s) {                                                                        \
             const double *w = v + (R - 1 - s);                                                               \
             double b = 0.0, q = 0.0;                                                                         \
@@ -178,7 +195,7 @@ static inline double weno3(double a, double b, double c)
             num = (s == 0) ? a * p[s] : num + a * p[s];                                                      \
             den = (s == 0) ? a : den + a;                                                                    \
         }                                                                                                    \
-        return num / den;                                                                                    \
+        return c0 + num / den;                                                                               \
     }
 OG_WENO_GENERIC(4)
 OG_WENO_GENERIC(5)
