@@ -42,3 +42,6 @@ from .diagnostics import (Average, DewpointTemperature, EquivalentPotentialTempe
 from .diagnostics import at, compute_averages, partial_z  # noqa: F401,E402
 from .diagnostics import AzimuthalMean, RadialVelocity, TangentialVelocity, azimuthal_mean  # noqa: F401,E402
 from .diagnostics import ColumnIntegral, precipitation_rate, surface_precipitation_flux  # noqa: F401,E402
+from . import balance  # noqa: F401,E402
+from .balance import (AdiabaticBalancer, DefaultTimeStepping, balance_adiabatically_, initial_fields,  # noqa: F401,E402
+                      nudge_initial_fields_, resolve_balance_Δt, snapshot_initial_fields)

@@ -367,6 +367,9 @@ SYMBOLS = {
     "bz_azimuthal_mean": (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_int32, _dp,
                                     C.POINTER(C.c_int64)]),
     "bz_polar_winds": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_void_p]),
+    "bz_nudge_fields": (C.c_int, [_ctx, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_double]),
+    "bz_balance_adiabatically_compressible": (C.c_int, [_ctx, _csp, _cpp, _cpp, _asp, C.c_double, C.c_int32, C.c_double, C.c_int32]),
+    "bz_balance_adiabatically_anelastic": (C.c_int, [_ctx, _sp, _pp, _pp, C.c_double, C.c_int32, C.c_double, C.c_int32]),
 }
 
 

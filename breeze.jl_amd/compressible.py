@@ -353,6 +353,28 @@ def _exner_reference_struct(T, dynamics):
     return br, arrays
 
 
+def _split_explicit_struct(T, grid, td, temperature_solver, substep_floattype, sponge=True):
+    """-> bz_split_explicit of a SplitExplicitTimeDiscretization; sponge = False leaves the UpperSponge out (the adiabatic-balance twin)."""
+    bt = T.bz_split_explicit()
+    bt.substeps = 0 if td.substeps is None else td.substeps
+    damp = td.damping
+    bt.damp_vertical = int(isinstance(damp, ThermalDivergenceDamping) and damp.damp_vertical)
+    bt.apply_first_substep_pressure_gradient = int(td.apply_first_substep_pressure_gradient)
+    bt.newton_maxiter = temperature_solver.maxiter
+    bt.acoustic_cfl, bt.forward_weight = td.acoustic_cfl, td.forward_weight
+    bt.damping_coefficient = damp.coefficient if isinstance(damp, (ThermalDivergenceDamping, DirectDivergenceDamping)) else -1.0
+    bt.direct_divergence_damping = int(isinstance(damp, DirectDivergenceDamping))
+    bt.damping_length_scale = (damp.length_scale or 0.0) if isinstance(damp, ThermalDivergenceDamping) else 0.0
+    bt.thermodynamic_tendency_factor = td.thermodynamic_tendency_factor
+    bt.vertical_momentum_tendency_factor = td.vertical_momentum_tendency_factor
+    bt.newton_abstol = temperature_solver.abstol
+    bt.substep_distribution = td.substep_distribution.code
+    bt.substep_float_bytes = 4 if (substep_floattype is np.float32 and grid.ftype == 8) else 0
+    if sponge and td.sponge is not None:
+        bt.sponge_ramp, bt.sponge_damping_rate, bt.sponge_depth = td.sponge.ramp.code, td.sponge.damping_rate, td.sponge.depth
+    return bt
+
+
 class CompressibleAtmosphereModel(_context.ContextOwner):
     """AtmosphereModel(grid; dynamics=CompressibleDynamics(SplitExplicitTimeDiscretization(...)), advection=WENO(order=5))
     — timestepper :AcousticRungeKutta3; coriolis = FPlane(f) and density-keyed Relaxation sponges on ρu, ρv, ρw, ρθ
@@ -476,25 +498,8 @@ class CompressibleAtmosphereModel(_context.ContextOwner):
         bg, self._zf = _context.grid_struct(T, grid)
         ref = dynamics.reference_state
         br, self._ref_arrays = _exner_reference_struct(T, dynamics)
+        bt = _split_explicit_struct(T, grid, dynamics.time_discretization, self.temperature_solver, self.timestepper.substepper.substep_floattype)
         td = dynamics.time_discretization
-        bt = T.bz_split_explicit()
-        bt.substeps = 0 if td.substeps is None else td.substeps
-        damp = td.damping
-        bt.damp_vertical = int(isinstance(damp, ThermalDivergenceDamping) and damp.damp_vertical)
-        bt.apply_first_substep_pressure_gradient = int(td.apply_first_substep_pressure_gradient)
-        bt.newton_maxiter = self.temperature_solver.maxiter
-        bt.acoustic_cfl, bt.forward_weight = td.acoustic_cfl, td.forward_weight
-        bt.damping_coefficient = damp.coefficient if isinstance(damp, (ThermalDivergenceDamping, DirectDivergenceDamping)) else -1.0
-        bt.direct_divergence_damping = int(isinstance(damp, DirectDivergenceDamping))
-        bt.damping_length_scale = (damp.length_scale or 0.0) if isinstance(damp, ThermalDivergenceDamping) else 0.0
-        bt.thermodynamic_tendency_factor = td.thermodynamic_tendency_factor
-        bt.vertical_momentum_tendency_factor = td.vertical_momentum_tendency_factor
-        bt.newton_abstol = self.temperature_solver.abstol
-        bt.substep_distribution = td.substep_distribution.code
-        sft = self.timestepper.substepper.substep_floattype
-        bt.substep_float_bytes = 4 if (sft is np.float32 and grid.ftype == 8) else 0
-        if td.sponge is not None:
-            bt.sponge_ramp, bt.sponge_damping_rate, bt.sponge_depth = td.sponge.ramp.code, td.sponge.damping_rate, td.sponge.depth
         self._open_context("bz_create_compressible", bg, _context.constants_struct(T, c), br, bt, advection.order)
         self._state = self._make_state()
         self._U0, self._G = self._make_prog(self.U0), self._make_prog(self.G)
@@ -708,13 +713,17 @@ def exner_columns_(model, potential_temperature, vapor_mass_fraction, surface_pr
                                              C.c_void_p(density.ptr())), "bz_exner_columns")
 
 
-def set_(model, compute_reference_state=False, **kw):
+def set_(model, compute_reference_state=False, balancer=None, **kw):
     """set!(model; ρ, θ, u, v, w, qᵗ, compute_reference_state): total density first, moisture, then establish_densities!, θ and velocities
     (set_atmosphere_model.jl:198-362; compressible_time_stepping.jl:105-150).  Walls in y: v given as a function is evaluated on the
     faces 0 … Ny-1, ρv takes the face-mean density through the no-flux halo row, and update_state! leaves exact zeros on the wall faces.
     ρ = HydrostaticallyBalancedDensity(p₀) is the reference's deferred density: a unit placeholder goes into ρᵈ, establish_densities! runs with
     neither density given, and the balanced density is computed after the closing update_state!; compute_reference_state = True recomputes
-    the reference state from the horizontal means first (a no-op without one)."""
+    the reference state from the horizontal means first (a no-op without one).  balancer = AdiabaticBalancer(...) | True:
+    balance_adiabatically!(model, balancer) closes the call (balance.py)."""
+    if balancer is not None and balancer is not False:      # refused by name before anything is set
+        from .balance import require_balance_model
+        require_balance_model(model, balancer, "set!(model; balancer)")
     balanced = next((v for n, v in kw.items() if _ALIASES.get(n) == "ρ" and isinstance(v, HydrostaticallyBalancedDensity)), None)
     if balanced is not None:
         _require_balance_scope(model, "HydrostaticallyBalancedDensity")
@@ -776,6 +785,9 @@ def set_(model, compute_reference_state=False, **kw):
         reset_reference_state_(model)
     if balanced is not None:
         set_hydrostatically_balanced_density_(model, balanced)
+    if balancer is not None and balancer is not False:
+        from .balance import balance_adiabatically_
+        balance_adiabatically_(model, balancer)
 
 
 def time_step_(model, Δt, whole_step=True):

@@ -234,6 +234,14 @@ static int compressible_step_body(bz_ctx *ctx, const bz_compressible_state *s, c
     return BZ_OK;
 }
 
+// the step body for a caller that has checked the arguments and opens the call itself (bz_adiabatic_balance.hip): launched, never replayed,
+// and without the moisture scan — the scan's word must say "unknown" (the stage kernels then skip nothing; same bits)
+int bzi_compressible_step_launched(bz_ctx *ctx, const bz_compressible_state *s, const bz_compressible_prognostic *U0,
+                                   const bz_compressible_prognostic *G, const bz_acoustic_substepper *sub, double dt)
+{
+    return compressible_step_body(ctx, s, U0, G, sub, dt);
+}
+
 extern "C" int bz_time_step_compressible(bz_ctx *ctx, const bz_compressible_state *s, const bz_compressible_prognostic *U0,
                                          const bz_compressible_prognostic *G, const bz_acoustic_substepper *sub, double dt)
 {

@@ -310,6 +310,9 @@ int bzi_acoustic_stage_end(bz_ctx *ctx, const bz_compressible_state *s, const bz
 // bz_instant_precip.hip: the once-per-step rain-out kernel of InstantaneousPrecipitation on the state's own arrays (bz_ctx::has_instant_precip);
 // bz_instantaneous_precipitation_update (public) is this followed by update_state! with tendencies
 int bzi_instantaneous_precipitation(bz_ctx *ctx, const bz_compressible_state *s, double dt);
+// bz_compressible.hip: the whole-step body, launched (no moisture scan, no recorded graph)
+int bzi_compressible_step_launched(bz_ctx *ctx, const bz_compressible_state *s, const bz_compressible_prognostic *U0,
+                                   const bz_compressible_prognostic *G, const bz_acoustic_substepper *sub, double dt);
 bool bzi_acoustic_stage_end_fusable(const bz_ctx *ctx);
 int bzi_acoustic_stage_end_fused(bz_ctx *ctx, const bz_compressible_state *s, const bz_compressible_prognostic *U0,
                                  const bz_compressible_prognostic *G, const bz_acoustic_substepper *sub, double dt, double beta,

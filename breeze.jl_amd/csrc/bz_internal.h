@@ -804,6 +804,8 @@ inline constexpr double BZ_SSP_RK3_ALPHA[3] = {1.0, 1.0 / 4.0, 2.0 / 3.0};      
 int bzi_zero_wall_faces(bz_ctx *ctx, const bz_prognostic *G, const bz_prognostic *U0 = nullptr);      // wall faces of the predictor rho w stay 0
 int bzi_fused_rk_physics(bz_ctx *ctx, const bz_state *s, const bz_prognostic *G, double dt, double alpha, bool first, bool fold);
 void bzi_lean_step_done(bz_ctx *ctx, bool diagnosed);
+int bzi_anelastic_steps_open(bz_ctx *ctx, const bz_state *s);      // a caller's own sequence of launched steps (bz_adiabatic_balance.hip)
+int bzi_anelastic_step_launched(bz_ctx *ctx, const bz_state *s, const bz_prognostic *U0, const bz_prognostic *G, double dt);
 int bzi_scan_moisture(bz_ctx *ctx, const bz_state *s);
 int bzi_scan_moisture_field(bz_ctx *ctx, const double *rho_q);
 const int *bzi_moisture_state(const bz_ctx *ctx);

@@ -362,6 +362,27 @@ static int surface_layer_first_step(bz_ctx *ctx, const bz_state *s)
     return bz_surface_layer_initialize(ctx, s);
 }
 
+// A sequence of steps of a caller that opens the call itself (bz_adiabatic_balance.hip).  open: what bz_time_step_anelastic does before its
+// step, with the moisture scan's word put to "unknown" instead of a scan (the kernels then skip nothing: same bits, and no read-back);
+// launched: one step that is never replayed from, or recorded into, a graph of the context.
+int bzi_anelastic_steps_open(bz_ctx *ctx, const bz_state *s)
+{
+    level_sums_open(ctx);
+    if (ctx->d_qstate) BZ_HIP(hipMemsetAsync(ctx->d_qstate, 0, sizeof(int), ctx->stream));
+    bzi_moisture_unknown(ctx);
+    return surface_layer_first_step(ctx, s);
+}
+
+int bzi_anelastic_step_launched(bz_ctx *ctx, const bz_state *s, const bz_prognostic *U0, const bz_prognostic *G, double dt)
+{
+    const int mode = ctx->graph_mode;
+    ctx->graph_mode = 0;
+    const int rc = one_anelastic_step(ctx, s, U0, G, dt, true);
+    ctx->graph_mode = mode;
+    ctx->lsum_fresh = false;
+    return rc;
+}
+
 extern "C" int bz_time_step_anelastic(bz_ctx *ctx, const bz_state *s, const bz_prognostic *U0, const bz_prognostic *G, double dt)
 {
     if (!ctx || !s || !U0 || !G) return BZ_ERR_INVALID;

@@ -685,9 +685,13 @@ def enforce_mass_conservation_(model):
     update_state_(model, compute_tendencies=False)
 
 
-def set_(model, enforce_mass_conservation=True, **kw):
-    """set!(model; kw...): θ / ρθ, u v w / ρu ρv ρw, qᵗ / ρqᵗ from numbers, arrays or f(x, y, z)."""
+def set_(model, enforce_mass_conservation=True, balancer=None, **kw):
+    """set!(model; kw...): θ / ρθ, u v w / ρu ρv ρw, qᵗ / ρqᵗ from numbers, arrays or f(x, y, z).  balancer = AdiabaticBalancer(...) | True:
+    balance_adiabatically!(model, balancer) after the fields are set (set_atmosphere_model.jl; balance.py)."""
     import torch
+    if balancer is not None and balancer is not False:      # refused by name before anything is set
+        from .balance import require_balance_model
+        require_balance_model(model, balancer, "set!(model; balancer)")
     if getattr(model, "_kinematic", False):
         return _set_kinematic(model, **kw)
     g = model.grid
@@ -792,6 +796,9 @@ def set_(model, enforce_mass_conservation=True, **kw):
     update_state_(model, compute_tendencies=False)
     if enforce_mass_conservation:
         enforce_mass_conservation_(model)
+    if balancer is not None and balancer is not False:
+        from .balance import balance_adiabatically_
+        balance_adiabatically_(model, balancer)
 
 
 def _set_kinematic(model, **kw):

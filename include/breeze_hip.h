@@ -1112,6 +1112,32 @@ int bz_azimuthal_mean(bz_ctx *ctx, const double *field, int z_face, double cente
  * the context's stream.  Flat-y contexts return BZ_ERR_UNSUPPORTED. */
 int bz_polar_winds(bz_ctx *ctx, const double *u, const double *v, double center_x, double center_y, double *tangential, double *radial);
 
+/* ---- adiabatic initialisation (csrc/bz_adiabatic_balance.hip) ----
+ * balance_adiabatically!(model; dt, cycles, weight) of the reference (src/AtmosphereModels/adiabatic_balance.jl:44-86), FV3's na_init: the
+ * initial fields — every prognostic field but rho_w — are snapshotted as whole parent arrays; each of `cycles` cycles runs, for s = +1 and
+ * then s = -1, time_step(s dt), time_step(-s dt), the nudge x <- (x + weight x0) / (1 + weight) of every initial field over its whole parent
+ * array, the halo fills of the nudged fields and update_state! with tendencies.  rho_w is never snapshotted or nudged.
+ *
+ * bz_nudge_fields — nudge_initial_fields!: one launch blends `n` <= 16 DEVICE arrays fields[i] of count[i] elements each towards snapshots[i],
+ * in the arrays' own precision; counts may differ (centre and z-face parents) and may be odd.  Asynchronous on the context's stream; any context.
+ *
+ * bz_balance_adiabatically_compressible / _anelastic — the whole loop behind one call, on the context it is given: the caller passes a
+ * context WITHOUT sponge, microphysics, closure, forcings and surface fluxes (the excursions must be reversible), with the state made
+ * consistent as before a first time step (compressible: bz_seed_time_averaged_velocities + bz_compressible_update_state(.., 1); anelastic:
+ * bz_update_state(.., 1)).  Initial fields: rho_d, rho_u, rho_v, rho_theta [, rho_q] — anelastic: rho_u, rho_v, rho_theta [, rho_q] and the
+ * user tracers; rho_q is left out of the list with nudge_moisture = 0; Kessler species are never nudged.  The snapshot memory is allocated
+ * and freed by the call; everything between is enqueued on the context's stream without a host synchronisation, the steps are launched,
+ * never replayed from a recorded graph, and nothing of the context's configuration changes (recorded steps stay valid).  The moisture scan
+ * is not run: the steps treat the moisture as present (same bits).  Negative dt steps are the ordinary steps with the sign of dt carried
+ * through: the substep count takes |dt| and the UpperSponge terms |dtau|.  BZ_ERR_INVALID: cycles < 1, dt zero or not finite, weight not
+ * finite or <= -1.  BZ_ERR_UNSUPPORTED with bz_last_error naming the reason: y-slab, kinematic and walled (Bounded x / y) contexts. */
+int bz_nudge_fields(bz_ctx *ctx, int32_t n, double *const *fields, const double *const *snapshots, const int64_t *count, double weight);
+int bz_balance_adiabatically_compressible(bz_ctx *ctx, const bz_compressible_state *s, const bz_compressible_prognostic *U0,
+                                          const bz_compressible_prognostic *G, const bz_acoustic_substepper *sub, double dt, int32_t cycles,
+                                          double weight, int32_t nudge_moisture);
+int bz_balance_adiabatically_anelastic(bz_ctx *ctx, const bz_state *s, const bz_prognostic *U0, const bz_prognostic *G, double dt,
+                                       int32_t cycles, double weight, int32_t nudge_moisture);
+
 /* ---- instrumentation (not part of the reference interface) ---- */
 /* When enabled, every kernel group is bracketed by hipEvents on the ctx stream. */
 int bz_profile_enable(bz_ctx *ctx, int on);
