@@ -8,7 +8,7 @@ repo root) rather than a plain `import`.
 """
 from ._lib import BreezeHIPError, LIB_PATH, SYMBOLS, build, load  # noqa: F401
 from .grids import Bounded, Center, Face, Flat, Periodic, RectilinearGrid  # noqa: F401
-from .thermodynamics import ReferenceState, ThermodynamicConstants  # noqa: F401
+from .thermodynamics import FlatauPolynomial, ReferenceState, ThermodynamicConstants  # noqa: F401
 from .model import (AnelasticDynamics, AtmosphereModel, Centered, Field, WENO, compute_auxiliary_thermodynamic_variables_,  # noqa: F401
                     compute_pressure_correction_, compute_scalar_tendency_, compute_tendencies_, compute_velocities_,
                     enforce_mass_conservation_, fill_halo_regions_, make_pressure_correction_, set_,

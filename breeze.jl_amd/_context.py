@@ -222,6 +222,48 @@ def check_mixed_phase_model(microphysics, thermodynamic_constants, forcing, boun
         refuse_mixed_phase(microphysics, where, "a bottom flux keyed ρe: the energy-to-θ conversion forms cᵖᵐ without qⁱ")
 
 
+def flatau_polynomial(thermodynamic_constants):
+    """The FlatauPolynomial of the constants, or None (Clausius-Clapeyron, Tetens)."""
+    from .thermodynamics import FlatauPolynomial
+    formula = getattr(thermodynamic_constants, "saturation_vapor_pressure", None)
+    return formula if isinstance(formula, FlatauPolynomial) else None
+
+
+def refuse_flatau_polynomial(thermodynamic_constants, where, why):
+    """ThermodynamicConstants(saturation_vapor_pressure = FlatauPolynomial()) runs inside the saturation adjustments of the single-device
+    AtmosphereModel (AnelasticDynamics) and CompressibleAtmosphereModel; every place whose kernels hard-wire the Clausius-Clapeyron expression
+    says so here, where the constants are checked and before a GPU is asked for."""
+    if flatau_polynomial(thermodynamic_constants) is not None:
+        raise NotImplementedError(f"{where}: ThermodynamicConstants(saturation_vapor_pressure = FlatauPolynomial()) is not implemented ({why}); "
+                                  "the default (Clausius-Clapeyron) constants run here")
+
+
+def check_flatau_anelastic(thermodynamic_constants, boundary_conditions):
+    """The bottom conditions of an anelastic model whose surface qᵛ⁺ is the Clausius-Clapeyron expression: BulkVaporFlux, and the surface layer
+    (PolynomialCoefficient, FilteredSurfaceVelocities, T₀(x, y)), whose stability correction forms θᵥ₀ from qᵛ⁺(T₀) for every condition.  Forcings
+    and bottom fluxes keyed e / ρe convert energy to θ with cᵖᵐ of the stored qᵛ, qˡ: they read no pᵛ⁺ and stay."""
+    if flatau_polynomial(thermodynamic_constants) is None:
+        return
+    from .forcings import BulkVaporFlux, _bulk_conditions, needs_surface_layer
+    if needs_surface_layer(boundary_conditions):
+        refuse_flatau_polynomial(thermodynamic_constants, "AtmosphereModel", "the surface layer (PolynomialCoefficient, FilteredSurfaceVelocities, "
+                                 "T₀(x, y)) evaluates the Clausius-Clapeyron qᵛ⁺ of the surface")
+    if any(isinstance(cond, BulkVaporFlux) for _, cond in _bulk_conditions(boundary_conditions)):
+        refuse_flatau_polynomial(thermodynamic_constants, "AtmosphereModel", "BulkVaporFlux evaluates the Clausius-Clapeyron qᵛ⁺ of the surface")
+
+
+def attach_flatau_polynomial(model):
+    """bz_set_saturation_vapor_pressure_polynomial from the constants of the model; nothing on Clausius-Clapeyron (and Tetens) constants."""
+    fp = flatau_polynomial(model.thermodynamic_constants)
+    if fp is None:
+        return
+    P = model._T.bz_flatau_polynomial()
+    for n in range(9):
+        P.liquid_coefficients[n], P.ice_coefficients[n] = fp.liquid_coefficients[n], fp.ice_coefficients[n]
+    P.reference_temperature, P.minimum_temperature_offset = fp.reference_temperature, fp.minimum_temperature_offset
+    model._check(model._lib.bz_set_saturation_vapor_pressure_polynomial(model._ctx, C.byref(P)), "bz_set_saturation_vapor_pressure_polynomial")
+
+
 def check_kessler_constants(thermodynamic_constants):
     """validate_microphysics (dcmip2016_kessler.jl:196-207)"""
     from .microphysics import TetensFormula

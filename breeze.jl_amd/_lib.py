@@ -63,6 +63,11 @@ class bz_mixed_phase_equilibrium(C.Structure):
                                           "ice_heat_capacity")]
 
 
+class bz_flatau_polynomial(C.Structure):
+    _fields_ = [("liquid_coefficients", C.c_double * 9), ("ice_coefficients", C.c_double * 9),
+                ("reference_temperature", C.c_double), ("minimum_temperature_offset", C.c_double)]
+
+
 class bz_negative_moisture_correction(C.Structure):
     """Descriptor of bz_set_negative_moisture_correction: the two phases, the species chain (heaviest first), the (number, mass) pairs and the
     clamped number fields, every array a device parent array.  Pointers and counts only: one struct for both precisions."""
@@ -251,6 +256,7 @@ SYMBOLS = {
     "bz_set_formulation": (C.c_int, [_ctx, C.c_int]),
     "bz_set_saturation_adjustment": (C.c_int, [_ctx, C.POINTER(bz_saturation_adjustment), C.c_void_p, C.c_void_p]),
     "bz_set_mixed_phase_equilibrium": (C.c_int, [_ctx, C.POINTER(bz_mixed_phase_equilibrium), C.c_void_p]),
+    "bz_set_saturation_vapor_pressure_polynomial": (C.c_int, [_ctx, C.POINTER(bz_flatau_polynomial)]),
     "bz_set_negative_moisture_correction": (C.c_int, [_ctx, C.POINTER(bz_negative_moisture_correction)]),
     "bz_fix_negative_moisture": (C.c_int, [_ctx, C.POINTER(bz_state)]),
     "bz_set_stream": (C.c_int, [_ctx, C.c_void_p]),
@@ -440,7 +446,7 @@ def _f32_type(t):
         inner = _f32_type(t._type_)
         return t if inner is t._type_ else C.POINTER(inner)
     if isinstance(t, type) and issubclass(t, C.Array):
-        return t
+        return C.c_float * t._length_ if t._type_ is C.c_double else t      # (arrays of pointers are shared by both ABIs)
     return t
 
 

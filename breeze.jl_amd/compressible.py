@@ -456,6 +456,11 @@ class CompressibleAtmosphereModel(_context.ContextOwner):
         self._kessler = _context.check_microphysics(microphysics, "compressible microphysics: DCMIP2016KesslerMicrophysics() and "
                                                                   "SaturationAdjustment(equilibrium = WarmPhaseEquilibrium()) are implemented",
                                                     instantaneous_precipitation_refused=ip_refused)
+        # FlatauPolynomial constants: the single-device model; a bulk vapour flux evaluates the Clausius-Clapeyron qᵛ⁺ of the surface
+        if type(self) is not CompressibleAtmosphereModel:
+            _context.refuse_flatau_polynomial(thermodynamic_constants, type(self).__name__, "y-slab models evaluate the Clausius-Clapeyron expression")
+        if "vapor" in self._surface_fluxes:
+            _context.refuse_flatau_polynomial(thermodynamic_constants, type(self).__name__, "BulkVaporFlux evaluates the Clausius-Clapeyron qᵛ⁺ of the surface")
         self.microphysics = microphysics
         from .microphysics import InstantaneousPrecipitation
         self._ip = isinstance(microphysics, InstantaneousPrecipitation)
@@ -510,6 +515,8 @@ class CompressibleAtmosphereModel(_context.ContextOwner):
             _context.attach_kessler(self, dynamics.standard_pressure)
         if self._ip:
             _context.attach_instantaneous_precipitation(self, fld)
+        if self._sa or self._ip:
+            _context.attach_flatau_polynomial(self)      # saturation_vapor_pressure = FlatauPolynomial() of the constants
         if coriolis is not None:      # the f-plane term of the slow momentum tendencies (bz_set_forcings with coriolis_f alone)
             Fc = T.bz_column_forcings()
             Fc.coriolis_f = coriolis.f

@@ -728,9 +728,9 @@ __global__ __launch_bounds__(256) void k_ac_recover(DevGrid g, AcFieldsT<ST> F, 
 // Single-device contexts only (a y-slab has no rho' in its halo rows).
 template <bool DAMP, bool LIN, int MP, class ST>
 __global__ __launch_bounds__(256) void k_ac_stage_end(DevGrid g, AcFieldsT<ST> F, DiagFields D, AcParams P, double dt_stage, ST *__restrict__ thL_out,
-                                                      double abstol, int maxiter)
+                                                      double abstol, int maxiter, const double *fl)
 {
-    constexpr bool KES = (MP == 2), SA = (MP == 1);
+    constexpr bool KES = (MP == 2), SA = (MP == 1 || MP == 3), FL = (MP == 3);      // 3: the FlatauPolynomial instantiation of 1 (k_cmp_diagnose)
     int bx, j, k;
     ac_pencil_block(bx, j, k);
     const int i = bx * 256 + threadIdx.x;
@@ -829,7 +829,7 @@ __global__ __launch_bounds__(256) void k_ac_stage_end(DevGrid g, AcFieldsT<ST> F
         }
         double qvap = q;
         if (SA) {
-            T = bz_ds_adjust(g, th, q, r, abstol, maxiter, qvap, ql);
+            T = bz_ds_adjust<FL>(g, th, q, r, abstol, maxiter, qvap, ql, ColPtr(fl));
             st_img(g.qv_field, n, qvap, ox, oy);
             st_img(g.ql_field, n, ql, ox, oy);
             sa_qv = qvap; sa_ql = ql;

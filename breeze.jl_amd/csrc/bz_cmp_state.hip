@@ -15,15 +15,16 @@
 // MP = 1: SaturationAdjustment(WarmPhaseEquilibrium) on the density-based state — rho q is the total moisture, q^v / q^l are
 // diagnosed by bz_ds_adjust at the cell's own total density and the temperature is the same Newton inversion with the latent
 // term (compressible_time_stepping.jl:191-250; saturation_adjustment.jl:236-301)
+// MP = 3: MP = 1 with saturation_vapor_pressure = FlatauPolynomial (bz_set_saturation_vapor_pressure_polynomial): bz_ds_adjust<true>
 // WY: walls in y (topology (Periodic, Bounded, Bounded), dry or vapour-carrying models).  The halo writes follow the conventions of
 // DESIGN section 6 "Walls in y" instead of periodic images: a field that is a centre in y gets the no-flux copy of rows 0 and Ny - 1 in its
 // first halo rows (oy = one row down / up for those two rows), rho v and v get exact zeros on their wall faces 0 and Ny (face Ny is the first
 // upper halo row).  Row 0 reads no y neighbour: its face density is the no-flux mean (rho_d itself) and its v the wall's zero — the halo row
 // below it is written by this launch.  x stays periodic, z is unchanged.  WY = false compiles to the code it replaced.
 template <bool FULL, bool LIN, int MP = 0, bool WY = false>
-__global__ __launch_bounds__(256) void k_cmp_diagnose(DevGrid g, DiagFields F, double abstol, int maxiter)
+__global__ __launch_bounds__(256) void k_cmp_diagnose(DevGrid g, DiagFields F, double abstol, int maxiter, const double *fl)
 {
-    constexpr bool KES = (MP == 2), SA = (MP == 1);
+    constexpr bool KES = (MP == 2), SA = (MP == 1 || MP == 3), FL = (MP == 3);
     static_assert(!WY || (MP == 0 && !LIN), "walls in y: no microphysics; the linearisation is refreshed by its own kernel (halo rows)");
     const int i = blockIdx.x * 256 + threadIdx.x, j = blockIdx.y, k = blockIdx.z;
     if (i >= g.Nx) return;
@@ -81,7 +82,7 @@ __global__ __launch_bounds__(256) void k_cmp_diagnose(DevGrid g, DiagFields F, d
         }
         double qvap = q;        // vapour fraction of the mixture constants (q itself unless the adjustment partitions it)
         if (SA) {
-            T = bz_ds_adjust(g, th, q, r, abstol, maxiter, qvap, ql);
+            T = bz_ds_adjust<FL>(g, th, q, r, abstol, maxiter, qvap, ql, ColPtr(fl));
             st_img(g.qv_field, n, qvap, ox, oy);
             st_img(g.ql_field, n, ql, ox, oy);
             sa_qv = qvap; sa_ql = ql;
@@ -305,10 +306,10 @@ int bzi_compressible_update_state(bz_ctx *ctx, const bz_compressible_state *s, c
         dim3 grid((g.Nx + 255) / 256, g.Ny, g.Nz), block(256);
         const double na = ctx->se.newton_abstol;
         const int nm = ctx->se.newton_maxiter;
-        if (g.bounded_y) hipLaunchKernelGGL((k_cmp_diagnose<true, false, 0, true>), grid, block, 0, ctx->stream, g, F, na, nm);
+        if (g.bounded_y) hipLaunchKernelGGL((k_cmp_diagnose<true, false, 0, true>), grid, block, 0, ctx->stream, g, F, na, nm, bzi_flatau(ctx));
         else bz_bools([&](auto lin) {
             constexpr bool LIN = lin();
-            bz_static_int<3>(g.microphysics, [&](auto mp) { hipLaunchKernelGGL((k_cmp_diagnose<true, LIN, mp()>), grid, block, 0, ctx->stream, g, F, na, nm); });
+            bz_static_int<4>(bzi_cmp_mp(ctx), [&](auto mp) { hipLaunchKernelGGL((k_cmp_diagnose<true, LIN, mp()>), grid, block, 0, ctx->stream, g, F, na, nm, bzi_flatau(ctx)); });
         }, with_linearization);
         BZ_LAUNCH_CHECK();
     }
@@ -344,8 +345,8 @@ int bzi_compressible_velocities(bz_ctx *ctx, const bz_compressible_state *s, con
     const DevGrid &g = ctx->dg;
     ProfileScope ps(ctx, "acoustic_velocities");
     DiagFields D = diag_fields(ctx, s, sub);
-    if (g.bounded_y) hipLaunchKernelGGL((k_cmp_diagnose<false, false, 0, true>), dim3((g.Nx + 255) / 256, g.Ny, g.Nz), dim3(256), 0, ctx->stream, g, D, 0.0, 0);
-    else hipLaunchKernelGGL((k_cmp_diagnose<false, false>), dim3((g.Nx + 255) / 256, g.Ny, g.Nz), dim3(256), 0, ctx->stream, g, D, 0.0, 0);
+    if (g.bounded_y) hipLaunchKernelGGL((k_cmp_diagnose<false, false, 0, true>), dim3((g.Nx + 255) / 256, g.Ny, g.Nz), dim3(256), 0, ctx->stream, g, D, 0.0, 0, nullptr);
+    else hipLaunchKernelGGL((k_cmp_diagnose<false, false>), dim3((g.Nx + 255) / 256, g.Ny, g.Nz), dim3(256), 0, ctx->stream, g, D, 0.0, 0, nullptr);
     BZ_LAUNCH_CHECK();
     return BZ_OK;
 }

@@ -167,6 +167,9 @@ static void bz_static_int(int v, Fn &&f)
     } else f(std::integral_constant<int, 0>());
 }
 
+// the MP instantiation of k_cmp_diagnose and k_ac_stage_end: g.microphysics, or 3 for a saturation adjustment on FlatauPolynomial constants
+static inline int bzi_cmp_mp(const bz_ctx *ctx) { return (ctx->dg.microphysics == 1 && ctx->fl_on) ? 3 : ctx->dg.microphysics; }
+
 // ---- one WS-RK3 stage of the acoustic loop in three pieces (the y-slab driver exchanges halos between them) ---------
 struct AcStage {
     int ntau = 0, cur = 0, done = 0;

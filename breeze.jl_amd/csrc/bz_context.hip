@@ -212,6 +212,39 @@ extern "C" int bz_set_mixed_phase_equilibrium(bz_ctx *ctx, const bz_mixed_phase_
     return BZ_OK;
 }
 
+// saturation_vapor_pressure = FlatauPolynomial(...) of the ThermodynamicConstants (src/Thermodynamics/flatau_polynomial.jl): the kernels that
+// evaluate p^v+ inside a saturation adjustment take their polynomial instantiation (bz_ctx::fl_on, bzi_flatau).  params == NULL: Clausius-Clapeyron.
+extern "C" int bz_set_saturation_vapor_pressure_polynomial(bz_ctx *ctx, const bz_flatau_polynomial *params)
+{
+    if (ctx) ++ctx->config_epoch;      // captured steps (bz_graph.hip) belong to one configuration
+    if (!ctx) return BZ_ERR_INVALID;
+    if (!params) { ctx->fl_on = false; return BZ_OK; }
+    const char *why = (ctx->slab_mode || ctx->comm) ? "y-slab contexts evaluate the Clausius-Clapeyron expression"
+                      : ctx->kinematic ? "the kinematic driver evaluates the Clausius-Clapeyron expression"
+                      : ctx->sl_on     ? "a surface layer is attached: its surface q^v+ is the Clausius-Clapeyron expression"
+                      : ((ctx->bulk_const_on && ctx->bulk.vapor_coefficient > 0.0) || (ctx->cmp_sf_on && ctx->cmp_sf.vapor.enabled))
+                          ? "a bulk vapour flux is attached: its surface q^v+ is the Clausius-Clapeyron expression"
+                          : nullptr;
+    if (why) {
+        ctx->last_error = std::string("bz_set_saturation_vapor_pressure_polynomial: ") + why;
+        return BZ_ERR_UNSUPPORTED;
+    }
+    double table[BZ_FL_COUNT];
+    for (int n = 0; n < 9; ++n) {
+        table[BZ_FL_LIQUID + n] = params->liquid_coefficients[n];
+        table[BZ_FL_ICE + n] = params->ice_coefficients[n];
+    }
+    table[BZ_FL_TR] = params->reference_temperature;
+    table[BZ_FL_DT] = params->minimum_temperature_offset;
+    for (int n = 0; n < BZ_FL_COUNT; ++n)
+        if (!std::isfinite(table[n])) return BZ_ERR_INVALID;
+    if (!ctx->d_flatau) BZ_HIP(hipMalloc(&ctx->d_flatau, BZ_FL_COUNT * sizeof(double)));
+    BZ_HIP(hipStreamSynchronize(ctx->stream));      // kernels in flight read the table
+    BZ_HIP(hipMemcpy(ctx->d_flatau, table, BZ_FL_COUNT * sizeof(double), hipMemcpyHostToDevice));
+    ctx->fl_on = true;
+    return BZ_OK;
+}
+
 extern "C" int bz_sync(bz_ctx *ctx)
 {
     if (!ctx) return BZ_ERR_INVALID;
@@ -454,6 +487,7 @@ extern "C" void bz_destroy(bz_ctx *ctx)
     bzi_compressible_teardown(ctx);
     bzi_balance_teardown(ctx);
     if (ctx->d_columns) hipFree(ctx->d_columns);
+    if (ctx->d_flatau) hipFree(ctx->d_flatau);
     bzi_forcing_teardown(ctx);
     bzi_closure_teardown(ctx);
     bzi_diffusivity_teardown(ctx);

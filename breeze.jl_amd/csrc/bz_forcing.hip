@@ -585,6 +585,11 @@ extern "C" int bz_set_bulk_surface_fluxes(bz_ctx *ctx, const bz_bulk_surface_flu
         ctx->last_error = "bz_set_bulk_surface_fluxes: implemented for the anelastic potential-temperature model";
         return BZ_ERR_UNSUPPORTED;
     }
+    if (ctx->fl_on && b->vapor_coefficient > 0.0) {      // (the reverse order is refused by bz_set_saturation_vapor_pressure_polynomial)
+        ctx->last_error = "bz_set_bulk_surface_fluxes: a bulk vapour flux evaluates the Clausius-Clapeyron q^v+ of the surface, and the context's "
+                          "saturation adjustment runs on a FlatauPolynomial (bz_set_saturation_vapor_pressure_polynomial)";
+        return BZ_ERR_UNSUPPORTED;
+    }
     ctx->bulk = *b;
     ctx->bulk_const_on = (b->drag_coefficient > 0.0) || (b->heat_coefficient > 0.0) || (b->vapor_coefficient > 0.0);
     ctx->has_bulk = ctx->bulk_const_on || ctx->sl_on;
@@ -612,6 +617,8 @@ extern "C" int bz_set_surface_layer(bz_ctx *ctx, const bz_surface_layer *L)
         else if (ctx->dg.formulation != 0) why = "the StaticEnergy formulation is not built";
         else if (ctx->dg.microphysics == 2) why = "DCMIP2016 Kessler microphysics is not built";
         else if (ctx->slab_mode) why = "y-slab contexts are not built (the filtered fields would need neighbour rows in the exchange)";
+        else if (ctx->fl_on) why = "the surface q^v+ is the Clausius-Clapeyron expression, and the context's saturation adjustment runs on a FlatauPolynomial "
+                                   "(bz_set_saturation_vapor_pressure_polynomial)";
         else if (L->filtered && L->filter_height_set) why = "a filter reference height other than the first cell centre is not built";
         else if (L->filtered && (ctx->dg.bounded_x || ctx->dg.bounded_y)) why = "filtered surface fields on a Bounded x or y are not built";
         if (why) { ctx->last_error = std::string("bz_set_surface_layer: ") + why; return BZ_ERR_UNSUPPORTED; }

@@ -135,8 +135,10 @@ struct PDFields {
     long long lsum_P;
 };
 
-template <int SA>       // 0: no microphysics, 1: warm-phase saturation adjustment, 2: Kessler condensate species, 3: mixed-phase saturation adjustment
-__global__ __launch_bounds__(256) void k_project_diagnose(DevGrid g, PDFields F, double dt, int gx, int nk)
+// SA  0: no microphysics, 1: warm-phase saturation adjustment, 2: Kessler condensate species, 3: mixed-phase saturation adjustment
+// FL  the FlatauPolynomial instantiation of SA = 1 and 3 (bz_set_saturation_vapor_pressure_polynomial)
+template <int SA, bool FL = false>
+__global__ __launch_bounds__(256) void k_project_diagnose(DevGrid g, PDFields F, double dt, int gx, int nk, const double *fl)
 {
     int bx, j, k;
     bz_stream_block(gx, g.Ny, nk, bx, j, k);
@@ -182,8 +184,8 @@ __global__ __launch_bounds__(256) void k_project_diagnose(DevGrid g, PDFields F,
         qcl = g.rqcl_field[n] / rc;
         qr = g.rqr_field[n] / rc;
         qvv = q;
-    } else if (SA == 1) T = bz_sa_diagnose(g, th, q, g.p_r[k], qvv, qll);
-    else if (SA == 3) T = bz_mp_diagnose(g, th, q, g.p_r[k], qvv, qll, qii);
+    } else if (SA == 1) T = bz_sa_diagnose<FL>(g, th, q, g.p_r[k], qvv, qll, ColPtr(fl));
+    else if (SA == 3) T = bz_mp_diagnose<FL>(g, th, q, g.p_r[k], qvv, qll, qii, ColPtr(fl));
     else T = (g.formulation == 1) ? (th - g.g * g.zc[k]) / cpm : bz_exner_factor(g, k, q, cpm) * th;
 
     if (F.lsum) {      // the stage's horizontal sums ride on the values in registers (a separate pass reads the four arrays again)
@@ -509,14 +511,19 @@ int bzi_project_diagnose(bz_ctx *ctx, const bz_state *s, double dt, const double
     F.lsum = level_sums ? bzi_level_sum_rows(ctx, &F.lsum_P) : nullptr;
     if (!F.lsum) F.lsum_P = 0;
     dim3 grid((unsigned)((long long)gx * g.Ny * nk)), block(256);
+    const double *fl = bzi_flatau(ctx);
     if (g.microphysics == 2)
-        hipLaunchKernelGGL((k_project_diagnose<2>), grid, block, 0, ctx->stream, g, F, dt, gx, nk);
+        hipLaunchKernelGGL((k_project_diagnose<2>), grid, block, 0, ctx->stream, g, F, dt, gx, nk, fl);
+    else if (g.microphysics == 1 && fl && g.sa_mixed)
+        hipLaunchKernelGGL((k_project_diagnose<3, true>), grid, block, 0, ctx->stream, g, F, dt, gx, nk, fl);
+    else if (g.microphysics == 1 && fl)
+        hipLaunchKernelGGL((k_project_diagnose<1, true>), grid, block, 0, ctx->stream, g, F, dt, gx, nk, fl);
     else if (g.microphysics == 1 && g.sa_mixed)
-        hipLaunchKernelGGL((k_project_diagnose<3>), grid, block, 0, ctx->stream, g, F, dt, gx, nk);
+        hipLaunchKernelGGL((k_project_diagnose<3>), grid, block, 0, ctx->stream, g, F, dt, gx, nk, fl);
     else if (g.microphysics == 1)
-        hipLaunchKernelGGL((k_project_diagnose<1>), grid, block, 0, ctx->stream, g, F, dt, gx, nk);
+        hipLaunchKernelGGL((k_project_diagnose<1>), grid, block, 0, ctx->stream, g, F, dt, gx, nk, fl);
     else
-        hipLaunchKernelGGL((k_project_diagnose<0>), grid, block, 0, ctx->stream, g, F, dt, gx, nk);
+        hipLaunchKernelGGL((k_project_diagnose<0>), grid, block, 0, ctx->stream, g, F, dt, gx, nk, fl);
     BZ_LAUNCH_CHECK();
     return BZ_OK;
 }

@@ -20,9 +20,11 @@
 // writes rho theta, rho q^v and (where water condensed) precipitation_rate in place: 7 compulsory words per cell.  No LDS, no barrier, no
 // halo writes (the update_state! that follows fills them).  A subsaturated cell leaves bz_ds_adjust before the secant loop.  q^v of the
 // microphysical fields is the model's specific-moisture array: update_state! refreshes it (rho q^v / rho with the new total density).
+// FL: the FlatauPolynomial instantiation (bz_set_saturation_vapor_pressure_polynomial), selected by the host
+template <bool FL = false>
 __global__ __launch_bounds__(256) void k_instantaneous_precipitation(DevGrid g, const double *__restrict__ rho, const double *__restrict__ rho_d,
                                                                      double *__restrict__ rth, double *__restrict__ rq,
-                                                                     double *__restrict__ prate, double dt, double nabstol, int nmaxiter)
+                                                                     double *__restrict__ prate, double dt, double nabstol, int nmaxiter, const double *fl)
 {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= g.Nx) return;
@@ -32,7 +34,7 @@ __global__ __launch_bounds__(256) void k_instantaneous_precipitation(DevGrid g, 
     const double th0 = rth[n] / rd;           // rho theta is dry-coupled
     if (th0 == 0.0) return;                   // is_absolute_zero: nothing to adjust (and no temperature to divide by)
     double qv, ql;
-    const double T = bz_ds_adjust(g, th0, qt, r, nabstol, nmaxiter, qv, ql);
+    const double T = bz_ds_adjust<FL>(g, th0, qt, r, nabstol, nmaxiter, qv, ql, ColPtr(fl));
     // rain-out: the vapour-only parcel keeps T (with_temperature of the state without condensate, L = 0)
     const double qd = 1.0 - qv;
     const double Rm = qd * g.Rd + qv * g.Rv;
@@ -93,8 +95,13 @@ int bzi_instantaneous_precipitation(bz_ctx *ctx, const bz_compressible_state *s,
 {
     const DevGrid &g = ctx->dg;
     ProfileScope ps(ctx, "instantaneous_precipitation");
-    hipLaunchKernelGGL(k_instantaneous_precipitation, dim3((g.Nx + 255) / 256, g.Ny, g.Nz), dim3(256), 0, ctx->stream, g, s->rho, s->rho_d,
-                       s->rho_theta, s->rho_q, ctx->ip_precipitation_rate, dt, ctx->se.newton_abstol, ctx->se.newton_maxiter);
+    const double *fl = bzi_flatau(ctx);
+    if (fl)
+        hipLaunchKernelGGL(k_instantaneous_precipitation<true>, dim3((g.Nx + 255) / 256, g.Ny, g.Nz), dim3(256), 0, ctx->stream, g, s->rho, s->rho_d,
+                           s->rho_theta, s->rho_q, ctx->ip_precipitation_rate, dt, ctx->se.newton_abstol, ctx->se.newton_maxiter, fl);
+    else
+        hipLaunchKernelGGL(k_instantaneous_precipitation<false>, dim3((g.Nx + 255) / 256, g.Ny, g.Nz), dim3(256), 0, ctx->stream, g, s->rho, s->rho_d,
+                           s->rho_theta, s->rho_q, ctx->ip_precipitation_rate, dt, ctx->se.newton_abstol, ctx->se.newton_maxiter, fl);
     BZ_LAUNCH_CHECK();
     return BZ_OK;
 }

@@ -253,8 +253,59 @@ __device__ __forceinline__ double bz_kessler_T(const DevGrid &g, double th, doub
     const double cpm = qd * g.cpd + qv * g.cpv + ql * g.sa_cl;
     return pow(pr / g.pst, (qd * g.Rd + qv * g.Rv) / cpm) * th + (g.sa_Ll * ql) / cpm;
 }
-__device__ __forceinline__ double bz_sa_psat(const DevGrid &g, double T)
+// saturation_vapor_pressure = FlatauPolynomial(...) (flatau_polynomial.jl:93-122): p^v+ = sum_n a_n x^n, n = 0..8, x = max(T - T_r, -delta T),
+// over liquid and over ice; on the mixed surface the two polynomials blended by lambda (not blended coefficients, as the Clausius-Clapeyron
+// mixed surface does).  evalpoly on a tuple is a Horner chain of muladd: eight dependent FMAs from the highest coefficient down, instead of the
+// pow and the exp of bz_sa_psat.  The table (bz_ctx::d_flatau: liquid a0..a8, ice a0..a8, T_r, delta T) is a kernel ARGUMENT of the six kernels
+// that have a polynomial instantiation, not a member of DevGrid: every other kernel of the library keeps its argument block.  It is read with
+// constant indices through the constant address space: scalar loads, the coefficients are scalar operands of the FMAs and cost no vector
+// registers.  bz_fl_table makes the pointer opaque at every evaluation, so the loads stay where the chain is: hoisted out of the secant loop the
+// twenty values would sit in forty scalar registers for the whole kernel, and the kernels that are already at their scalar budget would spill.
+// The mixed surface runs its two chains interleaved: they are independent, so one fills the other's FMA latency.
+constexpr int BZ_FL_LIQUID = 0, BZ_FL_ICE = 9, BZ_FL_TR = 18, BZ_FL_DT = 19, BZ_FL_COUNT = 20;
+__device__ __forceinline__ ColPtr bz_fl_table(ColPtr fl)
 {
+    const double *t = fl.p;
+    asm volatile("" : "+s"(t));
+    return ColPtr(t);
+}
+__device__ __forceinline__ double bz_fl_x(ColPtr t, double T) { return fmax(T - t[BZ_FL_TR], -t[BZ_FL_DT]); }
+template <int SURFACE>
+__device__ __forceinline__ double bz_fl_chain(ColPtr t, double x)
+{
+    double p = t[SURFACE + 8];
+#pragma unroll
+    for (int n = 7; n >= 0; --n) p = fma(p, x, t[SURFACE + n]);
+    return p;
+}
+__device__ __forceinline__ double bz_fl_psat_liquid(ColPtr fl, double T)
+{
+    const ColPtr t = bz_fl_table(fl);
+    return bz_fl_chain<BZ_FL_LIQUID>(t, bz_fl_x(t, T));
+}
+__device__ __forceinline__ double bz_fl_psat_ice(ColPtr fl, double T)
+{
+    const ColPtr t = bz_fl_table(fl);
+    return bz_fl_chain<BZ_FL_ICE>(t, bz_fl_x(t, T));
+}
+__device__ __forceinline__ double bz_fl_psat_mixed(ColPtr fl, double T, double lam)
+{
+    const ColPtr t = bz_fl_table(fl);
+    const double x = bz_fl_x(t, T);
+    double pl = t[BZ_FL_LIQUID + 8], pi = t[BZ_FL_ICE + 8];
+#pragma unroll
+    for (int n = 7; n >= 0; --n) {
+        pl = fma(pl, x, t[BZ_FL_LIQUID + n]);
+        pi = fma(pi, x, t[BZ_FL_ICE + n]);
+    }
+    return lam * pl + (1.0 - lam) * pi;
+}
+// FL (here and in every function below that evaluates p^v+): the polynomial instantiation, chosen by the host where it launches the kernel;
+// fl: its table (the last, defaulted argument: the Clausius-Clapeyron callers pass none and their instantiations do not read it)
+template <bool FL = false>
+__device__ __forceinline__ double bz_sa_psat(const DevGrid &g, double T, ColPtr fl = ColPtr())
+{
+    if constexpr (FL) return bz_fl_psat_liquid(fl, T);
     return g.sa_ptr * pow(T / g.sa_Ttr, g.sa_dc / g.Rv) * exp((1.0 / g.sa_Ttr - 1.0 / T) * g.sa_L0 / g.Rv);
 }
 __device__ __forceinline__ double bz_sa_T(const DevGrid &g, double th, double qv, double ql, double pr)
@@ -263,40 +314,43 @@ __device__ __forceinline__ double bz_sa_T(const DevGrid &g, double th, double qv
     const double cpm = qd * g.cpd + qv * g.cpv + ql * g.sa_cl;
     return pow(pr / g.pst, (qd * g.Rd + qv * g.Rv) / cpm) * th + (g.sa_Ll * ql) / cpm;
 }
-__device__ __forceinline__ void bz_sa_adjust(const DevGrid &g, double T, double qt, double pr, double &qv, double &ql)
+template <bool FL = false>
+__device__ __forceinline__ void bz_sa_adjust(const DevGrid &g, double T, double qt, double pr, double &qv, double &ql, ColPtr fl = ColPtr())
 {
-    const double ps = bz_sa_psat(g, T);
+    const double ps = bz_sa_psat<FL>(g, T, fl);
     const double qs = (g.Rd / g.Rv) * (1.0 - qt) * ps / (pr - ps);
     ql = fmax(0.0, qt - qs);
     qv = qt - ql;
 }
-__device__ __forceinline__ double bz_sa_residual(const DevGrid &g, double T, double th, double qt, double pr)
+template <bool FL = false>
+__device__ __forceinline__ double bz_sa_residual(const DevGrid &g, double T, double th, double qt, double pr, ColPtr fl = ColPtr())
 {
     double qv, ql;
-    bz_sa_adjust(g, T, qt, pr, qv, ql);
+    bz_sa_adjust<FL>(g, T, qt, pr, qv, ql, fl);
     return T - bz_sa_T(g, th, qv, ql, pr);
 }
-__device__ __forceinline__ double bz_sa_diagnose(const DevGrid &g, double th, double qt, double pr, double &qv, double &ql)
+template <bool FL = false>
+__device__ __forceinline__ double bz_sa_diagnose(const DevGrid &g, double th, double qt, double pr, double &qv, double &ql, ColPtr fl = ColPtr())
 {
     qv = qt; ql = 0.0;
     const double T1 = bz_sa_T(g, th, qt, 0.0, pr);
     if (th == 0.0) return T1;
     const double rho1 = pr / (((1.0 - qt) * g.Rd + qt * g.Rv) * T1);
-    if (qt <= bz_sa_psat(g, T1) / (rho1 * g.Rv * T1)) return T1;
+    if (qt <= bz_sa_psat<FL>(g, T1, fl) / (rho1 * g.Rv * T1)) return T1;
     double qv1, ql1;
-    bz_sa_adjust(g, T1, qt, pr, qv1, ql1);
+    bz_sa_adjust<FL>(g, T1, qt, pr, qv1, ql1, fl);
     const double dT = (g.sa_Ll * ql1) / ((1.0 - (qv1 + ql1)) * g.cpd + qv1 * g.cpv + ql1 * g.sa_cl);
     double x1 = T1, x2 = T1 + fmax(0.01, dT / 2.0);
-    double r1 = bz_sa_residual(g, x1, th, qt, pr), r2 = bz_sa_residual(g, x2, th, qt, pr);
+    double r1 = bz_sa_residual<FL>(g, x1, th, qt, pr, fl), r2 = bz_sa_residual<FL>(g, x2, th, qt, pr, fl);
     for (int it = 0; it < g.sa_maxiter && fabs(r2) > g.sa_abstol; ++it) {
         double s = (x2 - x1) / (r2 - r1);
         const bool valid = isfinite(s);
         s = valid ? s : 0.0;
         x1 = x2; r1 = r2;
         x2 -= r2 * s;
-        r2 = valid ? bz_sa_residual(g, x2, th, qt, pr) : 0.0;
+        r2 = valid ? bz_sa_residual<FL>(g, x2, th, qt, pr, fl) : 0.0;
     }
-    bz_sa_adjust(g, x2, qt, pr, qv, ql);
+    bz_sa_adjust<FL>(g, x2, qt, pr, qv, ql, fl);
     return bz_sa_T(g, th, qv, ql, pr);
 }
 // Mixed-phase saturation adjustment (equilibrium = MixedPhaseEquilibrium(T^f, T^h)): the inversion above on the temperature-dependent
@@ -310,8 +364,10 @@ __device__ __forceinline__ double bz_mp_lambda(const DevGrid &g, double T)
     const double Tc = T > g.sa_Tf ? g.sa_Tf : (T < g.sa_Th ? g.sa_Th : T);
     return (Tc - g.sa_Th) / (g.sa_Tf - g.sa_Th);
 }
-__device__ __forceinline__ double bz_mp_psat(const DevGrid &g, double T, double lam)
+template <bool FL = false>
+__device__ __forceinline__ double bz_mp_psat(const DevGrid &g, double T, double lam, ColPtr fl = ColPtr())
 {
+    if constexpr (FL) return bz_fl_psat_mixed(fl, T, lam);
     const double dc = lam * g.sa_dc + (1.0 - lam) * g.sa_dci;
     const double L0 = lam * g.sa_L0 + (1.0 - lam) * g.sa_L0i;
     return g.sa_ptr * pow(T / g.sa_Ttr, dc / g.Rv) * exp((1.0 / g.sa_Ttr - 1.0 / T) * L0 / g.Rv);
@@ -326,43 +382,46 @@ __device__ __forceinline__ double bz_mp_T(const DevGrid &g, double th, double qv
     const double cpm = qd * g.cpd + qv * g.cpv + ql * g.sa_cl + qi * g.sa_ci;
     return pow(pr / g.pst, (qd * g.Rd + qv * g.Rv) / cpm) * th + (g.sa_Ll * ql + g.sa_Li * qi) / cpm;
 }
-__device__ __forceinline__ void bz_mp_adjust(const DevGrid &g, double T, double qt, double pr, double &qv, double &ql, double &qi)
+template <bool FL = false>
+__device__ __forceinline__ void bz_mp_adjust(const DevGrid &g, double T, double qt, double pr, double &qv, double &ql, double &qi, ColPtr fl = ColPtr())
 {
     const double lam = bz_mp_lambda(g, T);
-    const double ps = bz_mp_psat(g, T, lam);
+    const double ps = bz_mp_psat<FL>(g, T, lam, fl);
     const double qs = (g.Rd / g.Rv) * (1.0 - qt) * ps / (pr - ps);
     const double qc = fmax(0.0, qt - qs);
     qv = qt - qc;
     ql = lam * qc;
     qi = (1.0 - lam) * qc;
 }
-__device__ __forceinline__ double bz_mp_residual(const DevGrid &g, double T, double th, double qt, double pr)
+template <bool FL = false>
+__device__ __forceinline__ double bz_mp_residual(const DevGrid &g, double T, double th, double qt, double pr, ColPtr fl = ColPtr())
 {
     double qv, ql, qi;
-    bz_mp_adjust(g, T, qt, pr, qv, ql, qi);
+    bz_mp_adjust<FL>(g, T, qt, pr, qv, ql, qi, fl);
     return T - bz_mp_T(g, th, qv, ql, qi, pr);
 }
-__device__ __forceinline__ double bz_mp_diagnose(const DevGrid &g, double th, double qt, double pr, double &qv, double &ql, double &qi)
+template <bool FL = false>
+__device__ __forceinline__ double bz_mp_diagnose(const DevGrid &g, double th, double qt, double pr, double &qv, double &ql, double &qi, ColPtr fl = ColPtr())
 {
     qv = qt; ql = 0.0; qi = 0.0;
     const double T1 = bz_sa_T(g, th, qt, 0.0, pr);
     if (th == 0.0) return T1;
     const double rho1 = pr / (((1.0 - qt) * g.Rd + qt * g.Rv) * T1);
-    if (qt <= bz_mp_psat(g, T1, bz_mp_lambda(g, T1)) / (rho1 * g.Rv * T1)) return T1;
+    if (qt <= bz_mp_psat<FL>(g, T1, bz_mp_lambda(g, T1), fl) / (rho1 * g.Rv * T1)) return T1;
     double qv1, ql1, qi1;
-    bz_mp_adjust(g, T1, qt, pr, qv1, ql1, qi1);
+    bz_mp_adjust<FL>(g, T1, qt, pr, qv1, ql1, qi1, fl);
     const double dT = (g.sa_Ll * ql1 + g.sa_Li * qi1) / bz_mp_cpm(g, qv1, ql1, qi1);
     double x1 = T1, x2 = T1 + fmax(0.01, dT / 2.0);
-    double r1 = bz_mp_residual(g, x1, th, qt, pr), r2 = bz_mp_residual(g, x2, th, qt, pr);
+    double r1 = bz_mp_residual<FL>(g, x1, th, qt, pr, fl), r2 = bz_mp_residual<FL>(g, x2, th, qt, pr, fl);
     for (int it = 0; it < g.sa_maxiter && fabs(r2) > g.sa_abstol; ++it) {
         double s = (x2 - x1) / (r2 - r1);
         const bool valid = isfinite(s);
         s = valid ? s : 0.0;
         x1 = x2; r1 = r2;
         x2 -= r2 * s;
-        r2 = valid ? bz_mp_residual(g, x2, th, qt, pr) : 0.0;
+        r2 = valid ? bz_mp_residual<FL>(g, x2, th, qt, pr, fl) : 0.0;
     }
-    bz_mp_adjust(g, x2, qt, pr, qv, ql, qi);
+    bz_mp_adjust<FL>(g, x2, qt, pr, qv, ql, qi, fl);
     return bz_mp_T(g, th, qv, ql, qi, pr);
 }
 // ---- density-based liquid-ice potential temperature state of CompressibleDynamics (LiquidIceDensityState) ----------------------------
@@ -385,9 +444,10 @@ __device__ __forceinline__ double bz_ds_temperature(const DevGrid &g, double th,
     return T;
 }
 // saturated_density_residual (saturation_adjustment.jl:236-253): theta^li(T) - theta0 of the state saturated at its own density
-__device__ __forceinline__ double bz_ds_residual(const DevGrid &g, double T, double th0, double rho, double qt, double &qv, double &ql)
+template <bool FL = false>
+__device__ __forceinline__ double bz_ds_residual(const DevGrid &g, double T, double th0, double rho, double qt, double &qv, double &ql, ColPtr fl = ColPtr())
 {
-    const double qs = bz_sa_psat(g, T) / (rho * g.Rv * T);
+    const double qs = bz_sa_psat<FL>(g, T, fl) / (rho * g.Rv * T);
     ql = fmax(0.0, qt - qs);
     qv = qt - ql;
     const double qd = 1.0 - (qv + ql);
@@ -398,28 +458,29 @@ __device__ __forceinline__ double bz_ds_residual(const DevGrid &g, double T, dou
     return (T - L) * pow(g.pst / p, Rm / cpm) - th0;
 }
 // adjust_thermodynamic_state(::LiquidIceDensityState, ::SaturationAdjustment) (saturation_adjustment.jl:264-301) -> T; sets qv, ql
+template <bool FL = false>
 __device__ __forceinline__ double bz_ds_adjust(const DevGrid &g, double th, double qt, double rho, double nabstol, int nmaxiter,
-                                               double &qv, double &ql)
+                                               double &qv, double &ql, ColPtr fl = ColPtr())
 {
     qv = qt; ql = 0.0;
     if (th == 0.0) return 0.0;
     const double T1 = bz_ds_temperature(g, th, qt, 0.0, rho, nabstol, nmaxiter);
-    if (qt <= bz_sa_psat(g, T1) / (rho * g.Rv * T1)) return T1;
+    if (qt <= bz_sa_psat<FL>(g, T1, fl) / (rho * g.Rv * T1)) return T1;
     double qv1, ql1;
-    bz_ds_residual(g, T1, th, rho, qt, qv1, ql1);
+    bz_ds_residual<FL>(g, T1, th, rho, qt, qv1, ql1, fl);
     const double dT = (g.sa_Ll * ql1) / ((1.0 - (qv1 + ql1)) * g.cpd + qv1 * g.cpv + ql1 * g.sa_cl);
     double x1 = T1, x2 = T1 + fmax(0.01, dT / 2.0);
     double a, b;
-    double r1 = bz_ds_residual(g, x1, th, rho, qt, a, b), r2 = bz_ds_residual(g, x2, th, rho, qt, a, b);
+    double r1 = bz_ds_residual<FL>(g, x1, th, rho, qt, a, b, fl), r2 = bz_ds_residual<FL>(g, x2, th, rho, qt, a, b, fl);
     for (int it = 0; it < g.sa_maxiter && fabs(r2) > g.sa_abstol; ++it) {
         double s = (x2 - x1) / (r2 - r1);
         const bool valid = isfinite(s);
         s = valid ? s : 0.0;
         x1 = x2; r1 = r2;
         x2 -= r2 * s;
-        r2 = valid ? bz_ds_residual(g, x2, th, rho, qt, a, b) : 0.0;
+        r2 = valid ? bz_ds_residual<FL>(g, x2, th, rho, qt, a, b, fl) : 0.0;
     }
-    bz_ds_residual(g, x2, th, rho, qt, qv, ql);
+    bz_ds_residual<FL>(g, x2, th, rho, qt, qv, ql, fl);
     return bz_ds_temperature(g, th, qv, ql, rho, nabstol, nmaxiter);
 }
 #endif
@@ -603,6 +664,10 @@ struct bz_ctx {
     // negative_moisture_correction of BulkMicrophysics (bz_set_negative_moisture_correction, bz_negative_moisture.hip): runs at the head of every
     // update_state! while a SaturationAdjustment is attached (dg.microphysics == 1)
     bool has_nmc = false;
+    // saturation_vapor_pressure = FlatauPolynomial(...) (bz_set_saturation_vapor_pressure_polynomial): the device table (BZ_FL_COUNT values) the
+    // polynomial instantiations take as a kernel argument; fl_on selects them (bzi_flatau)
+    double *d_flatau = nullptr;
+    bool fl_on = false;
     bz_negative_moisture_correction nmc;
     // forcing / Coriolis / bottom-flux stack (bz_set_forcings, bz_forcing.hip)
     bool has_relaxation = false;      // bz_set_relaxation: [rate target](u v w theta q), Nz + 1 entries each
@@ -863,6 +928,8 @@ int bzi_tendencies_fused_rk(bz_ctx *ctx, const bz_state *s, const bz_prognostic 
 int bzi_create(bz_ctx **out, const bz_grid *grid, const bz_constants *constants, const bz_reference_state *ref,
                int weno_order, int y_nranks, int y_rank, bool slab_mode, bool compressible = false);
 void bzi_compressible_teardown(bz_ctx *ctx);
+// the table of the polynomial instantiations, or null on a Clausius-Clapeyron context: the one predicate every launch site reads
+static inline const double *bzi_flatau(const bz_ctx *ctx) { return ctx->fl_on ? ctx->d_flatau : nullptr; }
 // bz_cmp_surface_flux.hip: compute_flux_bc_tendencies! of a compressible context (a no-op without an attached set)
 int bzi_cmp_surface_fluxes(bz_ctx *ctx, const bz_compressible_state *s, const bz_compressible_prognostic *G);
 void bzi_cmp_surface_flux_teardown(bz_ctx *ctx);

@@ -24,11 +24,13 @@ __global__ __launch_bounds__(TX *TY) void k_velocities(DevGrid g, double *__rest
 
 // ---- _compute_auxiliary_thermodynamic_variables! (:256-292) with
 // potential_temperature_formulation.jl:115-145 and Thermodynamics/dynamic_states.jl:31-58.
-template <bool MIX = false>      // MIX: the mixed-phase instantiation (bz_set_mixed_phase_equilibrium), selected by the host
+// MIX: the mixed-phase instantiation (bz_set_mixed_phase_equilibrium); FL: the FlatauPolynomial instantiation
+// (bz_set_saturation_vapor_pressure_polynomial); both selected by the host
+template <bool MIX = false, bool FL = false>
 __global__ __launch_bounds__(TX *TY) void k_thermo(DevGrid g, double *__restrict__ theta,
                                                   double *__restrict__ qv, double *__restrict__ T,
                                                   const double *__restrict__ rtheta,
-                                                  const double *__restrict__ rq)
+                                                  const double *__restrict__ rq, const double *fl)
 {
     int i = blockIdx.x * TX + threadIdx.x, j = blockIdx.y * TY + threadIdx.y, k = blockIdx.z;
     if (i >= g.Nx || j >= g.Ny) return;
@@ -59,9 +61,9 @@ __global__ __launch_bounds__(TX *TY) void k_thermo(DevGrid g, double *__restrict
         double qvv, qll;
         if constexpr (MIX) {
             double qii;
-            T[n] = bz_mp_diagnose(g, th, q, g.p_r[k], qvv, qll, qii);
+            T[n] = bz_mp_diagnose<FL>(g, th, q, g.p_r[k], qvv, qll, qii, ColPtr(fl));
             g.qi_field[n] = qii;
-        } else T[n] = bz_sa_diagnose(g, th, q, g.p_r[k], qvv, qll);
+        } else T[n] = bz_sa_diagnose<FL>(g, th, q, g.p_r[k], qvv, qll, ColPtr(fl));
         g.qv_field[n] = qvv;
         g.ql_field[n] = qll;
         return;
@@ -168,12 +170,20 @@ extern "C" int bz_compute_auxiliary_thermodynamic_variables(bz_ctx *ctx, const b
     const DevGrid &g = ctx->dg;
     {
         ProfileScope ps(ctx, "compute_auxiliary_thermodynamic_variables");
-        if (g.sa_mixed)
+        const double *fl = bzi_flatau(ctx);
+        if (fl && g.microphysics == 1) {
+            if (g.sa_mixed)
+                hipLaunchKernelGGL((k_thermo<true, true>), cell_grid(g, g.Nz), dim3(TX, TY), 0, ctx->stream, g, s->theta, s->q, s->T,
+                                   s->rho_theta, s->rho_q, fl);
+            else
+                hipLaunchKernelGGL((k_thermo<false, true>), cell_grid(g, g.Nz), dim3(TX, TY), 0, ctx->stream, g, s->theta, s->q, s->T,
+                                   s->rho_theta, s->rho_q, fl);
+        } else if (g.sa_mixed)
             hipLaunchKernelGGL(k_thermo<true>, cell_grid(g, g.Nz), dim3(TX, TY), 0, ctx->stream, g, s->theta, s->q, s->T,
-                               s->rho_theta, s->rho_q);
+                               s->rho_theta, s->rho_q, fl);
         else
             hipLaunchKernelGGL(k_thermo<false>, cell_grid(g, g.Nz), dim3(TX, TY), 0, ctx->stream, g, s->theta, s->q, s->T,
-                               s->rho_theta, s->rho_q);
+                               s->rho_theta, s->rho_q, fl);
         BZ_LAUNCH_CHECK();
     }
     double *f[6] = {s->T, s->q, s->theta, g.qv_field, g.microphysics == 2 ? g.qcl_field : g.ql_field, g.microphysics == 2 ? g.qr_field : g.qi_field};

@@ -327,6 +327,7 @@ class LibrarySlabAtmosphereModel(AtmosphereModel):
         from .model import PrescribedDynamics
         if isinstance(kw.get("dynamics"), PrescribedDynamics):
             raise NotImplementedError("AtmosphereModel(dynamics = PrescribedDynamics(...)): y-slab (distributed) models are not implemented")
+        _context.refuse_flatau_polynomial(thermodynamic_constants, type(self).__name__, "y-slab models evaluate the Clausius-Clapeyron expression")
         grid = _context.slab_grid(global_grid, rank, world)
         if transport == "torch":
             raise ValueError('LibrarySlabAtmosphereModel runs on the library-owned communicator: transport "rccl" or "local:<name>"')
@@ -399,6 +400,7 @@ class SlabAtmosphereModel(SlabStepper, _context.ContextOwner):
         _context.check_slab_topology(global_grid)      # (slab_grid checks it again: here only so that it still comes before the advection check)
         if advection is None or getattr(advection, "order", None) != 5:
             raise NotImplementedError("the HIP path requires advection=WENO(order=5)")
+        _context.refuse_flatau_polynomial(thermodynamic_constants, type(self).__name__, "y-slab models evaluate the Clausius-Clapeyron expression")
         grid = _context.slab_grid(global_grid, rank, world)
         if not torch.cuda.is_available():
             raise RuntimeError("SlabAtmosphereModel needs a GPU: the HIP path has no CPU fallback")

@@ -381,6 +381,13 @@ class AtmosphereModel(_context.ContextOwner):
         if any("Slab" in k.__name__ for k in type(self).__mro__):      # the y-slab models of distributed.py
             _context.refuse_mixed_phase(microphysics, type(self).__name__, "the halo exchanges of y-slab models carry qᵛ and qˡ only")
         _context.check_mixed_phase_model(microphysics, thermodynamic_constants, forcing, boundary_conditions)
+        # FlatauPolynomial constants: single-device anelastic models; the places that hard-wire Clausius-Clapeyron refuse by name
+        if any("Slab" in k.__name__ for k in type(self).__mro__):
+            _context.refuse_flatau_polynomial(thermodynamic_constants, type(self).__name__, "y-slab models evaluate the Clausius-Clapeyron expression")
+        if kin:
+            _context.refuse_flatau_polynomial(thermodynamic_constants, "AtmosphereModel(dynamics = PrescribedDynamics(...))",
+                                              "the kinematic driver evaluates the Clausius-Clapeyron expression")
+        _context.check_flatau_anelastic(thermodynamic_constants, boundary_conditions)
         self.microphysics = microphysics
         if self._kessler:
             _context.check_kessler_constants(thermodynamic_constants)
@@ -458,6 +465,7 @@ class AtmosphereModel(_context.ContextOwner):
         elif microphysics is not None:
             _context.attach_saturation_adjustment(self, fld)
             _context.attach_negative_moisture_correction(self)      # of a BulkMicrophysics
+            _context.attach_flatau_polynomial(self)                 # saturation_vapor_pressure = FlatauPolynomial() of the constants
         if self.tracers:
             arr = (_lib.bz_tracer_fields * len(self.tracers))()
             for t, n in enumerate(self.tracers):
@@ -708,6 +716,8 @@ def set_(model, enforce_mass_conservation=True, balancer=None, **kw):
         if key in ("T", "ℋ") and (model.formulation != "LiquidIcePotentialTemperature" or getattr(model, "_kessler", False)):
             raise NotImplementedError(f"set!(model; {name}) is implemented for the potential-temperature formulation "
                                       "(microphysics nothing or SaturationAdjustment)")
+        if key in ("T", "ℋ"):      # set-up arithmetic on Clausius-Clapeyron constants (ℋ evaluates pᵛ⁺; T is refused with it: one rule for both)
+            _context.refuse_flatau_polynomial(model.thermodynamic_constants, f"set!(model; {name})", "qᵛ⁺ from ℋ is the Clausius-Clapeyron expression")
         if key in ("T", "ℋ"):      # both conversions below know the liquid phase only
             _context.refuse_mixed_phase(model.microphysics, f"set!(model; {name})", "θ from T and qᵛ⁺ from ℋ are formed without qⁱ and over the liquid surface")
         if key == "T":

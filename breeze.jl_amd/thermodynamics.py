@@ -5,6 +5,33 @@ Pure numpy Float64; evaluated once per model."""
 import numpy as np
 
 
+class FlatauPolynomial:
+    """FlatauPolynomial(; liquid_coefficients, ice_coefficients, reference_temperature=273.16, minimum_temperature_offset=80)
+    (src/Thermodynamics/flatau_polynomial.jl:61-77): the eighth-order fits of Flatau et al. (1992) to the saturation vapour pressure over
+    liquid and over ice, pᵛ⁺ = Σₙ aₙ xⁿ with x = max(T - Tᵣ, -δT); coefficients in Pa, a₀ first.  The defaults are their relative-error-norm
+    sets (Tables 3 and 4).  Passed as ThermodynamicConstants(saturation_vapor_pressure = FlatauPolynomial()), it replaces the Clausius-Clapeyron
+    expression inside SaturationAdjustment (warm and mixed phase) and InstantaneousPrecipitation on the single-device models."""
+
+    LIQUID = (611.239921, 44.3987641, 1.42986287, 2.64847430e-2, 3.02950461e-4, 2.06739458e-6, 6.40689451e-9, -9.52447341e-12,
+              -9.76195544e-14)
+    ICE = (611.147274, 50.3160820, 1.88439774, 4.20895665e-2, 6.15021634e-4, 6.02588177e-6, 3.85852041e-8, 1.46898966e-10,
+           2.52751365e-13)
+
+    def __init__(self, liquid_coefficients=LIQUID, ice_coefficients=ICE, reference_temperature=273.16, minimum_temperature_offset=80):
+        self.liquid_coefficients = tuple(float(a) for a in liquid_coefficients)
+        self.ice_coefficients = tuple(float(a) for a in ice_coefficients)
+        for name, a in (("liquid_coefficients", self.liquid_coefficients), ("ice_coefficients", self.ice_coefficients)):
+            if len(a) != 9:
+                raise ValueError(f"FlatauPolynomial: {name} takes nine coefficients (a₀ … a₈ of the eighth-order polynomial), got {len(a)}")
+        self.reference_temperature = float(reference_temperature)
+        self.minimum_temperature_offset = float(minimum_temperature_offset)
+        if not all(np.isfinite(self.liquid_coefficients + self.ice_coefficients + (self.reference_temperature, self.minimum_temperature_offset))):
+            raise ValueError("FlatauPolynomial: coefficients, reference_temperature and minimum_temperature_offset must be finite")
+
+    def __repr__(self):
+        return f"FlatauPolynomial(Tᵣ={self.reference_temperature}, order={len(self.liquid_coefficients) - 1})"
+
+
 class ThermodynamicConstants:
     def __init__(self, molar_gas_constant=8.314462618, gravitational_acceleration=9.81,
                  energy_reference_temperature=273.15, triple_point_temperature=273.16,
@@ -12,7 +39,7 @@ class ThermodynamicConstants:
                  vapor_molar_mass=0.018015, vapor_heat_capacity=1850,
                  liquid_reference_latent_heat=2500800, liquid_heat_capacity=4181,
                  ice_reference_latent_heat=2834000, ice_heat_capacity=2108, saturation_vapor_pressure=None):
-        # saturation_vapor_pressure: None = ClausiusClapeyron (default) or a TetensFormula (breeze.jl_amd/microphysics.py)
+        # saturation_vapor_pressure: None = ClausiusClapeyron (default), a TetensFormula (breeze.jl_amd/microphysics.py) or a FlatauPolynomial
         self.saturation_vapor_pressure = saturation_vapor_pressure
         self.molar_gas_constant = float(molar_gas_constant)
         self.gravitational_acceleration = float(gravitational_acceleration)

@@ -145,6 +145,21 @@ typedef struct bz_mixed_phase_equilibrium {
     double ice_latent_heat, ice_heat_capacity;
 } bz_mixed_phase_equilibrium;
 int bz_set_mixed_phase_equilibrium(bz_ctx *ctx, const bz_mixed_phase_equilibrium *params, double *q_ice);
+/* ThermodynamicConstants(saturation_vapor_pressure = FlatauPolynomial(...)) (src/Thermodynamics/flatau_polynomial.jl): the eighth-order
+ * polynomial fits of Flatau et al. (1992), p^v+ = sum_n a_n x^n, n = 0..8, x = max(T - reference_temperature, -minimum_temperature_offset),
+ * over liquid and over ice, coefficients in Pa, a_0 first; on the mixed-phase surface lambda p^v+l + (1 - lambda) p^v+i.  While attached,
+ * every saturation adjustment of the context evaluates it in the place of the Clausius-Clapeyron expression: the anelastic adjustment (warm
+ * and mixed phase), the density-based adjustment of CompressibleDynamics and the one InstantaneousPrecipitation wraps.  The call may come
+ * before or after bz_set_saturation_adjustment / bz_set_mixed_phase_equilibrium / bz_set_instantaneous_precipitation and outlives them.
+ * params == NULL returns the context to Clausius-Clapeyron.  BZ_ERR_UNSUPPORTED, bz_last_error naming the function and the reason: y-slab and
+ * kinematic contexts, and a context with a surface layer or a bulk vapour flux attached (their surface q^v+ is Clausius-Clapeyron; in the
+ * other order bz_set_surface_layer, and bz_set_bulk_surface_fluxes / bz_set_compressible_surface_fluxes with a vapour flux, refuse).  The
+ * Kessler scheme and the diagnostics keep their own expressions.  Every call invalidates recorded steps. */
+typedef struct bz_flatau_polynomial {
+    double liquid_coefficients[9], ice_coefficients[9];
+    double reference_temperature, minimum_temperature_offset;
+} bz_flatau_polynomial;
+int bz_set_saturation_vapor_pressure_polynomial(bz_ctx *ctx, const bz_flatau_polynomial *params);
 /* negative_moisture_correction of BulkMicrophysics (src/Microphysics/bulk_microphysics.jl:26-40; src/AtmosphereModels/
  * negative_moisture_correction.jl:199-347): fix_negative_moisture!(model), the first call of update_state!
  * (update_atmosphere_model_state.jl:42), on the moisture prognostic rho_q and a species chain.  Per column, k = 1 the bottom, rho the

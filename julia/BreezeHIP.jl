@@ -545,6 +545,26 @@ function attach_instantaneous_precipitation!(ctx, model)
                                c.triple_point_temperature, c.triple_point_pressure, solver.abstol, Int32(solver.maxiter), Int32(0))
     check(ccall((:bz_set_instantaneous_precipitation, libbreeze_hip), Cint, (Ptr{Cvoid}, Ref{BzSaturationAdjustment}, Ptr{Cdouble}),
                 ctx, P, devptr(model.microphysical_fields.precipitation_rate)), "bz_set_instantaneous_precipitation", ctx)
+    attach_saturation_vapor_pressure!(ctx, c)
+    return nothing
+end
+
+# bz_flatau_polynomial: the isbits NTuples lay out as the C arrays
+struct BzFlatauPolynomial
+    liquid_coefficients::NTuple{9, Float64}; ice_coefficients::NTuple{9, Float64}
+    reference_temperature::Float64; minimum_temperature_offset::Float64
+end
+
+"""saturation_vapor_pressure of the constants, after the adjustment that evaluates it is attached: a `FlatauPolynomial` goes to
+bz_set_saturation_vapor_pressure_polynomial; every other formulation leaves the context on Clausius-Clapeyron, as before."""
+function attach_saturation_vapor_pressure!(ctx, constants)
+    formula = constants.saturation_vapor_pressure
+    if formula isa Breeze.Thermodynamics.FlatauPolynomial
+        P = BzFlatauPolynomial(map(Float64, formula.liquid_coefficients), map(Float64, formula.ice_coefficients),
+                               Float64(formula.reference_temperature), Float64(formula.minimum_temperature_offset))
+        check(ccall((:bz_set_saturation_vapor_pressure_polynomial, libbreeze_hip), Cint, (Ptr{Cvoid}, Ref{BzFlatauPolynomial}), ctx, P),
+              "bz_set_saturation_vapor_pressure_polynomial", ctx)
+    end
     return nothing
 end
 
