@@ -70,11 +70,6 @@ static AcFields ac_fields(bz_ctx *ctx, const bz_compressible_state *s, const bz_
 
 // k_ac_forward2 addresses every array by a 32-bit byte offset from its base and fetches the outer x neighbours of a row's two edge lanes
 // with one load: arrays below 4 GB, two z halo levels (its ring words are requested two levels ahead), no row whose first lane is its last
-static int forward2_cfg(const bz_ctx *ctx)
-{
-    const int cfg = ctx->tune.ac_cfg;
-    return (cfg != 0 && cfg != 1 && cfg != 2 && cfg != 4 && cfg != 5 && cfg != 6 && cfg != 8 && cfg != 12 && cfg != 13 && cfg != 22 && cfg != 28) ? 29 : cfg;
-}
 static bool ac_forward2_ok(const bz_ctx *ctx)
 {
     const DevGrid &g = ctx->dg;
@@ -195,8 +190,8 @@ int bzi_acoustic_stage_begin(bz_ctx *ctx, const bz_compressible_state *s, const 
     // the fold costs a stage four words per cell (R G_ru, G_rv; W Gp_ru, Gp_rv) and saves every substep one (p^L): stages of >= 5 substeps
     // (the 512 x 512 x 256 benchmark: 6, 9, 18; the supercell shape of configs[4]: 2, 3, 5 — its first two stages keep p^L in the substep)
     S.pfold = S.fwd2 && ctx->d_Gp_ru && (ntau >= 5 || ctx->tune.ac_pfold > 1);      // (y-slabs: the kernel folds the row above the slab too)
-    // the stage's first sweeps form its initial perturbations themselves (default variant of k_ac_forward2 on a single device)
-    S.init_mode = (S.fwd2 && ctx->tune.ac_init_fold && forward2_cfg(ctx) == 29) ? (store0 ? 2 : 1) : 0;      // (y-slabs too: U0 and U carry exchanged halo rows)
+    // the stage's first sweeps (k_ac_forward2, k_ac_column_backward) form its initial perturbations themselves
+    S.init_mode = (S.fwd2 && ctx->tune.ac_init_fold) ? (store0 ? 2 : 1) : 0;      // (y-slabs too: U0 and U carry exchanged halo rows)
     // buffer rotation (compressible_step_body): the caller passed the state arrays themselves as U0 — nothing to copy; the perturbations
     // U0 - U are (+0) by subtraction where a kernel forms them, and known zeros to the folded first sweeps
     const bool copy0 = store0 && !ctx->ac_rotate;
@@ -214,44 +209,23 @@ int bzi_acoustic_stage_begin(bz_ctx *ctx, const bz_compressible_state *s, const 
     return BZ_OK;
 }
 
-// the forward sweep of a fused substep through k_ac_forward2: first substep of the stage / damping of the previous substep / folded p^L
-// gradient, in the variant CFG of the kernel (BZ_AC_CFG; block size, waves per SIMD and what else the kernel reads from its bits)
-template <bool PF, int CFG>
-static void launch_forward2_cfg(bz_ctx *ctx, const AcFields &Fs, const AcParams &P, dim3 cols, dim3 bcol, bool first, bool damp, int init)
+// the forward sweep of a fused substep through k_ac_forward2: first substep of the stage (init: it forms the stage's initial perturbations
+// itself, S.init_mode) / damping of the previous substep / folded p^L gradient
+static void launch_forward2(bz_ctx *ctx, const AcFields &Fs, const AcParams &P, dim3 cols, dim3 bcol, bool first, bool damp, bool pfold, int init)
 {
     const DevGrid &g = ctx->dg;
     ac_storage(ctx, [&](auto st) {
         using ST = typename decltype(st)::type;
         const AcFieldsT<ST> F = ac_cast<ST>(Fs);
-        // the INIT variants (the first sweep forms the stage's initial perturbations) exist for the default CFG only
-        if constexpr (CFG == 29) {
-            if (first && init == 2) { hipLaunchKernelGGL((k_ac_forward2<true, false, PF, CFG, ST, 2>), cols, bcol, 0, ctx->stream, g, F, P); return; }
-            if (first && init) { hipLaunchKernelGGL((k_ac_forward2<true, false, PF, CFG, ST, 1>), cols, bcol, 0, ctx->stream, g, F, P); return; }
-        }
-        if (first) hipLaunchKernelGGL((k_ac_forward2<true, false, PF, CFG, ST>), cols, bcol, 0, ctx->stream, g, F, P);
-        else if (damp) hipLaunchKernelGGL((k_ac_forward2<false, true, PF, CFG, ST>), cols, bcol, 0, ctx->stream, g, F, P);
-        else hipLaunchKernelGGL((k_ac_forward2<false, false, PF, CFG, ST>), cols, bcol, 0, ctx->stream, g, F, P);
+        bz_bools([&](auto pf) {
+            constexpr bool PF = pf();
+            if (first && init == 2) hipLaunchKernelGGL((k_ac_forward2<true, false, PF, ST, 2>), cols, bcol, 0, ctx->stream, g, F, P);
+            else if (first && init) hipLaunchKernelGGL((k_ac_forward2<true, false, PF, ST, 1>), cols, bcol, 0, ctx->stream, g, F, P);
+            else if (first) hipLaunchKernelGGL((k_ac_forward2<true, false, PF, ST>), cols, bcol, 0, ctx->stream, g, F, P);
+            else if (damp) hipLaunchKernelGGL((k_ac_forward2<false, true, PF, ST>), cols, bcol, 0, ctx->stream, g, F, P);
+            else hipLaunchKernelGGL((k_ac_forward2<false, false, PF, ST>), cols, bcol, 0, ctx->stream, g, F, P);
+        }, pfold);
     });
-}
-static void launch_forward2(bz_ctx *ctx, const AcFields &Fs, const AcParams &P, dim3 cols, dim3 bcol, bool first, bool damp, bool pfold, int cfg, int init)
-{
-    bz_bools([&](auto pf) {
-        constexpr bool PF = pf();
-        switch (cfg) {      // (forward2_cfg: one of these)
-        case 0: launch_forward2_cfg<PF, 0>(ctx, Fs, P, cols, bcol, first, damp, 0); break;
-        case 1: launch_forward2_cfg<PF, 1>(ctx, Fs, P, cols, bcol, first, damp, 0); break;
-        case 2: launch_forward2_cfg<PF, 2>(ctx, Fs, P, cols, bcol, first, damp, 0); break;
-        case 4: launch_forward2_cfg<PF, 4>(ctx, Fs, P, cols, bcol, first, damp, 0); break;
-        case 5: launch_forward2_cfg<PF, 5>(ctx, Fs, P, cols, bcol, first, damp, 0); break;
-        case 6: launch_forward2_cfg<PF, 6>(ctx, Fs, P, cols, bcol, first, damp, 0); break;
-        case 8: launch_forward2_cfg<PF, 8>(ctx, Fs, P, cols, bcol, first, damp, 0); break;
-        case 12: launch_forward2_cfg<PF, 12>(ctx, Fs, P, cols, bcol, first, damp, 0); break;
-        case 13: launch_forward2_cfg<PF, 13>(ctx, Fs, P, cols, bcol, first, damp, 0); break;
-        case 22: launch_forward2_cfg<PF, 22>(ctx, Fs, P, cols, bcol, first, damp, 0); break;
-        case 28: launch_forward2_cfg<PF, 28>(ctx, Fs, P, cols, bcol, first, damp, 0); break;
-        default: launch_forward2_cfg<PF, 29>(ctx, Fs, P, cols, bcol, first, damp, cfg == 29 ? init : 0); break;
-        }
-    }, pfold);
 }
 
 // substep `sstep` (1-based) of the stage opened by bzi_acoustic_stage_begin
@@ -291,16 +265,15 @@ int bzi_acoustic_substep(bz_ctx *ctx, const bz_compressible_state *s, const bz_c
             {
                 ProfileScope ps(ctx, "acoustic_horizontal+column_forward");
                 if (S.fwd2) {
-                    const int cfg = forward2_cfg(ctx);
-                    const int bt = (cfg & 1) ? 512 : 256;
-                    const int fx = ctx->tune.ac_bx == 512 && bt == 512 ? 512 : ctx->tune.ac_bx == 256 ? 256 : ctx->tune.ac_bx == 128 ? 128 : 64, fy = bt / fx;
+                    const int bx = ctx->tune.ac_bx;      // 512 threads as fx columns of fy rows
+                    const int fx = (bx == 128 || bx == 256 || bx == 512) ? bx : 64, fy = 512 / fx;
                     dim3 cols2((g.Nx + fx - 1) / fx, (g.Ny + fy - 1) / fy), bcol2(fx, fy);
                     P.xcd = (ctx->tune.ac_xcd && cols2.y % 8 == 0) ? 1 : 0;
                     // <u>, <v> in pairs counted from the stage's last substep (AcParams::acc_mode): substep 1 starts the accumulators, an odd
                     // substep out (substep 2) is added alone
                     if (ctx->tune.ac_pair_avg && !S.direct && !ctx->substep_f32 && sstep >= 2)      // (y-slabs too: a row accumulates its own faces)
                         P.acc_mode = ((ntau - sstep) & 1) ? 1 : (sstep >= 3 ? 2 : 0);
-                    launch_forward2(ctx, Fs, P, cols2, bcol2, sstep == 1, damp, S.pfold, cfg, S.init_mode);
+                    launch_forward2(ctx, Fs, P, cols2, bcol2, sstep == 1, damp, S.pfold, S.init_mode);
                 }
                 else if (sstep == 1)
                     hipLaunchKernelGGL((k_ac_column_forward<true, true, false, ST>), cols, bcol, 0, ctx->stream, g, ac_cast<ST>(Fs), P);

@@ -337,20 +337,23 @@ __global__ __launch_bounds__(ACX * ACY, AC_MINW) void k_ac_column_forward(DevGri
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// Round 6: the fused forward sweep written for the memory pipe.  The kernel above spends 77 % of its wave cycles parked
-// (profiles/r05_pmc_compressible.json) for two reasons its ISA shows:
-//   * its stores (rup, rvp, au, av, rs, rths, phi) cannot be proven not to alias the loads that follow them in program order (au / av are
-//     read-modify-write, the ring loads of the next level sit below the stores), so hipcc keeps that order and — the vector-memory counter
-//     returns in order — drains everything outstanding four times per level (`s_waitcnt vmcnt(0)`; store, one load, drain, store, ...):
-//     four to five memory round trips per level instead of one;
-//   * every `F.x[n + d]` is a 64-bit per-lane address: 45 base pairs = 90 of its 214 VGPRs hold addresses (two waves per SIMD).
-// Here every load of a level — the level's own words, the neighbours' and the ring words of the levels above — is issued before the
-// first store of the level, all stores close the level, and every access is `uniform base + 32-bit per-lane byte offset` (the saddr form
-// of global_load: one offset register per neighbour displacement).  The arithmetic is the text of the kernel above, so the results carry
-// its bits; PF folds the stage-constant horizontal gradient of p^L into the slow tendencies (Gp_ru, Gp_rv written by k_ac_stage_init:
-// one array and four neighbour loads less per level and substep; the only deviation, one rounding of G - dp).
-// Neighbours in x of theta_L, C, (rho theta)' and its previous value come from the neighbouring lanes; the two edge lanes of a row fetch
-// theirs with one predicated load per array.
+// The fused forward sweep of periodic grids (ac_forward2_ok), written for the memory pipe.  A block is 512 threads (64 x 8, 128 x 4,
+// 256 x 2 or 512 x 1 columns; a wavefront is always 64 consecutive cells of one row) with a register budget of two waves per SIMD.  A
+// column marches up its levels; per level
+//   * every load — the level's own words, the neighbours' and the ring words of the levels above — is issued before the first store, and
+//     all stores close the level, so the compiler never has to drain the vector-memory counter between a store and a load it cannot prove
+//     independent;
+//   * every access is `uniform base + 32-bit per-lane byte offset` (the saddr form of global_load: one offset register per neighbour
+//     displacement instead of a 64-bit address per array);
+//   * the loads of level k + 1 are issued before level k is worked on (two levels per trip, see the loop), so they fly under the
+//     arithmetic, the stores and the barrier of level k;
+//   * one s_barrier keeps the rows of a block in step: a row's y neighbours are requested while their lines are near;
+//   * neighbours in x of theta_L, C, (rho theta)' and its previous value come from the neighbouring lanes by DPP moves (bz_lane_up /
+//     bz_lane_down); the two edge lanes of a row fetch theirs with one predicated load per array.
+// What each of these bought over k_ac_column_forward, and the variants that lost, are in DESIGN §7 ("k_ac_forward2").
+// The arithmetic is the text of the kernel above, so the results carry its bits; PF folds the stage-constant horizontal gradient of p^L
+// into the slow tendencies (Gp_ru, Gp_rv written by k_ac_stage_init: one array and four neighbour loads less per level and substep; the
+// only deviation, one rounding of G - dp).
 // ---------------------------------------------------------------------------------------------------------------------
 template <class T>
 __device__ __forceinline__ T ac_ld(const T *base, unsigned e)
@@ -382,15 +385,12 @@ __device__ __forceinline__ double ac_face_update2(double up, double G, double rt
     return up + P.dtau * (G - dp);
 }
 
-// CFG: bit 0: 512 threads per block instead of 256; bit 1: register budget for three waves per SIMD instead of two; bit 2: the rows of a
-// block advance level by level together (one s_barrier per level); bit 3: the loads of level k + 1 are issued before level k is worked on;
-// bit 4: x neighbours by DPP wavefront shifts instead of ds_bpermute
 // INIT (first substep of a stage only): 0 the stage's initial perturbations are read from their arrays (k_ac_stage_init stored them);
 // 1 they are formed here from U0 - U (rounded through the storage type, as the stored ones are) — the initialisation pass neither writes
 // them (5 words per cell) nor does this sweep read them back (5): it reads U0 and U (10) and stores the initial (rho theta)' (1), which
 // the next substep's damping and the stage epilogue read; 2 first stage of a whole step: the state IS U0, the perturbations are exact zeros
-template <bool FIRST, bool DAMP, bool PF, int CFG, class ST, int INIT = 0>
-__global__ __launch_bounds__((CFG & 1) ? 512 : 256, (CFG & 2) ? 3 : 2) void k_ac_forward2(DevGrid g, AcFieldsT<ST> F, AcParams P)
+template <bool FIRST, bool DAMP, bool PF, class ST, int INIT = 0>
+__global__ __launch_bounds__(512, 2) void k_ac_forward2(DevGrid g, AcFieldsT<ST> F, AcParams P)
 {
     static_assert(FIRST || INIT == 0, "initial perturbations belong to the first substep of a stage");
     int bx = blockIdx.x, by = blockIdx.y;
@@ -399,7 +399,7 @@ __global__ __launch_bounds__((CFG & 1) ? 512 : 256, (CFG & 2) ? 3 : 2) void k_ac
         bx = (int)(r % gridDim.x);
         by = (int)(c * (gridDim.y >> 3) + r / gridDim.x);
     }
-    // 256 threads as 64 x 4, 128 x 2 or 256 x 1 columns (BZ_AC_BX): a wavefront is always 64 consecutive cells of one row
+    // 512 threads as 64 x 8, 128 x 4, 256 x 2 or 512 x 1 columns (BZ_AC_BX): a wavefront is always 64 consecutive cells of one row
     const int i = bx * (int)blockDim.x + threadIdx.x, j = by * (int)blockDim.y + threadIdx.y;
     if (i >= g.Nx || j >= g.Ny) return;
     const WrapIdx W = wrap_of(g, i, j);
@@ -435,7 +435,7 @@ __global__ __launch_bounds__((CFG & 1) ? 512 : 256, (CFG & 2) ? 3 : 2) void k_ac
     double thf_0 = th_0, thf_m = th_0;               // theta at faces k (k = 0: one-sided) and k-1
 
     // every word a level asks the memory for, as one record: `level(e, k)` issues the loads (own level k, the neighbours', the ring words of the
-    // levels above); with CFG bit 3 the record of level k + 1 is requested before level k is worked on (its loads fly under the ~280 VALU
+    // levels above); the record of level k + 1 is requested before level k is worked on (its loads fly under the ~280 VALU
     // instructions, the stores and the barrier of level k: the rows of a block that advance in lock step would otherwise leave the memory
     // pipe idle between a level's stores and the next level's loads)
     struct AcLevel {
@@ -485,7 +485,6 @@ __global__ __launch_bounds__((CFG & 1) ? 512 : 256, (CFG & 2) ? 3 : 2) void k_ac
         L.w_n = INIT == 2 ? 0.0 : INIT == 1 ? pert_w(e1 + sz) : ac_ld(F.rwp, e1 + sz);
         return L;
     };
-    constexpr bool PIPE = (CFG & 8) != 0;
     auto work = [&](const AcLevel &L, const int k, const unsigned e) {
         const double rdc = g.rdzc[k];
         const double Ax = g.Ax[k], Ay = g.Ay[k], Vinv = g.Vinv_c[k];
@@ -497,12 +496,11 @@ __global__ __launch_bounds__((CFG & 1) ? 512 : 256, (CFG & 2) ? 3 : 2) void k_ac
         const double sp = sponge[k];                // sponge_rhs / sponge_term_diag (acoustic_substepping.jl:591-602)
 
         // ---- neighbours in x from the neighbouring lanes ----
-        constexpr bool DPP = (CFG & 16) != 0;
-        double thxm = ac_lane_up<DPP>(th_0), thxp = ac_lane_down<DPP>(th_0);
-        double c_xm = ac_lane_up<DPP>(C_0), c_xp = ac_lane_down<DPP>(C_0);
-        double rt_xm = ac_lane_up<DPP>(rthp), rt_xp = ac_lane_down<DPP>(rthp);
+        double thxm = bz_lane_up(th_0), thxp = bz_lane_down(th_0);
+        double c_xm = bz_lane_up(C_0), c_xp = bz_lane_down(C_0);
+        double rt_xm = bz_lane_up(rthp), rt_xp = bz_lane_down(rthp);
         double o_xm = 0.0, o_xp = 0.0;
-        if (DAMP) { o_xm = ac_lane_up<DPP>(o0); o_xp = ac_lane_down<DPP>(o0); }
+        if (DAMP) { o_xm = bz_lane_up(o0); o_xp = bz_lane_down(o0); }
         if (edge_m) { thxm = e_th; c_xm = e_C; rt_xm = e_rt; o_xm = e_o; }
         if (edge_p) { thxp = e_th; c_xp = e_C; rt_xp = e_rt; o_xp = e_o; }
         const double thym = thy_m0, thyp = thy_p0, c_ym = cy_m0, c_yp = cy_p0;
@@ -565,7 +563,7 @@ __global__ __launch_bounds__((CFG & 1) ? 512 : 256, (CFG & 2) ? 3 : 2) void k_ac
         if (FIRST) ac_st(F.tfac, e, t);
         ac_st(F.phi, e, phi);
         phi_m = phi;
-        if (CFG & 4) __builtin_amdgcn_s_barrier();      // the rows of a block advance together: a row's y neighbours are requested while their lines are near
+        __builtin_amdgcn_s_barrier();      // the rows of a block advance together: a row's y neighbours are requested while their lines are near
 
         // advance the rings
         rs_m = rs; rths_m = rths; rp_m = rp; rthp_m = rthp;
@@ -576,22 +574,18 @@ __global__ __launch_bounds__((CFG & 1) ? 512 : 256, (CFG & 2) ? 3 : 2) void k_ac
         cy_m0 = cy_mn; cy_p0 = cy_pn;
         thy_m0 = thy_m1; thy_p0 = thy_p1; thy_m1 = thy_mn; thy_p1 = thy_pn;
     };
-    if (!PIPE) {
-        for (int k = 0; k < Nz; ++k, e += sz) work(level(e, k), k, e);
-    } else {
-        // two levels per trip so that the two records live in fixed registers (a rotation `current = next` would have to wait for the
-        // next level's loads before it could copy them); the last level re-reads itself
-        AcLevel LA = level(e, 0), LB;
+    // two levels per trip so that the two records live in fixed registers (a rotation `current = next` would have to wait for the
+    // next level's loads before it could copy them); the last level re-reads itself
+    AcLevel LA = level(e, 0), LB;
 #pragma unroll 1
-        for (int k = 0; k < Nz; k += 2, e += 2 * sz) {
-            const int k1 = (k + 1 < Nz) ? k + 1 : k;
-            LB = level(e + (unsigned)(k1 - k) * sz, k1);
-            work(LA, k, e);
-            if (k + 1 < Nz) {
-                const int k2 = (k + 2 < Nz) ? k + 2 : k + 1;
-                LA = level(e + (unsigned)(k2 - k) * sz, k2);
-                work(LB, k + 1, e + sz);
-            }
+    for (int k = 0; k < Nz; k += 2, e += 2 * sz) {
+        const int k1 = (k + 1 < Nz) ? k + 1 : k;
+        LB = level(e + (unsigned)(k1 - k) * sz, k1);
+        work(LA, k, e);
+        if (k + 1 < Nz) {
+            const int k2 = (k + 2 < Nz) ? k + 2 : k + 1;
+            LA = level(e + (unsigned)(k2 - k) * sz, k2);
+            work(LB, k + 1, e + sz);
         }
     }
 }

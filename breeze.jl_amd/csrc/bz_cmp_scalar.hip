@@ -318,7 +318,7 @@ __global__ __launch_bounds__(64 * SLT, 2) void k_scalar_rho3d_lds(DevGrid g, dou
         const double Ax = g.Ax[k], Ay = g.Ay[k];
         if (GRHO) {      // G_rho = -div(rho u) of the cell: the x neighbour from the next lane, the lower z face carried from the level below
             const double gru0 = ru[n], grv0 = rv[n], grv1 = rv[n + sy], grw1 = rw[n + sz];
-            double gru1 = ac_lane_down<true>(gru0);
+            double gru1 = bz_lane_down(gru0);
             if (tx == 63) gru1 = ru[n + 1];
             const double a = Ax * gru1 - Ax * gru0;
             const double b = Ay * grv1 - Ay * grv0;

@@ -765,7 +765,7 @@ static int dist_time_step_lean(bz_ctx *ctx, const bz_state *s, const bz_prognost
     if ((rc = bzi_zero_wall_faces(ctx, G, U0))) return rc;
     // The scalar-pair kernel feeds nothing of the pressure solve: with messages in flight (W > 1) it runs on the context's second
     // stream beside the source term, the transforms and both all-to-alls, and is joined before the projection kernel.
-    const bool fork = (c->W > 1 || c->self_messages || ctx->side_scalar) && !ctx->tune.comm_no_side_scalar;
+    const bool fork = (c->W > 1 || c->self_messages) && !ctx->tune.comm_no_side_scalar;
     const int first_part = fork ? 1 : 3;
     for (int stage = 0; stage < 3; ++stage) {
         const double alpha = BZ_SSP_RK3_ALPHA[stage];

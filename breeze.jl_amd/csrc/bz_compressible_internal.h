@@ -26,13 +26,6 @@ __device__ __forceinline__ WrapIdx wrap_of(const DevGrid &g, int i, int j)
     return w;
 }
 
-// a value one lane up / down the 64-lane wavefront (lane l receives lane l - 1 / l + 1): the DPP moves of bz_internal.h (bz_lane_up /
-// bz_lane_down), or — DPP = false, the measured alternative of the forward sweep — the shuffles through the LDS pipe
-template <bool DPP>
-__device__ __forceinline__ double ac_lane_up(double v) { return DPP ? bz_lane_up(v) : __shfl_up(v, 1); }
-template <bool DPP>
-__device__ __forceinline__ double ac_lane_down(double v) { return DPP ? bz_lane_down(v) : __shfl_down(v, 1); }
-
 // update_state!: what k_cmp_diagnose (bz_cmp_state.hip) and the tail of k_ac_stage_end (bz_acoustic_kernels.h) read and write
 struct DiagFields {
     double *rho_d, *rho, *ru, *rv, *rw, *rth, *rq;

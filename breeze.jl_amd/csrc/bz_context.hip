@@ -7,7 +7,7 @@
 
 ProfileScope::ProfileScope(bz_ctx *c, const char *name) : ctx(c)
 {
-    if (!ctx->profiling || ctx->profile_mute) return;
+    if (!ctx->profiling) return;
     for (size_t s = 0; s < ctx->slots.size(); ++s)
         if (ctx->slots[s].name == name || std::strcmp(ctx->slots[s].name, name) == 0) slot = (int)s;
     if (slot < 0) {
@@ -53,7 +53,6 @@ void bzi_read_tuning(bz_tuning &t)
     t.no_k6_stored = on("BZ_NO_K6_STORED");
     t.no_closure_march = on("BZ_NO_CLOSURE_MARCH");
     t.no_dry_shortcut = on("BZ_NO_DRY_SHORTCUT");
-    t.side_scalar = on("BZ_SIDE_SCALAR");
     t.no_fuse_forcing = on("BZ_NO_FUSE_FORCING");
     t.no_fold_forcing = on("BZ_NO_FOLD_FORCING");
     t.no_fuse_level_sums = on("BZ_NO_FUSE_LEVEL_SUMS");
@@ -63,14 +62,12 @@ void bzi_read_tuning(bz_tuning &t)
     t.ac_init_fold = num("BZ_AC_INIT_FOLD", 1);
     t.ac_pair_avg = num("BZ_AC_PAIR_AVG", 1);
     t.ac_rotate = num("BZ_AC_ROTATE", 1);
-    t.ac_cfg = num("BZ_AC_CFG", 29);
     t.ac_bx = num("BZ_AC_BX", 128);
     t.no_tridiag_coop = on("BZ_NO_TRIDIAG_COOP");
     t.no_xfft = on("BZ_NO_XFFT");
     t.poisson_kxmajor = num("BZ_POISSON_KXMAJOR", 1);
     t.poisson_kx_pad = num("BZ_POISSON_KX_PAD", 1);
     t.poisson_kx_chunk_kb = num("BZ_POISSON_KX_CHUNK_KB", 0);
-    t.poisson_chunk = num("BZ_POISSON_CHUNK", 0);
     t.no_generic_march = on("BZ_NO_GENERIC_MARCH");
     t.no_rho3d_exchange = on("BZ_NO_RHO3D_EXCHANGE");
     t.scalar_lds = num("BZ_SCALAR_LDS", 1);
@@ -79,7 +76,6 @@ void bzi_read_tuning(bz_tuning &t)
     t.comm_no_overlap = on("BZ_COMM_NO_OVERLAP");
     t.comm_self_messages = on("BZ_COMM_SELF_MESSAGES");
     t.comm_no_side_scalar = on("BZ_COMM_NO_SIDE_SCALAR");
-    t.nmc_store_always = on("BZ_NMC_STORE_ALWAYS");
     t.graph = num("BZ_GRAPH", -1);
     t.graph_debug = on("BZ_GRAPH_DEBUG");
 }
@@ -122,10 +118,6 @@ int bzi_apply_stream(bz_ctx *ctx, hipStream_t stream)
     if (ctx->xf && ctx->plan_y) BZ_FFT(hipfftSetStream(ctx->plan_y, ctx->stream));      // the y transforms of the LDS x-transform pipeline
     if (ctx->plan_yc) BZ_FFT(hipfftSetStream(ctx->plan_yc, ctx->stream));
     if (ctx->plan_yc_last) BZ_FFT(hipfftSetStream(ctx->plan_yc_last, ctx->stream));
-    if (ctx->pchunk) {
-        BZ_FFT(hipfftSetStream(ctx->plan_fwd_c, ctx->stream));
-        BZ_FFT(hipfftSetStream(ctx->plan_inv_c, ctx->stream));
-    }
     if (ctx->slab_plans_ok) {
         BZ_FFT(hipfftSetStream(ctx->slab_plan_x_fwd, ctx->stream));
         BZ_FFT(hipfftSetStream(ctx->slab_plan_x_inv, ctx->stream));

@@ -455,11 +455,10 @@ int bzi_poisson_source_fused(bz_ctx *ctx, const bz_state *s, double dt, double *
 {
     const DevGrid &g = ctx->dg;
     ProfileScope ps(ctx, "poisson_source_term");
-    const int k0 = ctx->krn ? ctx->kr0 : 0, nk = ctx->krn ? ctx->krn : g.Nz;      // level range (chunked Poisson pipeline) or all
-    dim3 grid((g.Nx + 255) / 256, g.Ny, nk), block(256);
+    dim3 grid((g.Nx + 255) / 256, g.Ny, g.Nz), block(256);
     hipLaunchKernelGGL(k_poisson_source_rows, grid, block, 0, ctx->stream, g, rhs ? rhs : ctx->d_rhs,
                        predictor ? predictor->rho_u : s->rho_u, predictor ? predictor->rho_v : s->rho_v,
-                       predictor ? predictor->rho_w : s->rho_w, dt, k0);
+                       predictor ? predictor->rho_w : s->rho_w, dt, 0);
     BZ_LAUNCH_CHECK();
     return BZ_OK;
 }
@@ -475,8 +474,8 @@ int bzi_project_lean(bz_ctx *ctx, const bz_state *s, double dt, const double *ph
     F.phi_c = phi_c ? phi_c : ctx->d_rhs;
     F.phi_below = phi_below;
     F.sa = sa; F.sb = sb;
-    F.k0 = ctx->krn ? ctx->kr0 : 0;
-    const int nk = ctx->krn ? ctx->krn : g.Nz;
+    F.k0 = 0;
+    const int nk = g.Nz;
     if (BZ_PV == 2 && g.Nx % 2 == 0) {
         const int gx = (g.Nx / 2 + 255) / 256;
         dim3 grid((unsigned)((long long)gx * g.Ny * nk)), block(256);
@@ -506,8 +505,8 @@ int bzi_project_diagnose(bz_ctx *ctx, const bz_state *s, double dt, const double
     F.phi_c = phi_c ? phi_c : ctx->d_rhs;
     F.phi_below = phi_below;
     F.store_phi = store_phi ? 1 : 0;
-    F.k0 = ctx->krn ? ctx->kr0 : 0;
-    const int gx = (g.Nx + 255) / 256, nk = ctx->krn ? ctx->krn : g.Nz;
+    F.k0 = 0;
+    const int gx = (g.Nx + 255) / 256, nk = g.Nz;
     F.lsum = level_sums ? bzi_level_sum_rows(ctx, &F.lsum_P) : nullptr;
     if (!F.lsum) F.lsum_P = 0;
     dim3 grid((unsigned)((long long)gx * g.Ny * nk)), block(256);

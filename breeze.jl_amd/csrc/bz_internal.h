@@ -494,7 +494,9 @@ struct ProfileSlot {
 };
 
 // Every BZ_* environment switch of the library, read ONCE when a context is created (bzi_read_tuning, bz_context.hip): nothing on a
-// launch path calls getenv.  They select measured alternatives for A/B runs; defaults are the shipped choices.
+// launch path calls getenv.  They select measured alternatives for A/B runs; defaults are the shipped choices.  Each one
+// selects a path that some shipped configuration takes or that a test checks a living kernel against; a switch whose alternative lost and
+// that nothing else reaches goes with the code it kept alive (HISTORY.md has the measurements).
 struct bz_tuning {
     bool no_fused = false;            // BZ_NO_FUSED: per-operator sequence instead of the fused whole-step tiers
     bool no_fuse_rk = false;          // BZ_NO_FUSE_RK
@@ -503,7 +505,6 @@ struct bz_tuning {
     bool no_closure_march = false;    // BZ_NO_CLOSURE_MARCH: the cell-per-thread closure kernels everywhere
     bool no_k6_stored = false;        // BZ_NO_K6_STORED: the stored-velocity tiers keep the fourth-generation tile kernels (k_{u,v,w}_tend_lds)
     bool no_dry_shortcut = false;     // BZ_NO_DRY_SHORTCUT: the lean kernels always carry rho q (no moisture scan)
-    bool side_scalar = false;         // BZ_SIDE_SCALAR: scalar kernel beside the pressure solve on one GPU too
     bool no_fuse_forcing = false;     // BZ_NO_FUSE_FORCING
     bool no_fold_forcing = false;     // BZ_NO_FOLD_FORCING: the fused-RK tier keeps the momentum terms of the forcing stack in the forcing pass
     int ac_xcd = 1;                   // BZ_AC_XCD=0: the forward acoustic sweep in launch order (XCD = tile column) instead of XCD = band of tile rows
@@ -512,16 +513,13 @@ struct bz_tuning {
     int ac_pair_avg = 1;              // BZ_AC_PAIR_AVG=0: <u>, <v> accumulated in every substep instead of two substeps at a time (AcParams::acc_mode)
     int ac_init_fold = 1;             // BZ_AC_INIT_FOLD=0: k_ac_stage_init stores the stage's initial perturbations and the first sweeps read them back
     int ac_pfold = 1;                 // BZ_AC_PFOLD=0: the horizontal gradient of p^L stays in every substep instead of folded into the stage's slow tendencies
-    int ac_bx = 128;                  // BZ_AC_BX: columns of a k_ac_forward2 block along x (64, 128, 256, 512; rows = threads / columns)
-    int ac_cfg = 29;                  // BZ_AC_CFG: k_ac_forward2 variant (bit 0: 512-thread blocks, bit 1: register budget of three waves per SIMD, bit 2: barrier per level,
-                                      // bit 3: next level's loads in flight, bit 4: DPP lane shifts); built: 0 1 2 4 5 6 8 12 13 22 28 29
+    int ac_bx = 128;                  // BZ_AC_BX: columns of a k_ac_forward2 block along x (64, 128, 256, 512; rows = 512 / columns)
     bool no_fuse_level_sums = false;  // BZ_NO_FUSE_LEVEL_SUMS: the subsidence averages always come from their own pass over u, v, theta, q
     bool no_tridiag_coop = false;     // BZ_NO_TRIDIAG_COOP: sequential Thomas kernel
     bool no_xfft = false;             // BZ_NO_XFFT: library 2-D plans instead of the hand-written x transforms
     int poisson_kxmajor = 1;          // BZ_POISSON_KXMAJOR=0: level-major half spectrum, three whole-spectrum passes between the x transforms
     int poisson_kx_chunk_kb = 0;      // BZ_POISSON_KX_CHUNK_KB: the same in KB (tests: the chunked pipeline on small grids)
     int poisson_kx_pad = 1;           // BZ_POISSON_KX_PAD: phantom lines per wavenumber of the kx-major spectrum (0 .. 4)
-    int poisson_chunk = 0;            // BZ_POISSON_CHUNK: level-chunked Poisson pipeline (needs BZ_NO_XFFT)
     int scalar_lds = 1;               // BZ_SCALAR_LDS=0: the 3-D-density scalar tendency keeps the kernel that reads its stencils through the L1 (k_scalar_tendency_rho3d_x)
     bool no_rho3d_exchange = false;   // BZ_NO_RHO3D_EXCHANGE: the compressible scalar tendency keeps the kernel that evaluates five fluxes per cell
     bool no_generic_march = false;    // BZ_NO_GENERIC_MARCH: WENO 7 / 9 keep the two-pass (flux arrays + divergence) kernels everywhere
@@ -530,7 +528,6 @@ struct bz_tuning {
     bool comm_no_overlap = false;     // BZ_COMM_NO_OVERLAP
     bool comm_self_messages = false;  // BZ_COMM_SELF_MESSAGES: world 1 sends every message to itself
     bool comm_no_side_scalar = false; // BZ_COMM_NO_SIDE_SCALAR
-    bool nmc_store_always = false;    // BZ_NMC_STORE_ALWAYS: k_fix_negative_moisture stores every cell instead of the cells whose bits changed
     int graph = -1;                   // BZ_GRAPH (-1: unset)
     bool graph_debug = false;         // BZ_GRAPH_DEBUG
 };
@@ -573,11 +570,6 @@ struct bz_ctx {
     hipfftHandle plan_fwd = 0, plan_inv = 0;
     hipfftDoubleComplex *d_dctx = nullptr;      // Bounded x: half spectrum of the permuted rows ((Nx/2 + 1) x Nz), between the row transform and the cosine combination
     bool plans_ok = false;
-    // chunked Poisson pipeline (bz_poisson.hip): 2-D plans over `pchunk` levels, so that source term -> x transform -> y transform
-    // (and y -> x -> projection on the way back) of one level range run back to back while the range sits in the 256 MiB Infinity Cache
-    hipfftHandle plan_fwd_c = 0, plan_inv_c = 0;
-    int pchunk = 0;
-    int kr0 = 0, krn = 0;            // level range of the next source / projection launch (krn = 0: all levels)
     // hand-written x transforms with a transposed (ky-fastest) half spectrum (bz_xfft_kernels.h)
     bool xf = false;
     bool xf_slab = false;            // y-slab context whose rows the same kernels transform (bz_comm.hip: dist_poisson)
@@ -587,7 +579,6 @@ struct bz_ctx {
     bool kxmajor = false;
     int kx_cw = 0, kx_nch = 0, kx_pad = 0;      // wavenumbers per chunk, chunks, phantom lines per wavenumber
     hipfftHandle plan_yc = 0, plan_yc_last = 0;      // y transforms of one chunk / of the (shorter) last chunk
-    int profile_mute = 0;            // > 0: ProfileScope objects record nothing (an enclosing scope covers the launches)
     // y-slab mode: 1-D batched plans of the distributed transform (bz_slab_transform, created on first use)
     hipfftHandle slab_plan_x_fwd = 0, slab_plan_x_inv = 0, slab_plan_y = 0;
     bool slab_plans_ok = false;
@@ -625,7 +616,6 @@ struct bz_ctx {
     bool lean_xcd = true;             // XCD-contiguous block order of the lean kernels (BZ_NO_XCD=1 disables)
     hipStream_t side_stream = nullptr;   // the scalar-pair kernel of a stage runs here, beside the pressure solve on the main stream
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    bool side_scalar = false;         // BZ_SIDE_SCALAR=1: single-GPU seam too (the distributed step does it whenever W > 1)
     void *d_lev_rows = nullptr;       // LevRow5[Nz + 2 Hz]: the lean kernels' column constants, one 64-byte row per level (bz_tendency5.hip)
     double *d_pi_dry = nullptr;       // (p_r[k]/p_st)^(Rd/cpd), k = -Hz .. Nz+Hz-1: Exner factor of a dry cell, built with the device pow()
     // CompressibleDynamics + SplitExplicitTimeDiscretization (bz_create_compressible)
@@ -887,7 +877,6 @@ void bzi_poisson_teardown(bz_ctx *ctx);
 int bzi_poisson_solve(bz_ctx *ctx, const bz_state *s, double dt);
 int bzi_poisson_spectral(bz_ctx *ctx);
 int bzi_poisson_from_momentum(bz_ctx *ctx, const bz_state *s, double dt, const bz_prognostic *predictor);
-int bzi_fft_chunk(bz_ctx *ctx, int k0, bool forward);
 int bzi_xf_forward(bz_ctx *ctx, const bz_state *s, double dt, const bz_prognostic *predictor, const double *rhs = nullptr,
                    double *hat = nullptr, int blocks = 1, int klo = 0, int khi = 0);      // khi = 0: all levels
 int bzi_xf_inverse(bz_ctx *ctx, const double *hat = nullptr, double *phi = nullptr, int blocks = 1, int klo = 0, int khi = 0);

@@ -30,14 +30,13 @@ struct NmcLists {
 __device__ __forceinline__ double nmc_max0(double x) { return x > 0.0 ? x : (x != x ? x : 0.0); }
 __device__ __forceinline__ double nmc_min(double a, double b) { return b != b ? b : (a < b ? a : b); }
 __device__ __forceinline__ bool nmc_same_bits(double a, double b) { return bz_real_bits(a) == bz_real_bits(b); }
-template <bool SA>
+// a cell is stored where its bits changed ("Store policy")
 __device__ __forceinline__ void nmc_store(double *__restrict__ f, long long n, double v, double v_loaded)
 {
-    if (SA || !nmc_same_bits(v, v_loaded)) f[n] = v;
+    if (!nmc_same_bits(v, v_loaded)) f[n] = v;
 }
 
 // Species borrowing, orphaned numbers and the clamp of one cell; v is rho q^ve of the cell (read by the caller, stored by the caller).
-template <bool SA>
 __device__ __forceinline__ double nmc_species_cell(const NmcLists &L, long long n, double rho, double v)
 {
     double m[NMC_MAX], m0[NMC_MAX];
@@ -60,21 +59,21 @@ __device__ __forceinline__ double nmc_species_cell(const NmcLists &L, long long 
     }
 #pragma unroll
     for (int c = 0; c < NMC_MAX; ++c)
-        if (c < L.n_mass) nmc_store<SA>(L.mass[c], n, m[c], m0[c]);
+        if (c < L.n_mass) nmc_store(L.mass[c], n, m[c], m0[c]);
 #pragma unroll
     for (int p = 0; p < NMC_MAX; ++p) {
         if (p < L.n_pairs) {
             const int pi = L.pair_idx[p];
             const double mv = pi == 0 ? m[0] : pi == 1 ? m[1] : pi == 2 ? m[2] : pi == 3 ? m[3] : L.pair_mass[p][n];
             const double nv = L.number[p][n];
-            nmc_store<SA>(L.number[p], n, mv <= 0.0 ? 0.0 : nv, nv);
+            nmc_store(L.number[p], n, mv <= 0.0 ? 0.0 : nv, nv);
         }
     }
 #pragma unroll
     for (int c = 0; c < NMC_MAX; ++c) {
         if (c < L.n_clamp) {
             const double nv = L.clamp[c][n];      // may be a number field stored just above: the same lane, the same address
-            nmc_store<SA>(L.clamp[c], n, nmc_max0(nv), nv);
+            nmc_store(L.clamp[c], n, nmc_max0(nv), nv);
         }
     }
     return v;
@@ -93,9 +92,8 @@ __device__ __forceinline__ double nmc_down(const DevGrid &g, int k, double v, do
 }
 
 // grid (ceil(Nx / 64), Ny), block 64: one wave, one row, 64 columns; ragged Nx through the predicate.
-// SPECIES: a non-empty chain / pair / clamp list under SpeciesBorrowing; VERT: vertical borrowing; SA: store always (else store where the
-// bits changed).
-template <bool SPECIES, bool VERT, bool SA>
+// SPECIES: a non-empty chain / pair / clamp list under SpeciesBorrowing; VERT: vertical borrowing.
+template <bool SPECIES, bool VERT>
 __global__ __launch_bounds__(64) void k_fix_negative_moisture(DevGrid g, NmcLists L, double *__restrict__ rq)
 {
     const int i = blockIdx.x * 64 + threadIdx.x, j = blockIdx.y;
@@ -106,7 +104,7 @@ __global__ __launch_bounds__(64) void k_fix_negative_moisture(DevGrid g, NmcList
         for (int k = Nz - 1; k >= 0; --k) {
             const long long n = n0 + (long long)k * sz;
             const double v0 = rq[n];
-            nmc_store<SA>(rq, n, nmc_species_cell<SA>(L, n, g.rho[k], v0), v0);
+            nmc_store(rq, n, nmc_species_cell(L, n, g.rho[k], v0), v0);
         }
         return;
     }
@@ -123,35 +121,29 @@ __global__ __launch_bounds__(64) void k_fix_negative_moisture(DevGrid g, NmcList
             // a value with a clear sign bit, or a NaN, on a positive density: no deficit, and +- 0 / dz leaves its bits alone
             work = work || (__builtin_signbit(v[u]) && v[u] == v[u]) || !(g.rho[k - u] > 0.0);
         }
-        if (!__any(work)) {
-            if (SA) {
-#pragma unroll
-                for (int u = 0; u < NMC_U; ++u) rq[n0 + (long long)(k - u) * sz] = v[u];
-            }
-            continue;
-        }
+        if (!__any(work)) continue;
 #pragma unroll
         for (int u = 0; u < NMC_U; ++u) {
             const long long n = n0 + (long long)(k - u) * sz;
-            if (SPECIES) v[u] = nmc_species_cell<SA>(L, n, g.rho[k - u], v[u]);
+            if (SPECIES) v[u] = nmc_species_cell(L, n, g.rho[k - u], v[u]);
             v[u] = nmc_down(g, k - u, v[u], carry);
-            nmc_store<SA>(rq, n, v[u], vin[u]);
+            nmc_store(rq, n, v[u], vin[u]);
         }
     }
     for (; k >= 2; --k) {
         const long long n = n0 + (long long)k * sz;
         const double vin = rq[n];
         double v = vin;
-        if (SPECIES) v = nmc_species_cell<SA>(L, n, g.rho[k], v);
+        if (SPECIES) v = nmc_species_cell(L, n, g.rho[k], v);
         v = nmc_down(g, k, v, carry);
-        nmc_store<SA>(rq, n, v, vin);
+        nmc_store(rq, n, v, vin);
     }
     double b0 = b0_in, b1 = b1_in;
     if (Nz >= 2) {
-        if (SPECIES) b1 = nmc_species_cell<SA>(L, n0 + sz, g.rho[1], b1);
+        if (SPECIES) b1 = nmc_species_cell(L, n0 + sz, g.rho[1], b1);
         b1 = nmc_down(g, 1, b1, carry);
     }
-    if (SPECIES) b0 = nmc_species_cell<SA>(L, n0, g.rho[0], b0);
+    if (SPECIES) b0 = nmc_species_cell(L, n0, g.rho[0], b0);
     const double dz0 = g.dzc[0];
     if (Nz >= 2) {
         // the bottom receives the last deficit, then borrows upward from level 2 what it lacks and level 2 has
@@ -161,13 +153,13 @@ __global__ __launch_bounds__(64) void k_fix_negative_moisture(DevGrid g, NmcList
         const double dq = (qb < 0.0 && qt > 0.0) ? nmc_min(-b0 * dz0, b1 * dz1) : 0.0;
         b0 = b0 + dq / dz0;
         b1 = b1 - dq / dz1;
-        nmc_store<SA>(rq, n0 + sz, b1, b1_in);
+        nmc_store(rq, n0 + sz, b1, b1_in);
     } else {
         // Nz = 1: k_top = k_bot, dq = 0 is added to and subtracted from the one cell
         b0 = b0 + 0.0 / dz0;
         b0 = b0 - 0.0 / dz0;
     }
-    nmc_store<SA>(rq, n0, b0, b0_in);
+    nmc_store(rq, n0, b0, b0_in);
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------------------------------
@@ -259,12 +251,7 @@ int bzi_fix_negative_moisture(bz_ctx *ctx, double *rho_q)
     const DevGrid &g = ctx->dg;
     ProfileScope ps(ctx, "fix_negative_moisture");
     const dim3 grid((g.Nx + 63) / 64, g.Ny), block(64);
-    const bool sa = ctx->tune.nmc_store_always;
-#define NMC_LAUNCH(S, V)                                                                                                          \
-    do {                                                                                                                          \
-        if (sa) hipLaunchKernelGGL((k_fix_negative_moisture<S, V, true>), grid, block, 0, ctx->stream, g, L, rho_q);              \
-        else hipLaunchKernelGGL((k_fix_negative_moisture<S, V, false>), grid, block, 0, ctx->stream, g, L, rho_q);                \
-    } while (0)
+#define NMC_LAUNCH(S, V) hipLaunchKernelGGL((k_fix_negative_moisture<S, V>), grid, block, 0, ctx->stream, g, L, rho_q)
     if (species && vert) NMC_LAUNCH(true, true);
     else if (species) NMC_LAUNCH(true, false);
     else NMC_LAUNCH(false, true);

@@ -572,26 +572,6 @@ int bzi_poisson_setup(bz_ctx *ctx, const double *h_rho /* Nz+2Hz, halo-inclusive
             ctx->kxmajor = true;
         }
     }
-    // chunk plans of the L3-resident pipeline
-    int ch = ctx->tune.poisson_chunk;
-    if (ch > 0 && ch < Nz && Nz % ch == 0 && !ctx->xf) {
-        BZ_FFT(hipfftPlanMany(&ctx->plan_fwd_c, 2, n, nullptr, 1, 0, nullptr, 1, 0, HIPFFT_D2Z, ch));
-        BZ_FFT(hipfftPlanMany(&ctx->plan_inv_c, 2, n, nullptr, 1, 0, nullptr, 1, 0, HIPFFT_Z2D, ch));
-        BZ_FFT(hipfftSetStream(ctx->plan_fwd_c, ctx->stream));
-        BZ_FFT(hipfftSetStream(ctx->plan_inv_c, ctx->stream));
-        ctx->pchunk = ch;
-    }
-    return BZ_OK;
-}
-
-// 2-D transforms of levels k0 .. k0 + pchunk - 1
-int bzi_fft_chunk(bz_ctx *ctx, int k0, bool forward)
-{
-    const DevGrid &g = ctx->dg;
-    double *real = ctx->d_rhs + (size_t)g.Nx * g.Ny * k0;
-    hipfftDoubleComplex *hat = ctx->d_hat + (size_t)ctx->NXH * g.Ny * k0;
-    if (forward) BZ_FFT(hipfftExecD2Z(ctx->plan_fwd_c, real, hat));
-    else BZ_FFT(hipfftExecZ2D(ctx->plan_inv_c, hat, real));
     return BZ_OK;
 }
 
@@ -612,7 +592,6 @@ void bzi_poisson_teardown(bz_ctx *ctx)
     if (ctx->plans_ok) {
         hipfftDestroy(ctx->plan_fwd);
         hipfftDestroy(ctx->plan_inv);
-        if (ctx->pchunk) { hipfftDestroy(ctx->plan_fwd_c); hipfftDestroy(ctx->plan_inv_c); ctx->pchunk = 0; }
         ctx->plans_ok = false;
     }
     if (ctx->d_dctx) hipFree(ctx->d_dctx);
@@ -798,7 +777,7 @@ int bzi_poisson_from_momentum(bz_ctx *ctx, const bz_state *s, double dt, const b
 {
     const DevGrid &g = ctx->dg;
     int rc;
-    if (ctx->xf && !ctx->pchunk) {
+    if (ctx->xf) {
         {
             ProfileScope ps(ctx, "poisson_source_term+fft_x");
             if ((rc = bzi_xf_forward(ctx, s, dt, predictor))) return rc;

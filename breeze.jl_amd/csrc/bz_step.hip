@@ -137,31 +137,11 @@ static int lean_project(bz_ctx *ctx, const bz_state *s, const LeanStage &L, cons
     return full ? bzi_project_diagnose(ctx, s, adt, nullptr, nullptr, G, true, L.oa, L.ob) : bzi_project_lean(ctx, &L.sout, adt, nullptr, nullptr, G, L.oa, L.ob);
 }
 
-// Pressure solve from the predictor in the G slots and the projection of a lean stage, in the context's variant of the solve.
-// forked: the scalar-pair kernel of the stage is on the side stream and joins before the projection.
-static int lean_solve_and_project(bz_ctx *ctx, const bz_state *s, const LeanStage &L, const bz_prognostic *G, double adt, bool full, bool forked)
+// Pressure solve from the predictor in the G slots and the projection of a lean stage: the hand-written x transforms or the library's 2-D plans
+static int lean_solve_and_project(bz_ctx *ctx, const bz_state *s, const LeanStage &L, const bz_prognostic *G, double adt, bool full)
 {
-    const DevGrid &g = ctx->dg;
-    const int ch = ctx->pchunk;
     int rc = BZ_OK;
-    if (ch) {
-        // chunked pipeline: each level range goes source term -> x transform -> y transform (and, after the vertical solves,
-        // y -> x -> projection) back to back, so the intermediate passes find the range in the Infinity Cache
-        {
-            ProfileScope ps(ctx, "poisson_source_term+fft_forward");
-            ctx->profile_mute++;
-            for (int k0 = 0; k0 < g.Nz && !rc; k0 += ch) {
-                ctx->kr0 = k0; ctx->krn = ch;
-                rc = bzi_poisson_source_fused(ctx, s, adt, nullptr, G);
-                if (!rc) rc = bzi_fft_chunk(ctx, k0, true);
-            }
-            ctx->krn = 0;
-            ctx->profile_mute--;
-        }
-        if (rc) return rc;
-        ProfileScope ps(ctx, "poisson_tridiagonal");
-        if ((rc = bzi_tridiag_launch(ctx, (double *)ctx->d_hat, 1.0 / ((double)g.Nx * (double)g.Ny), g.Ny, 1))) return rc;
-    } else if (ctx->xf) {
+    if (ctx->xf) {
         // hand-written x transforms (bz_xfft_kernels.h): the source term is evaluated inside the forward x pass; y transforms
         // (contiguous) and vertical solves on the transposed spectrum
         {
@@ -175,18 +155,7 @@ static int lean_solve_and_project(bz_ctx *ctx, const bz_state *s, const LeanStag
         if ((rc = bzi_poisson_source_fused(ctx, s, adt, nullptr, G))) return rc;
         if ((rc = bzi_poisson_spectral(ctx))) return rc;
     }
-    if (forked && (rc = bzi_scalar_pair_join(ctx))) return rc;
-    if (!ch) return lean_project(ctx, s, L, G, adt, full);
-    ProfileScope ps(ctx, !full ? "poisson_fft_inverse+project_momentum" : "poisson_fft_inverse+project_and_diagnose");
-    ctx->profile_mute++;
-    for (int k0 = 0; k0 < g.Nz && !rc; k0 += ch) {
-        if ((rc = bzi_fft_chunk(ctx, k0, false))) break;
-        ctx->kr0 = k0; ctx->krn = ch;
-        rc = lean_project(ctx, s, L, G, adt, full);
-    }
-    ctx->krn = 0;
-    ctx->profile_mute--;
-    return rc;
+    return lean_project(ctx, s, L, G, adt, full);
 }
 
 // Lean seam (bz_tendency5_kernels.h): the tendency kernels read the prognostic fields only and derive u, v, w, theta, q^v, T on the
@@ -197,18 +166,16 @@ static int step_lean(bz_ctx *ctx, const bz_state *s, const bz_prognostic *U0, co
 {
     int rc;
     if ((rc = bzi_zero_wall_faces(ctx, G, U0))) return rc;
-    const bool fork = ctx->side_scalar && !ctx->has_forcings;
     for (int stage = 0; stage < 3; ++stage) {
         const double alpha = BZ_SSP_RK3_ALPHA[stage];
         LeanStage L;
         bzi_lean_stage(s, U0, G, stage, &L);
-        if ((rc = bzi_lean_tendencies(ctx, L, G, dt, alpha, stage == 0, 0, fork ? 1 : 3))) return rc;
-        if (fork && (rc = bzi_scalar_pair_fork(ctx, L, G, dt, alpha, stage == 0))) return rc;
+        if ((rc = bzi_lean_tendencies(ctx, L, G, dt, alpha, stage == 0, 0, 3))) return rc;
         // the bottom fluxes of the stage (bzi_lean_forcings_ok), evaluated from the intact previous-stage momentum and added, weighted alpha dt, to
         // what the fused RK updates just wrote: the predictor momentum in the G slots and rho theta / rho q in the stage's output buffers (the Coriolis /
         // profile terms went into the RK epilogues: Lean5::mforce, bz_tendency5.hip; T is no stored field here: the next stage derives it from oa, ob)
         if (ctx->has_forcings && (rc = bzi_flux_bc(ctx, &L.sin, G->rho_u, G->rho_v, L.oa, L.ob, alpha * dt))) return rc;
-        if ((rc = lean_solve_and_project(ctx, s, L, G, alpha * dt, diagnose && stage == 2, fork))) return rc;
+        if ((rc = lean_solve_and_project(ctx, s, L, G, alpha * dt, diagnose && stage == 2))) return rc;
     }
     bzi_lean_step_done(ctx, diagnose);
     return BZ_OK;

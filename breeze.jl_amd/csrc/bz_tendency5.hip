@@ -41,14 +41,13 @@ int bzi_lean_setup(bz_ctx *ctx)
     hipLaunchKernelGGL(k_lev_rows, dim3((n + 63) / 64), dim3(64), 0, 0, g, ctx->d_pi_dry, (LevRow5 *)ctx->d_lev_rows, n);
     BZ_HIP(hipGetLastError());
     BZ_HIP(hipDeviceSynchronize());
-    // plain side stream: two unmasked streams take turns (every kernel stretches by the other's time), and a side stream on a CU mask of its
-    // own bought nothing either (HISTORY.md)
+    // the side stream of the slab driver's scalar-pair kernel (bz_comm.hip), plain: two unmasked streams take turns (every kernel stretches by
+    // the other's time), and a side stream on a CU mask of its own bought nothing either.  A single device keeps one stream: 47.4 -> 46.4
+    // ms/step at 512^3 with the fork, but concurrent kernels make per-kernel durations (and the roofline bookkeeping built on them)
+    // meaningless (HISTORY.md)
     BZ_HIP(hipStreamCreateWithFlags(&ctx->side_stream, hipStreamNonBlocking));
     BZ_HIP(hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming));
     BZ_HIP(hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming));
-    // single GPU: measured 47.4 -> 46.4 ms/step at 512^3 when on, but concurrent kernels make per-kernel durations (and the roofline
-    // bookkeeping built on them) meaningless, so it is opt-in there; the distributed step turns it on whenever messages are in flight
-    ctx->side_scalar = ctx->tune.side_scalar;
     ctx->lean = !ctx->tune.no_lean;
     ctx->lean_xcd = !ctx->tune.no_xcd;
     return BZ_OK;

@@ -275,13 +275,12 @@ def test_three_moist_steps_on_ragged_rows_match_oracle(oracle, oc, bz, size, kes
 
 
 # ---- 3. the new sweep against the old one -----------------------------------------------------------------------------------------------------
-def _sweep_run(oracle, oc, bz, monkeypatch, size, fwd2, pfold=0, cfg=29, bx=128):
+def _sweep_run(oracle, oc, bz, monkeypatch, size, fwd2, pfold=0, bx=128):
     monkeypatch.setenv("BZ_AC_FWD2", str(fwd2))
     if pfold is None:
         monkeypatch.delenv("BZ_AC_PFOLD", raising=False)
     else:
         monkeypatch.setenv("BZ_AC_PFOLD", str(pfold))
-    monkeypatch.setenv("BZ_AC_CFG", str(cfg))
     monkeypatch.setenv("BZ_AC_BX", str(bx))
     om, hm = _tg().make_pair(oracle, oc, bz, size=size, substeps=6)
     set_bubble(om, hm, oracle_too=False)
@@ -298,18 +297,17 @@ def _sweep_run(oracle, oc, bz, monkeypatch, size, fwd2, pfold=0, cfg=29, bx=128)
 @pytest.mark.parametrize("size", [(66, 6, 4), (130, 9, 6), (190, 12, 9), (258, 6, 4)], ids=_id)
 def test_forward2_on_ragged_rows_matches_the_column_kernel(oracle, oc, bz, size, monkeypatch):
     """k_ac_forward2 without the p^L fold carries the arithmetic text of k_ac_column_forward: three steps (the shape's stable dt) agree to 1e-13 on every prognostic
-    field (BZ_AC_FWD2 = 1 / 0, BZ_AC_PFOLD = 0), and the four row widths a block can have — 128 x 4, 512 x 1, 64 x 8, 256 x 2 (BZ_AC_CFG,
-    BZ_AC_BX = (29, 128), (29, 512), (13, 64), (13, 256), one bit-identical group of test_forward_sweep_round6_kernel) — give the same bits:
-    where a row's waves fall in a block, and which of them are ragged, changes nothing."""
+    field (BZ_AC_FWD2 = 1 / 0, BZ_AC_PFOLD = 0), and the four row widths a block can have — 128 x 4, 512 x 1, 64 x 8, 256 x 2 (BZ_AC_BX =
+    128, 512, 64, 256) — give the same bits: where a row's waves fall in a block, and which of them are ragged, changes nothing."""
     tg = _tg()
     old = _sweep_run(oracle, oc, bz, monkeypatch, size, 0)
-    ref = _sweep_run(oracle, oc, bz, monkeypatch, size, 1, 0, 29, 128)
+    ref = _sweep_run(oracle, oc, bz, monkeypatch, size, 1, 0, 128)
     for k in ref:
         assert tg.rel(ref[k], old[k]) <= 1e-13, (k, tg.rel(ref[k], old[k]), where(ref[k], old[k]))
-    for cfg, bx in ((29, 512), (13, 64), (13, 256)):
-        b = _sweep_run(oracle, oc, bz, monkeypatch, size, 1, 0, cfg, bx)
+    for bx in (512, 64, 256):
+        b = _sweep_run(oracle, oc, bz, monkeypatch, size, 1, 0, bx)
         for k in ref:
-            assert np.array_equal(b[k], ref[k]), (k, cfg, bx, where(b[k], ref[k]))
+            assert np.array_equal(b[k], ref[k]), (k, bx, where(b[k], ref[k]))
 
 
 @pytest.mark.gpu

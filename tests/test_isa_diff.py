@@ -73,3 +73,24 @@ def test_one_changed_operand_is_reported_as_different():
     assert isa_diff.report(a, b, out=out) == 1
     text = out.getvalue()
     assert "DIFFERENT _Z5k_twoPd" in text and "-\tv_add_f64 v[2:3], v[2:3], v1" in text and "+\tv_add_f64 v[2:3], v[2:3], v[4:5]" in text
+
+
+def test_rename_makes_a_kernel_that_lost_a_template_argument_compare_equal(tmp_path):
+    """k_two<29, true> of A is k_two<true> of B: the same text under another mangled name.  Without --rename it is gone from A and new in B
+    (exit status 1); with A's name rewritten it is equal, a changed operand still shows, and only the variant that was really removed
+    (k_two<13, true>) is left in A.  k_two is function 12 of A's file and function 1 of B's: the compiler pads the comment behind a label
+    to a column, so its labels are followed by one blank less."""
+    a = "\t.text\n" + _kernel("_Z5k_oneILi29ELb1EEvPd", 0) + _kernel("_Z5k_oneILi13ELb1EEvPd", 1) + _kernel("_Z5k_twoPd", 12).replace("_2: ", "_2:") + TAIL
+    b = "\t.text\n" + _kernel("_Z5k_oneILb1EEvPd", 0) + _kernel("_Z5k_twoPd", 1, first_label=5) + TAIL
+    for d, text in (("a", a), ("b", b), ("c", b.replace("v1", "v[4:5]", 1))):
+        (tmp_path / d).mkdir()
+        (tmp_path / d / "unit.s").write_text(text)
+    equal, differ, only_a, only_b = isa_diff.compare(isa_diff.load(tmp_path / "a"), isa_diff.load(tmp_path / "b"))
+    assert equal == ["unit.s: _Z5k_twoPd"] and only_b == ["unit.s: _Z5k_oneILb1EEvPd"] and len(only_a) == 2
+    renames = [(r"_Z5k_oneILi29E", "_Z5k_oneI")]
+    ra = isa_diff.load(tmp_path / "a", renames)
+    out = io.StringIO()
+    assert isa_diff.report(ra, isa_diff.load(tmp_path / "b"), out=out) == 0
+    assert out.getvalue().splitlines() == ["equal: 2  different: 0  only in A: 1  only in B: 0", "ONLY IN A unit.s: _Z5k_oneILi13ELb1EEvPd"]
+    equal, differ, only_a, only_b = isa_diff.compare(ra, isa_diff.load(tmp_path / "c"))
+    assert differ == ["unit.s: _Z5k_oneILb1EEvPd"] and equal == ["unit.s: _Z5k_twoPd"] and only_b == []

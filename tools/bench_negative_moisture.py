@@ -5,10 +5,11 @@ model, and that the uncorrected step did not pay for it.
 Grids 256 x 256 x 128 and 512 x 512 x 256 over 25.6 km x 25.6 km x 10 km, Float64 and Float32, WENO(order = 5), warm-phase saturation
 adjustment under theta_0 = 300 K.
   kernel   ms per launch of k_fix_negative_moisture (profile slot fix_negative_moisture) on a field without negative cells and on one with
-           about a tenth of its cells negative (scattered cells and whole upper layers, so deficits travel), under both store policies
-           (store where the bits changed: the default; BZ_NMC_STORE_ALWAYS=1: every cell), against its compulsory bytes (one word read per
-           cell, one written per cell that changes) and the 8 TB/s roofline.  The field is restored from a copy before every launch (not
-           timed: the slot's events bracket the kernel alone); windows of `--launches` launches rotate over the four cases.
+           about a tenth of its cells negative (scattered cells and whole upper layers, so deficits travel), against its compulsory bytes
+           (one word read per cell, one written per cell that changes) and the 8 TB/s roofline.  The kernel stores a cell where its bits
+           changed; the store-always policy it was measured against is in the recorded lines (policy = "store_always") and in DESIGN §7.
+           The field is restored from a copy before every launch (not timed: the slot's events bracket the kernel alone); windows of
+           `--launches` launches alternate between the two cases.
   step     ms per time_step of the corrected model and of the model built with the bare SaturationAdjustment, same build, same state (a
            saturated column, a warm bubble, about a tenth of the cells of the upper levels negative), alternating windows
   parent   (--parent-lib DIR: libbreeze_hip.so / libbreeze_hip_f32.so built from the parent commit) the uncorrected step on this build and on
@@ -64,16 +65,13 @@ def main():
     import breeze_jl_amd as bz
     from breeze_jl_amd import _lib
 
-    def build(size, ft, corrected, lib_dir=None, store_always=False):
+    def build(size, ft, corrected, lib_dir=None):
         own = (_lib.LIB_PATH, _lib.F32_LIB_PATH)
         if lib_dir:          # the model binds the library its constructor finds under these names
             _lib.LIB_PATH, _lib.F32_LIB_PATH = os.path.join(lib_dir, "libbreeze_hip.so"), os.path.join(lib_dir, "libbreeze_hip_f32.so")
             for p in (_lib.LIB_PATH, _lib.F32_LIB_PATH):
                 if p not in _lib._libs:
                     bind_parent(p)
-        os.environ.pop("BZ_NMC_STORE_ALWAYS", None)
-        if store_always:          # read once, when the context is created
-            os.environ["BZ_NMC_STORE_ALWAYS"] = "1"
         try:
             g = bz.RectilinearGrid(size, x=(0.0, 25.6e3), y=(0.0, 25.6e3), z=(0.0, 10e3), float_type=ft)
             ref = bz.ReferenceState(g, potential_temperature=300.0)
@@ -82,7 +80,6 @@ def main():
             m = bz.AtmosphereModel(g, dynamics=bz.AnelasticDynamics(ref), advection=bz.WENO(order=5), microphysics=micro)
         finally:
             _lib.LIB_PATH, _lib.F32_LIB_PATH = own
-            os.environ.pop("BZ_NMC_STORE_ALWAYS", None)
         return m, ref
 
     def state(size, m, ref, negatives):
@@ -160,34 +157,33 @@ def main():
 
             # ---- the kernel per launch ----
             cases = {}
-            for policy, always in (("store_if_changed", False), ("store_always", True)):
-                m, ref = build(size, ft, True, store_always=always)
-                m.profile_enable(True)
-                rng = np.random.default_rng(1)
-                rho = np.asarray(ref.density)[m.grid.Hz:m.grid.Hz + m.grid.Nz][:, None, None]
-                clean = (rho * (1e-3 + 1e-2 * rng.random((size[2], size[1], size[0])))).astype(ft)
-                neg = clean.copy()
-                neg[rng.random(neg.shape) < 0.07] *= -0.3                               # scattered cells
-                neg[size[2] - max(1, (3 * size[2]) // 100):] *= -0.05                   # whole upper layers: deficits travel
-                for name, arr in (("no_negatives", clean), ("tenth_negative", neg)):
-                    m.moisture_density.set_interior(arr)
-                    saved = m.moisture_density.parent.clone()
-                    bz.fix_negative_moisture_(m)
-                    m.synchronize()
-                    after = m.moisture_density.interior.cpu().numpy()
-                    changed = int((after.view(np.uint64 if word == 8 else np.uint32) != arr.view(np.uint64 if word == 8 else np.uint32)).sum())
-                    cases[(policy, name)] = dict(model=m, saved=saved, negative_fraction=float((arr < 0).mean()), changed=changed)
+            m, ref = build(size, ft, True)
+            m.profile_enable(True)
+            rng = np.random.default_rng(1)
+            rho = np.asarray(ref.density)[m.grid.Hz:m.grid.Hz + m.grid.Nz][:, None, None]
+            clean = (rho * (1e-3 + 1e-2 * rng.random((size[2], size[1], size[0])))).astype(ft)
+            neg = clean.copy()
+            neg[rng.random(neg.shape) < 0.07] *= -0.3                               # scattered cells
+            neg[size[2] - max(1, (3 * size[2]) // 100):] *= -0.05                   # whole upper layers: deficits travel
+            for name, arr in (("no_negatives", clean), ("tenth_negative", neg)):
+                m.moisture_density.set_interior(arr)
+                saved = m.moisture_density.parent.clone()
+                bz.fix_negative_moisture_(m)
+                m.synchronize()
+                after = m.moisture_density.interior.cpu().numpy()
+                changed = int((after.view(np.uint64 if word == 8 else np.uint32) != arr.view(np.uint64 if word == 8 else np.uint32)).sum())
+                cases[name] = dict(saved=saved, negative_fraction=float((arr < 0).mean()), changed=changed)
             for case in cases.values():
-                kernel_window(case["model"], case["saved"])          # warm-up
+                kernel_window(m, case["saved"])          # warm-up
             times = {k: [] for k in cases}
             keys = list(cases)
             for r in range(a.rounds):
                 for k in keys[r % len(keys):] + keys[:r % len(keys)]:
-                    times[k].append(kernel_window(cases[k]["model"], cases[k]["saved"]))
-            for (policy, name), case in cases.items():
-                t = stats(times[(policy, name)])
+                    times[k].append(kernel_window(m, cases[k]["saved"]))
+            for name, case in cases.items():
+                t = stats(times[name])
                 nbytes = (cells + case["changed"]) * word
-                emit(what="kernel", policy=policy, field=name, negative_fraction=case["negative_fraction"], cells_changed=case["changed"],
+                emit(what="kernel", policy="store_if_changed", field=name, negative_fraction=case["negative_fraction"], cells_changed=case["changed"],
                      launches_per_window=a.launches, windows=a.rounds, ms_per_launch=t, compulsory_bytes=nbytes,
                      share_of_8TBs=nbytes / (t["median"] * 1e-3) / ROOFLINE)
             del cases, case, m, saved

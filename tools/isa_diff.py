@@ -1,14 +1,17 @@
 #!/usr/bin/env python3
 """Compare the device assembly of two builds, kernel by kernel.
 
-    python3 tools/isa_diff.py DIR_A DIR_B [--diff-lines N]
+    python3 tools/isa_diff.py DIR_A DIR_B [--diff-lines N] [--rename REGEX REPL]...
 
 DIR_A and DIR_B hold the `hipcc --cuda-device-only -S` output of the same translation units (any *.s below them).  Per function symbol
 the tool reports: equal text in both, different text (with a short unified diff), only in A, only in B.  "Text" is the function body
 from its label to its .Lfunc_end label plus its .amdhsa_kernel ... .end_amdhsa_kernel descriptor.  Local labels that carry the index of
 the function inside its file (.LBB<i>_<n>, .LJTI<i>_<n>, .Ltmp<n>, .Lfunc_end<i>) are renumbered by order of first appearance inside
-the function, so a kernel compares equal when kernels in front of it came or went.  __hip_cuid_* is ignored.  The comparison is of
-text alone.  Exit status 1 when a symbol differs or exists in B only.
+the function, so a kernel compares equal when kernels in front of it came or went; the blanks in front of a comment count as one (the
+compiler pads a label's comment to a column, so the padding moves with the width of the index).  __hip_cuid_* is ignored.  --rename REGEX REPL (may
+be repeated) is re.sub applied to every line of A, symbols included, before anything is compared: a kernel that lost a template argument
+has another mangled name in B, and compares equal to its form in A once A's name is rewritten.  The comparison is of text alone.  Exit
+status 1 when a symbol differs or exists in B only.
 """
 import argparse
 import difflib
@@ -20,6 +23,7 @@ TYPE = re.compile(r"^\s*\.type\s+([^\s,]+),@function")
 FUNC_END = re.compile(r"^\.Lfunc_end\d+:")
 DESC_BEGIN = re.compile(r"^\s*\.amdhsa_kernel\s+(\S+)")
 DESC_END = re.compile(r"^\s*\.end_amdhsa_kernel")
+PAD = re.compile(r"[ \t]+;")
 LOCAL = re.compile(r"(?:\.L|\b)(BB|JTI)\d+_(\d+)|\.L(tmp)(\d+)|\.L(func_end)\d+")      # the compiler's loop comments say BB<i>_<n> without .L
 
 
@@ -35,7 +39,7 @@ def renumber(lines):
             seen[key] = sum(1 for k in seen if k[0] == kind)
         return "%s%s_%d" % (".L" if m.group(0).startswith(".L") else "", kind, seen[key])
 
-    return [LOCAL.sub(sub, ln) for ln in lines]
+    return [PAD.sub(" ;", LOCAL.sub(sub, ln)) for ln in lines]
 
 
 def functions(text):
@@ -69,10 +73,16 @@ def functions(text):
     return {name: renumber(lines + desc.get(name, [])) for name, lines in body.items()}
 
 
-def load(root):
+def rename(text, renames):
+    for pattern, repl in renames:
+        text = re.sub(pattern, repl, text)
+    return text
+
+
+def load(root, renames=()):
     out = {}
     for path in sorted(pathlib.Path(root).rglob("*.s")):
-        for name, lines in functions(path.read_text()).items():
+        for name, lines in functions(rename(path.read_text(), renames)).items():
             out["%s: %s" % (path.relative_to(root), name)] = lines      # per file: several units may instantiate the same template
     return out
 
@@ -102,5 +112,6 @@ if __name__ == "__main__":
     ap.add_argument("dir_a")
     ap.add_argument("dir_b")
     ap.add_argument("--diff-lines", type=int, default=40)
+    ap.add_argument("--rename", nargs=2, action="append", default=[], metavar=("REGEX", "REPL"))
     args = ap.parse_args()
-    sys.exit(report(load(args.dir_a), load(args.dir_b), args.diff_lines))
+    sys.exit(report(load(args.dir_a, args.rename), load(args.dir_b), args.diff_lines))

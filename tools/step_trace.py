@@ -134,10 +134,7 @@ def single_device_cases(bz):
         # lean tier
         "lean/dry_bubble": ({}, lambda: dry_bubble(bz), 2.0),
         "lean/vapour": ({}, lambda: moist_bubble(bz), 2.0),
-        "lean/side_scalar": ({"BZ_SIDE_SCALAR": "1"}, lambda: dry_bubble(bz), 2.0),
         "lean/no_xfft": ({"BZ_NO_XFFT": "1"}, lambda: dry_bubble(bz), 2.0),
-        "lean/chunked_pipeline": ({"BZ_NO_XFFT": "1", "BZ_POISSON_CHUNK": "4"}, lambda: dry_bubble(bz), 2.0),
-        "lean/chunked_pipeline_side_scalar": ({"BZ_NO_XFFT": "1", "BZ_POISSON_CHUNK": "4", "BZ_SIDE_SCALAR": "1"}, lambda: moist_bubble(bz), 2.0),
         "lean/cbl_forcing_stack": ({}, lambda: cbl(bz), 0.05),
         "lean/walls_in_y": ({}, lambda: dry_bubble(bz, topology=PBB), 2.0),
         "lean/cbl_walls_in_y": ({}, lambda: cbl(bz, topology=PBB), 0.05),
