@@ -198,7 +198,8 @@ def refuse_bulk_microphysics(microphysics, where, why):
 
 def refuse_mixed_phase(microphysics, where, why):
     """SaturationAdjustment(equilibrium = MixedPhaseEquilibrium()) runs on the single-device anelastic AtmosphereModel (potential-temperature
-    formulation, Clausius-Clapeyron constants); every other place says so here, where the microphysics type is checked."""
+    formulation) and, attached by compressible.set_mixed_phase_equilibrium_, on the single-device CompressibleAtmosphereModel that is
+    periodic in x and y or Flat in y; every other place says so here, where the microphysics type is checked."""
     if is_mixed_phase(microphysics):
         raise NotImplementedError(f"{where}: SaturationAdjustment(equilibrium = MixedPhaseEquilibrium()) is not implemented ({why}); "
                                   "pass equilibrium = WarmPhaseEquilibrium()")
@@ -220,6 +221,23 @@ def check_mixed_phase_model(microphysics, thermodynamic_constants, forcing, boun
         refuse_mixed_phase(microphysics, where, "bulk surface fluxes and the surface layer form cᵖᵐ without qⁱ")
     if any(_key(name) == "ρe" for name in (boundary_conditions or {})):
         refuse_mixed_phase(microphysics, where, "a bottom flux keyed ρe: the energy-to-θ conversion forms cᵖᵐ without qⁱ")
+
+
+def check_mixed_phase_compressible(microphysics, where, thermodynamic_constants, surface_fluxes, slab, walls):
+    """What compressible.set_mixed_phase_equilibrium_ does not attach the mixed-phase form to: y-slabs (their halo exchanges carry qᵛ and qˡ),
+    lateral walls, Tetens constants and the bulk surface fluxes, whose kernel forms cᵖᵐ from qᵛ and qˡ alone.  (The constructors refuse
+    BulkMicrophysics, and InstantaneousPrecipitation(equilibrium = MixedPhaseEquilibrium()) refuses itself.)"""
+    if not is_mixed_phase(microphysics):
+        return
+    from .microphysics import TetensFormula
+    if slab:
+        refuse_mixed_phase(microphysics, where, "the halo exchanges of y-slab models carry qᵛ and qˡ only")
+    if walls:
+        refuse_mixed_phase(microphysics, where, "SaturationAdjustment is not built on a compressible model between walls (Bounded x / Bounded y)")
+    if isinstance(getattr(thermodynamic_constants, "saturation_vapor_pressure", None), TetensFormula):
+        refuse_mixed_phase(microphysics, where, "TetensFormula constants: the ice coefficients of the Tetens formula are not mirrored")
+    if surface_fluxes:
+        refuse_mixed_phase(microphysics, where, "bulk surface fluxes form cᵖᵐ without qⁱ")
 
 
 def flatau_polynomial(thermodynamic_constants):

@@ -256,6 +256,7 @@ SYMBOLS = {
     "bz_set_formulation": (C.c_int, [_ctx, C.c_int]),
     "bz_set_saturation_adjustment": (C.c_int, [_ctx, C.POINTER(bz_saturation_adjustment), C.c_void_p, C.c_void_p]),
     "bz_set_mixed_phase_equilibrium": (C.c_int, [_ctx, C.POINTER(bz_mixed_phase_equilibrium), C.c_void_p]),
+    "bz_set_compressible_mixed_phase_equilibrium": (C.c_int, [_ctx, C.POINTER(bz_mixed_phase_equilibrium), C.c_void_p]),
     "bz_set_saturation_vapor_pressure_polynomial": (C.c_int, [_ctx, C.POINTER(bz_flatau_polynomial)]),
     "bz_set_negative_moisture_correction": (C.c_int, [_ctx, C.POINTER(bz_negative_moisture_correction)]),
     "bz_fix_negative_moisture": (C.c_int, [_ctx, C.POINTER(bz_state)]),

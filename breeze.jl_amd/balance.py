@@ -83,6 +83,10 @@ def require_balance_model(model, balancer, what="balance_adiabatically!"):
             return None
         raise TypeError(f"{what}: `balancer` must be an AdiabaticBalancer or a Bool")
     if _is_compressible(model):
+        if balancer.with_moisture:      # the twin steps the moisture with the vapour-only thermodynamics; its closing update_state! would re-partition it
+            from ._context import refuse_mixed_phase
+            refuse_mixed_phase(getattr(model, "microphysics", None), f"{what} (with_moisture = true)", "the balance of the moisture-carrying compressible state is "
+                               "checked against the warm-phase adjustment only; pass with_moisture=False")
         ts = balancer.time_stepping
         if isinstance(ts, DefaultTimeStepping):
             raise NotImplementedError(f"{what}: the default time_stepping of AdiabaticBalancer is the fully explicit twin "

@@ -452,7 +452,9 @@ class CompressibleAtmosphereModel(_context.ContextOwner):
                       if type(self) is not CompressibleAtmosphereModel
                       else "InstantaneousPrecipitation: not implemented on a compressible model with a Flat y" if Flat in grid.topology else None)
         _context.refuse_bulk_microphysics(microphysics, type(self).__name__, "the moisture update of CompressibleDynamics is fused into the acoustic stage epilogue")
-        _context.refuse_mixed_phase(microphysics, type(self).__name__, "the density-based mixed-phase adjustment of CompressibleDynamics is the follow-up")
+        # the constructor attaches the warm-phase adjustment; the density-based mixed-phase form is attached to the built model (set_mixed_phase_equilibrium_)
+        _context.refuse_mixed_phase(microphysics, type(self).__name__, "the constructor attaches the warm-phase density-based adjustment; the mixed-phase "
+                                    "form is attached to the built model by compressible.set_mixed_phase_equilibrium_(model, MixedPhaseEquilibrium(...))")
         self._kessler = _context.check_microphysics(microphysics, "compressible microphysics: DCMIP2016KesslerMicrophysics() and "
                                                                   "SaturationAdjustment(equilibrium = WarmPhaseEquilibrium()) are implemented",
                                                     instantaneous_precipitation_refused=ip_refused)
@@ -628,6 +630,43 @@ def detach_surface_fluxes_(model):
     model._surface_fluxes = {}
 
 
+def set_mixed_phase_equilibrium_(model, equilibrium):
+    """equilibrium = MixedPhaseEquilibrium(Tᶠ, Tʰ) of the SaturationAdjustment of a built CompressibleAtmosphereModel: the density-based
+    adjustment on the mixed surface (adjust_thermodynamic_state(::LiquidIceDensityState, ::SaturationAdjustment),
+    src/Microphysics/saturation_adjustment.jl:241-293) through bz_set_compressible_mixed_phase_equilibrium.  The model is one built with
+    SaturationAdjustment(equilibrium = WarmPhaseEquilibrium()); its `microphysics` becomes the adjustment with the given equilibrium (same
+    solver) and microphysical_fields gains qⁱ (materialize_microphysical_fields(::MPSA), saturation_adjustment.jl:119), which update_state!
+    and every stage epilogue diagnose from then on: call it before set!, or follow it with update_state_.  `equilibrium` a
+    WarmPhaseEquilibrium (or None) returns the model to the warm phase.  What the mixed form does not run with raises NotImplementedError
+    naming MixedPhaseEquilibrium before the context is touched: y-slabs, walls, bulk surface fluxes, TetensFormula constants."""
+    from .microphysics import MixedPhaseEquilibrium, SaturationAdjustment, WarmPhaseEquilibrium
+    current = getattr(model, "microphysics", None)
+    if not isinstance(model, CompressibleAtmosphereModel):
+        raise TypeError("set_mixed_phase_equilibrium_: `model` must be a CompressibleAtmosphereModel (AtmosphereModel takes the equilibrium in its constructor)")
+    if not getattr(model, "_sa", False) or not isinstance(current, SaturationAdjustment):
+        raise NotImplementedError("set_mixed_phase_equilibrium_: MixedPhaseEquilibrium belongs to a SaturationAdjustment, and the model was built with "
+                                  f"microphysics = {type(current).__name__}; build it with SaturationAdjustment(equilibrium = WarmPhaseEquilibrium())")
+    name = "bz_set_compressible_mixed_phase_equilibrium"
+    if equilibrium is None or isinstance(equilibrium, WarmPhaseEquilibrium):
+        model._check(getattr(model._lib, name)(model._ctx, None, None), name)
+        model.microphysics = SaturationAdjustment(solver=current.solver, equilibrium=WarmPhaseEquilibrium())
+        model.microphysical_fields.pop("qⁱ", None)
+        return model
+    if not isinstance(equilibrium, MixedPhaseEquilibrium):
+        raise TypeError("set_mixed_phase_equilibrium_: `equilibrium` must be a MixedPhaseEquilibrium or a WarmPhaseEquilibrium")
+    adjustment = SaturationAdjustment(solver=current.solver, equilibrium=equilibrium)
+    _context.check_mixed_phase_compressible(adjustment, "set_mixed_phase_equilibrium_", model.thermodynamic_constants, model._surface_fluxes,
+                                            slab=type(model) is not CompressibleAtmosphereModel, walls=model.lateral_walls)
+    c, μ = model.thermodynamic_constants, model.microphysical_fields
+    qi = μ["qⁱ"] if "qⁱ" in μ else Field(model.grid, _LOC["ccc"], model.device)
+    mp = model._T.bz_mixed_phase_equilibrium(equilibrium.freezing_temperature, equilibrium.homogeneous_ice_nucleation_temperature,
+                                             c.ice_reference_latent_heat, c.ice_heat_capacity)
+    model._check(getattr(model._lib, name)(model._ctx, C.byref(mp), C.c_void_p(qi.ptr())), name)
+    model.microphysical_fields = {"qᵛ": μ["qᵛ"], "qˡ": μ["qˡ"], "qⁱ": qi, "qᵉ": μ["qᵉ"]}
+    model.microphysics = adjustment
+    return model
+
+
 def acoustic_rk3_substep_loop_(model, Δt, β):
     model._check(model._lib.bz_acoustic_substep_loop(model._ctx, C.byref(model._state), C.byref(model._U0), C.byref(model._G),
                                                      C.byref(model._sub), float(Δt), float(β)), "bz_acoustic_substep_loop")
@@ -671,6 +710,8 @@ def _require_balance_scope(model, what):
         raise NotImplementedError(f"{what}: not implemented on a compressible model between walls (Bounded x / Bounded y)")
     if type(model) is not CompressibleAtmosphereModel:
         raise NotImplementedError(f"{what}: not implemented on y-slab (distributed) compressible models")
+    # the balanced columns and the reference profiles are integrated with Rᵐ and cᵖᵐ of (qᵛ, qˡ): no ice fraction
+    _context.refuse_mixed_phase(getattr(model, "microphysics", None), what, "the hydrostatic columns are integrated without qⁱ")
 
 
 def specific_humidity(model):
@@ -742,6 +783,8 @@ def set_(model, compute_reference_state=False, balancer=None, **kw):
     keys = {}
     for name, value in kw.items():
         key = _ALIASES.get(name)
+        if key is None and name in ("T", "ℋ", "H", "relative_humidity"):      # (set!(T | ℋ) is not built here; a mixed-phase model says why it could not be)
+            _context.refuse_mixed_phase(model.microphysics, f"set!(model; {name})", "θ from T and qᵛ⁺ from ℋ are formed without qⁱ and over the liquid surface")
         if key is None:
             raise ValueError(f"Cannot set! {name} in AtmosphereModel because {name} is neither a prognostic variable, a "
                              "settable thermodynamic variable, nor a settable diagnostic variable!")

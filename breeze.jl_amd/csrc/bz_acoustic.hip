@@ -404,7 +404,7 @@ int bzi_acoustic_stage_end_fused(bz_ctx *ctx, const bz_compressible_state *s, co
             ProfileScope ps(ctx, with_linearization ? "acoustic_stage_end+update_state+linearization" : "acoustic_stage_end+update_state");
             bz_bools([&](auto da, auto lin) {
                 constexpr bool DAMP = da(), LIN = lin();
-                bz_static_int<4>(bzi_cmp_mp(ctx), [&](auto mp) {
+                bz_static_int<6>(bzi_cmp_mp(ctx), [&](auto mp) {
                     hipLaunchKernelGGL((k_ac_stage_end<DAMP, LIN, mp(), ST>), rows, b256, 0, ctx->stream, g, ac_cast<ST>(F), D, Pe, dts, (ST *)thL_out, na, nm, bzi_flatau(ctx));
                 });
             }, S.damping, with_linearization);

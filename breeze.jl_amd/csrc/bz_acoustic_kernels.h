@@ -724,7 +724,8 @@ template <bool DAMP, bool LIN, int MP, class ST>
 __global__ __launch_bounds__(256) void k_ac_stage_end(DevGrid g, AcFieldsT<ST> F, DiagFields D, AcParams P, double dt_stage, ST *__restrict__ thL_out,
                                                       double abstol, int maxiter, const double *fl)
 {
-    constexpr bool KES = (MP == 2), SA = (MP == 1 || MP == 3), FL = (MP == 3);      // 3: the FlatauPolynomial instantiation of 1 (k_cmp_diagnose)
+    // 3: the FlatauPolynomial instantiation of 1; 4 | 5: the mixed-phase instantiations of 1 | 3 (k_cmp_diagnose)
+    constexpr bool KES = (MP == 2), MIX = (MP == 4 || MP == 5), SA = (MP == 1 || MP == 3 || MIX), FL = (MP == 3 || MP == 5);
     int bx, j, k;
     ac_pencil_block(bx, j, k);
     const int i = bx * 256 + threadIdx.x;
@@ -809,7 +810,7 @@ __global__ __launch_bounds__(256) void k_ac_stage_end(DevGrid g, AcFieldsT<ST> F
         st_img(D.rw, n + sz, 0.0, ox, oy);
         st_img(D.w, n + sz, 0.0, ox, oy);
     }
-    double r, q, th, T, p, qcl_v = 0.0, qr_v = 0.0, sa_qv = 0.0, sa_ql = 0.0;
+    double r, q, th, T, p, qcl_v = 0.0, qr_v = 0.0, sa_qv = 0.0, sa_ql = 0.0, sa_qi = 0.0;
     {
         double ql = 0.0;
         if (KES) r = rd + (rq + (rqcl + (rqr + 0.0)));
@@ -822,15 +823,22 @@ __global__ __launch_bounds__(256) void k_ac_stage_end(DevGrid g, AcFieldsT<ST> F
             ql = qcl_v + qr_v;
         }
         double qvap = q;
-        if (SA) {
+        if constexpr (MIX) {
+            T = bz_ds_adjust_mixed<FL>(g, th, q, r, abstol, maxiter, qvap, ql, sa_qi, ColPtr(fl));
+            st_img(g.qv_field, n, qvap, ox, oy);
+            st_img(g.ql_field, n, ql, ox, oy);
+            st_img(g.qi_field, n, sa_qi, ox, oy);
+            sa_qv = qvap; sa_ql = ql;
+        } else if (SA) {
             T = bz_ds_adjust<FL>(g, th, q, r, abstol, maxiter, qvap, ql, ColPtr(fl));
             st_img(g.qv_field, n, qvap, ox, oy);
             st_img(g.ql_field, n, ql, ox, oy);
             sa_qv = qvap; sa_ql = ql;
         }
-        const double qd = 1.0 - (qvap + ql);
+        const double qd = MIX ? 1.0 - (qvap + ql + sa_qi) : 1.0 - (qvap + ql);
         const double Rm = qd * g.Rd + qvap * g.Rv;
-        const double cpm = (KES || SA) ? qd * g.cpd + qvap * g.cpv + ql * g.sa_cl : qd * g.cpd + qvap * g.cpv;
+        const double cpm = MIX ? qd * g.cpd + qvap * g.cpv + ql * g.sa_cl + sa_qi * g.sa_ci
+                               : (KES || SA) ? qd * g.cpd + qvap * g.cpv + ql * g.sa_cl : qd * g.cpd + qvap * g.cpv;
         if (!SA) {
             const double kap = Rm / cpm;
             const double gam = cpm / (cpm - Rm);
@@ -885,6 +893,7 @@ __global__ __launch_bounds__(256) void k_ac_stage_end(DevGrid g, AcFieldsT<ST> F
             st_img(g.qv_field, n + h, sa_qv, ox, oy);
             st_img(g.ql_field, n + h, sa_ql, ox, oy);
         }
+        if constexpr (MIX) st_img(g.qi_field, n + h, sa_qi, ox, oy);
         if (KES) {
             st_img(F.rqcl, n + h, rqcl, ox, oy);
             st_img(F.rqr, n + h, rqr, ox, oy);

@@ -16,6 +16,9 @@
 // diagnosed by bz_ds_adjust at the cell's own total density and the temperature is the same Newton inversion with the latent
 // term (compressible_time_stepping.jl:191-250; saturation_adjustment.jl:236-301)
 // MP = 3: MP = 1 with saturation_vapor_pressure = FlatauPolynomial (bz_set_saturation_vapor_pressure_polynomial): bz_ds_adjust<true>
+// MP = 4: SaturationAdjustment(MixedPhaseEquilibrium(T^f, T^h)) (bz_set_compressible_mixed_phase_equilibrium): bz_ds_adjust_mixed diagnoses
+// q^v, q^l and q^i; R_m, c_pm, the pressure and (LIN) the linearisation carry the ice fraction (acoustic_substepping.jl:390-410);
+// MP = 5: MP = 4 on the FlatauPolynomial surface.  The host picks the instantiation (bzi_cmp_mp): MP <= 3 read no mixed-phase member.
 // WY: walls in y (topology (Periodic, Bounded, Bounded), dry or vapour-carrying models).  The halo writes follow the conventions of
 // DESIGN section 6 "Walls in y" instead of periodic images: a field that is a centre in y gets the no-flux copy of rows 0 and Ny - 1 in its
 // first halo rows (oy = one row down / up for those two rows), rho v and v get exact zeros on their wall faces 0 and Ny (face Ny is the first
@@ -24,7 +27,7 @@
 template <bool FULL, bool LIN, int MP = 0, bool WY = false>
 __global__ __launch_bounds__(256) void k_cmp_diagnose(DevGrid g, DiagFields F, double abstol, int maxiter, const double *fl)
 {
-    constexpr bool KES = (MP == 2), SA = (MP == 1 || MP == 3), FL = (MP == 3);
+    constexpr bool KES = (MP == 2), MIX = (MP == 4 || MP == 5), SA = (MP == 1 || MP == 3 || MIX), FL = (MP == 3 || MP == 5);
     static_assert(!WY || (MP == 0 && !LIN), "walls in y: no microphysics; the linearisation is refreshed by its own kernel (halo rows)");
     const int i = blockIdx.x * 256 + threadIdx.x, j = blockIdx.y, k = blockIdx.z;
     if (i >= g.Nx) return;
@@ -62,7 +65,7 @@ __global__ __launch_bounds__(256) void k_cmp_diagnose(DevGrid g, DiagFields F, d
         st_img(F.rw, n + sz, 0.0, ox, oy);
         st_img(F.w, n + sz, 0.0, ox, oy);
     }
-    double r = 0.0, q = 0.0, th = 0.0, T = 0.0, p = 0.0, rq = 0.0, qcl_v = 0.0, qr_v = 0.0, sa_qv = 0.0, sa_ql = 0.0;
+    double r = 0.0, q = 0.0, th = 0.0, T = 0.0, p = 0.0, rq = 0.0, qcl_v = 0.0, qr_v = 0.0, sa_qv = 0.0, sa_ql = 0.0, sa_qi = 0.0;
     if (FULL) {
         rq = F.rq[n];
         double rqcl = 0.0, rqr = 0.0, ql = 0.0;
@@ -81,15 +84,22 @@ __global__ __launch_bounds__(256) void k_cmp_diagnose(DevGrid g, DiagFields F, d
             ql = qcl_v + qr_v;
         }
         double qvap = q;        // vapour fraction of the mixture constants (q itself unless the adjustment partitions it)
-        if (SA) {
+        if constexpr (MIX) {
+            T = bz_ds_adjust_mixed<FL>(g, th, q, r, abstol, maxiter, qvap, ql, sa_qi, ColPtr(fl));
+            st_img(g.qv_field, n, qvap, ox, oy);
+            st_img(g.ql_field, n, ql, ox, oy);
+            st_img(g.qi_field, n, sa_qi, ox, oy);
+            sa_qv = qvap; sa_ql = ql;
+        } else if (SA) {
             T = bz_ds_adjust<FL>(g, th, q, r, abstol, maxiter, qvap, ql, ColPtr(fl));
             st_img(g.qv_field, n, qvap, ox, oy);
             st_img(g.ql_field, n, ql, ox, oy);
             sa_qv = qvap; sa_ql = ql;
         }
-        const double qd = 1.0 - (qvap + ql);
+        const double qd = MIX ? 1.0 - (qvap + ql + sa_qi) : 1.0 - (qvap + ql);
         const double Rm = qd * g.Rd + qvap * g.Rv;
-        const double cpm = (KES || SA) ? qd * g.cpd + qvap * g.cpv + ql * g.sa_cl : qd * g.cpd + qvap * g.cpv;
+        const double cpm = MIX ? qd * g.cpd + qvap * g.cpv + ql * g.sa_cl + sa_qi * g.sa_ci
+                               : (KES || SA) ? qd * g.cpd + qvap * g.cpv + ql * g.sa_cl : qd * g.cpd + qvap * g.cpv;
         if (!SA) {
             const double kap = Rm / cpm;
             const double gam = cpm / (cpm - Rm);
@@ -147,6 +157,7 @@ __global__ __launch_bounds__(256) void k_cmp_diagnose(DevGrid g, DiagFields F, d
                 st_img(g.qv_field, n + h, sa_qv, ox, oy);
                 st_img(g.ql_field, n + h, sa_ql, ox, oy);
             }
+            if constexpr (MIX) st_img(g.qi_field, n + h, sa_qi, ox, oy);
             if (KES) {
                 st_img(g.rqcl_field, n + h, g.rqcl_field[n], ox, oy);
                 st_img(g.rqr_field, n + h, g.rqr_field[n], ox, oy);
@@ -158,7 +169,9 @@ __global__ __launch_bounds__(256) void k_cmp_diagnose(DevGrid g, DiagFields F, d
     }
 }
 
-// refresh_linearization_basic_state! (acoustic_substepping.jl:318-399)
+// refresh_linearization_basic_state! (acoustic_substepping.jl:318-399); MIX: the mixed-phase instantiation, q^d = 1 - q^v - q^l - q^i and
+// c_pm with c_i q^i (acoustic_substepping.jl:390-410) — the host selects it by DevGrid::sa_mixed, MIX = false reads no ice member
+template <bool MIX>
 __global__ __launch_bounds__(256) void k_cmp_linearization(DevGrid g, double *__restrict__ Pi, double *__restrict__ thL,
                                                            double *__restrict__ gR, double *__restrict__ Clin,
                                                            const double *__restrict__ p, const double *__restrict__ rho_d,
@@ -177,9 +190,12 @@ __global__ __launch_bounds__(256) void k_cmp_linearization(DevGrid g, double *__
     const double rd = rho_d[n];
     const double q = (g.microphysics == 1) ? g.qv_field[n] : qv[n];
     const double ql = (g.microphysics == 2) ? g.qcl_field[n] + g.qr_field[n] : ((g.microphysics == 1) ? g.ql_field[n] : 0.0);
-    const double qd = 1.0 - q - ql;
+    double qi = 0.0;
+    if constexpr (MIX) qi = g.qi_field[n];
+    const double qd = MIX ? 1.0 - q - ql - qi : 1.0 - q - ql;
     const double Rm = qd * g.Rd + q * g.Rv;
-    const double cpm = g.microphysics ? qd * g.cpd + q * g.cpv + ql * g.sa_cl : qd * g.cpd + q * g.cpv;
+    const double cpm = MIX ? qd * g.cpd + q * g.cpv + ql * g.sa_cl + qi * g.sa_ci
+                           : g.microphysics ? qd * g.cpd + q * g.cpv + ql * g.sa_cl : qd * g.cpd + q * g.cpv;
     const double P = pow(p[n] / g.pst, g.Rd / g.cpd);
     const double gr = cpm * Rm / (cpm - Rm);
     st_store(Pi, nd, P, st32);
@@ -309,7 +325,7 @@ int bzi_compressible_update_state(bz_ctx *ctx, const bz_compressible_state *s, c
         if (g.bounded_y) hipLaunchKernelGGL((k_cmp_diagnose<true, false, 0, true>), grid, block, 0, ctx->stream, g, F, na, nm, bzi_flatau(ctx));
         else bz_bools([&](auto lin) {
             constexpr bool LIN = lin();
-            bz_static_int<4>(bzi_cmp_mp(ctx), [&](auto mp) { hipLaunchKernelGGL((k_cmp_diagnose<true, LIN, mp()>), grid, block, 0, ctx->stream, g, F, na, nm, bzi_flatau(ctx)); });
+            bz_static_int<6>(bzi_cmp_mp(ctx), [&](auto mp) { hipLaunchKernelGGL((k_cmp_diagnose<true, LIN, mp()>), grid, block, 0, ctx->stream, g, F, na, nm, bzi_flatau(ctx)); });
         }, with_linearization);
         BZ_LAUNCH_CHECK();
     }
@@ -375,8 +391,10 @@ extern "C" int bz_refresh_linearization(bz_ctx *ctx, const bz_compressible_state
     const int hrows = g.wrap_y ? 0 : g.bounded_y ? 1 : ((ctx->se.direct_divergence_damping && ctx->se.damping_coefficient >= 0.0) ? 2 : 1);
     const int hcols = g.bounded_x ? 1 : 0;
     dim3 grid((g.Nx + 2 * hcols + 255) / 256, g.Ny + 2 * hrows, g.Nz), block(256);
-    hipLaunchKernelGGL(k_cmp_linearization, grid, block, 0, ctx->stream, g, sub->exner, sub->potential_temperature,
-                       sub->gamma_R_mixture, ctx->d_Clin, s->p, s->rho_d, s->rho_theta, s->q, ctx->substep_f32 ? 1 : 0, hrows, hcols);
+    bz_bools([&](auto mix) {
+        hipLaunchKernelGGL(k_cmp_linearization<mix()>, grid, block, 0, ctx->stream, g, sub->exner, sub->potential_temperature,
+                           sub->gamma_R_mixture, ctx->d_Clin, s->p, s->rho_d, s->rho_theta, s->q, ctx->substep_f32 ? 1 : 0, hrows, hcols);
+    }, g.sa_mixed != 0);
     BZ_LAUNCH_CHECK();
     return BZ_OK;
 }

@@ -89,6 +89,11 @@ extern "C" int bz_set_compressible_surface_fluxes(bz_ctx *ctx, const bz_compress
         return BZ_ERR_UNSUPPORTED;
     }
     if (!f) { ctx->cmp_sf_on = false; return BZ_OK; }
+    if (ctx->dg.sa_mixed) {      // (the reverse order is refused by bz_set_compressible_mixed_phase_equilibrium)
+        ctx->last_error = "bz_set_compressible_surface_fluxes: the bulk surface fluxes form c_pm without q^i, and the context's saturation adjustment "
+                          "runs on MixedPhaseEquilibrium (bz_set_compressible_mixed_phase_equilibrium)";
+        return BZ_ERR_UNSUPPORTED;
+    }
     if (ctx->fl_on && f->vapor.enabled) {      // (the reverse order is refused by bz_set_saturation_vapor_pressure_polynomial)
         ctx->last_error = "bz_set_compressible_surface_fluxes: a bulk vapour flux evaluates the Clausius-Clapeyron q^v+ of the surface, and the context's "
                           "saturation adjustment runs on a FlatauPolynomial (bz_set_saturation_vapor_pressure_polynomial)";

@@ -160,8 +160,13 @@ static void bz_static_int(int v, Fn &&f)
     } else f(std::integral_constant<int, 0>());
 }
 
-// the MP instantiation of k_cmp_diagnose and k_ac_stage_end: g.microphysics, or 3 for a saturation adjustment on FlatauPolynomial constants
-static inline int bzi_cmp_mp(const bz_ctx *ctx) { return (ctx->dg.microphysics == 1 && ctx->fl_on) ? 3 : ctx->dg.microphysics; }
+// the MP instantiation of k_cmp_diagnose and k_ac_stage_end: g.microphysics, or for a saturation adjustment 3 on FlatauPolynomial constants,
+// 4 with MixedPhaseEquilibrium (bz_set_compressible_mixed_phase_equilibrium) and 5 with both
+static inline int bzi_cmp_mp(const bz_ctx *ctx)
+{
+    if (ctx->dg.microphysics != 1) return ctx->dg.microphysics;
+    return ctx->dg.sa_mixed ? (ctx->fl_on ? 5 : 4) : (ctx->fl_on ? 3 : 1);
+}
 
 // ---- one WS-RK3 stage of the acoustic loop in three pieces (the y-slab driver exchanges halos between them) ---------
 struct AcStage {

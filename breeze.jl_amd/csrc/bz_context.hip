@@ -204,6 +204,41 @@ extern "C" int bz_set_mixed_phase_equilibrium(bz_ctx *ctx, const bz_mixed_phase_
     return BZ_OK;
 }
 
+// The same equilibrium on a CompressibleDynamics context (adjust_thermodynamic_state(::LiquidIceDensityState, ::SaturationAdjustment),
+// src/Microphysics/saturation_adjustment.jl:241-293): k_cmp_diagnose, k_ac_stage_end and k_cmp_linearization take their mixed instantiation
+// (bzi_cmp_mp, DevGrid::sa_mixed), which diagnoses q^i into `q_ice` and carries it in R_m, c_pm, the pressure and the linearisation.
+// Single-device contexts that are periodic in x and y; params == NULL: back to the warm phase.
+extern "C" int bz_set_compressible_mixed_phase_equilibrium(bz_ctx *ctx, const bz_mixed_phase_equilibrium *params, double *q_ice)
+{
+    if (ctx) ++ctx->config_epoch;      // captured steps (bz_graph.hip) belong to one configuration
+    if (!ctx) return BZ_ERR_INVALID;
+    DevGrid &g = ctx->dg;
+    if (!params) { bzi_clear_mixed_phase(g); return BZ_OK; }
+    const char *why = ctx->kinematic       ? "the kinematic driver diagnoses q^v and q^l only"
+                      : !ctx->compressible ? "the context was not created by bz_create_compressible (anelastic contexts take bz_set_mixed_phase_equilibrium)"
+                      : (ctx->slab_mode || ctx->comm) ? "y-slab contexts exchange the halos of q^v and q^l only"
+                      : (g.bounded_x || g.bounded_y)  ? "not implemented on a Bounded x or y"
+                      : g.microphysics == 2           ? "DCMIP2016KesslerMicrophysics is attached"
+                      : ctx->has_instant_precip       ? "InstantaneousPrecipitation is attached: its update runs the warm-phase adjustment"
+                      : ctx->cmp_sf_on                ? "bulk surface fluxes are attached: they form c_pm without q^i"
+                      : g.microphysics != 1           ? "no SaturationAdjustment is attached (call bz_set_saturation_adjustment first)"
+                                                      : nullptr;
+    if (why) {
+        ctx->last_error = std::string("bz_set_compressible_mixed_phase_equilibrium: ") + why;
+        return BZ_ERR_UNSUPPORTED;
+    }
+    if (!q_ice || !(params->freezing_temperature > params->homogeneous_ice_nucleation_temperature)) return BZ_ERR_INVALID;
+    g.sa_mixed = 1;
+    g.sa_Tf = params->freezing_temperature;
+    g.sa_Th = params->homogeneous_ice_nucleation_temperature;
+    g.sa_Li = params->ice_latent_heat;
+    g.sa_ci = params->ice_heat_capacity;
+    g.sa_dci = ctx->constants.vapor_heat_capacity - params->ice_heat_capacity;
+    g.sa_L0i = params->ice_latent_heat - g.sa_dci * ctx->sa_energy_reference_temperature;
+    g.qi_field = q_ice;
+    return BZ_OK;
+}
+
 // saturation_vapor_pressure = FlatauPolynomial(...) of the ThermodynamicConstants (src/Thermodynamics/flatau_polynomial.jl): the kernels that
 // evaluate p^v+ inside a saturation adjustment take their polynomial instantiation (bz_ctx::fl_on, bzi_flatau).  params == NULL: Clausius-Clapeyron.
 extern "C" int bz_set_saturation_vapor_pressure_polynomial(bz_ctx *ctx, const bz_flatau_polynomial *params)

@@ -62,8 +62,8 @@ struct DevGrid {
     int bounded_y;         // 1: topology (Periodic, Bounded, Bounded): walls in y (wrap_y = 0: y neighbours are halo rows — a no-flux row for
                            // fields that are centres in y, impenetrable wall faces j = 0, Ny for rho v and v; WENO / Centered buffers by row;
                            // cosine transform along y in the pressure solve; per-operator kernels only)
-    // SaturationAdjustment(equilibrium = MixedPhaseEquilibrium(T^f, T^h)) (bz_set_mixed_phase_equilibrium; microphysics stays 1): all zero /
-    // null on warm-phase contexts.  The hosts select the mixed INSTANTIATION of a kernel by sa_mixed; no warm kernel reads these members.
+    // SaturationAdjustment(equilibrium = MixedPhaseEquilibrium(T^f, T^h)) (bz_set_mixed_phase_equilibrium, on compressible contexts
+    // bz_set_compressible_mixed_phase_equilibrium; microphysics stays 1): all zero / null on warm-phase contexts.  The hosts select the mixed INSTANTIATION of a kernel by sa_mixed; no warm kernel reads these members.
     int sa_mixed;
     double sa_Tf, sa_Th, sa_Li, sa_ci, sa_dci, sa_L0i;               // dci = cpv - ci, L0i = Li - dci * T_energy
     double *qi_field;                                                // model.microphysical_fields.q^i (parent)
@@ -482,6 +482,82 @@ __device__ __forceinline__ double bz_ds_adjust(const DevGrid &g, double th, doub
     }
     bz_ds_residual<FL>(g, x2, th, rho, qt, qv, ql, fl);
     return bz_ds_temperature(g, th, qv, ql, rho, nabstol, nmaxiter);
+}
+// ---- the density-based state with equilibrium = MixedPhaseEquilibrium(T^f, T^h) (bz_set_compressible_mixed_phase_equilibrium) --------
+// The three functions above with the ice phase, called by the mixed instantiations (MP = 4 | 5) of k_cmp_diagnose and k_ac_stage_end alone.
+// temperature(::LiquidIceDensityState) (dynamic_states.jl:197-232): L = (L_l q^l + L_i q^i) / c_pm, c_pm with c_i q^i
+__device__ __forceinline__ double bz_ds_temperature_mixed(const DevGrid &g, double th, double qv, double ql, double qi, double rho,
+                                                          double abstol, int maxiter)
+{
+    const double qd = 1.0 - (qv + ql + qi);
+    const double Rm = qd * g.Rd + qv * g.Rv;
+    const double cpm = qd * g.cpd + qv * g.cpv + ql * g.sa_cl + qi * g.sa_ci;
+    const double kap = Rm / cpm, gam = cpm / (cpm - Rm);
+    const double L = (g.sa_Ll * ql + g.sa_Li * qi) / cpm;
+    double T = pow(th, gam) * pow(rho * Rm / g.pst, gam - 1.0) + L;
+    double dT = T;
+    for (int it = 0; it < maxiter && fabs(dT) > abstol; ++it) {
+        const double Phi = pow(rho * Rm * T / g.pst, kap) * th;
+        dT = -(T - Phi - L) / (1.0 - kap * Phi / T);
+        T += dT;
+    }
+    return T;
+}
+// p^v+ over the surface equilibrated at T (vapor_saturation.jl:170-185): bz_mp_psat, with the polynomial's two chains one after the other.
+// The same FMAs in the same order per chain as bz_fl_psat_mixed, so the same bits; the table pointer is made opaque again between them, so
+// the nine coefficients of one chain are loaded when that chain runs: the compressible kernels are at their scalar budget (DESIGN section 6,
+// resource table), and the interleaved form, which holds eighteen coefficients at once, sent k_cmp_diagnose<true, true, 5> to scratch.
+template <bool FL = false>
+__device__ __forceinline__ double bz_ds_psat_mixed(const DevGrid &g, double T, double lam, ColPtr fl = ColPtr())
+{
+    if constexpr (FL) return lam * bz_fl_psat_liquid(fl, T) + (1.0 - lam) * bz_fl_psat_ice(fl, T);
+    return bz_mp_psat<false>(g, T, lam);
+}
+// saturated_density_residual with MixedPhaseEquilibrium (saturation_adjustment.jl:241-253): q^v+ = p^v+ / (rho R^v T) over the surface
+// equilibrated at T, the partition of equilibrated_moisture_mass_fractions (saturation_adjustment.jl:92-100)
+template <bool FL = false>
+__device__ __forceinline__ double bz_ds_residual_mixed(const DevGrid &g, double T, double th0, double rho, double qt, double &qv, double &ql,
+                                                       double &qi, ColPtr fl = ColPtr())
+{
+    const double lam = bz_mp_lambda(g, T);
+    const double qs = bz_ds_psat_mixed<FL>(g, T, lam, fl) / (rho * g.Rv * T);
+    const double qc = fmax(0.0, qt - qs);
+    qv = qt - qc;
+    ql = lam * qc;
+    qi = (1.0 - lam) * qc;
+    const double qd = 1.0 - (qv + ql + qi);
+    const double Rm = qd * g.Rd + qv * g.Rv;
+    const double cpm = qd * g.cpd + qv * g.cpv + ql * g.sa_cl + qi * g.sa_ci;
+    const double L = (g.sa_Ll * ql + g.sa_Li * qi) / cpm;
+    const double p = rho * Rm * T;
+    return (T - L) * pow(g.pst / p, Rm / cpm) - th0;
+}
+// adjust_thermodynamic_state(::LiquidIceDensityState, ::SaturationAdjustment{MixedPhaseEquilibrium}) (saturation_adjustment.jl:264-293)
+// -> T; sets qv, ql, qi.  The exits of bz_ds_adjust: theta = 0, the clear parcel, the non-finite slope, maxiter and abstol = 0.
+template <bool FL = false>
+__device__ __forceinline__ double bz_ds_adjust_mixed(const DevGrid &g, double th, double qt, double rho, double nabstol, int nmaxiter,
+                                                     double &qv, double &ql, double &qi, ColPtr fl = ColPtr())
+{
+    qv = qt; ql = 0.0; qi = 0.0;
+    if (th == 0.0) return 0.0;
+    const double T1 = bz_ds_temperature_mixed(g, th, qt, 0.0, 0.0, rho, nabstol, nmaxiter);
+    if (qt <= bz_ds_psat_mixed<FL>(g, T1, bz_mp_lambda(g, T1), fl) / (rho * g.Rv * T1)) return T1;
+    double qv1, ql1, qi1;
+    bz_ds_residual_mixed<FL>(g, T1, th, rho, qt, qv1, ql1, qi1, fl);
+    const double dT = (g.sa_Ll * ql1 + g.sa_Li * qi1) / bz_mp_cpm(g, qv1, ql1, qi1);
+    double x1 = T1, x2 = T1 + fmax(0.01, dT / 2.0);
+    double a, b, c;
+    double r1 = bz_ds_residual_mixed<FL>(g, x1, th, rho, qt, a, b, c, fl), r2 = bz_ds_residual_mixed<FL>(g, x2, th, rho, qt, a, b, c, fl);
+    for (int it = 0; it < g.sa_maxiter && fabs(r2) > g.sa_abstol; ++it) {
+        double s = (x2 - x1) / (r2 - r1);
+        const bool valid = isfinite(s);
+        s = valid ? s : 0.0;
+        x1 = x2; r1 = r2;
+        x2 -= r2 * s;
+        r2 = valid ? bz_ds_residual_mixed<FL>(g, x2, th, rho, qt, a, b, c, fl) : 0.0;
+    }
+    bz_ds_residual_mixed<FL>(g, x2, th, rho, qt, qv, ql, qi, fl);
+    return bz_ds_temperature_mixed(g, th, qv, ql, qi, rho, nabstol, nmaxiter);
 }
 #endif
 

@@ -30,7 +30,13 @@ class SecantSolver:
 
 class SaturationAdjustment:
     """SaturationAdjustment(; solver = SecantSolver(abstol=1e-4, maxiter=20), equilibrium = MixedPhaseEquilibrium())
-    (saturation_adjustment.jl:55-70).  The mixed-phase equilibrium runs on the anelastic AtmosphereModel; every other model refuses it by name."""
+    (saturation_adjustment.jl:55-70).  The mixed-phase equilibrium runs on the single-device anelastic AtmosphereModel (pressure form: qᵛ⁺ at
+    the reference pressure) and on the single-device CompressibleAtmosphereModel that is periodic in x and y or Flat in y (density form,
+    saturation_adjustment.jl:241-293: qᵛ⁺ = pᵛ⁺ / (ρ Rᵛ T) at the cell's own density, inside update_state! and the fused stage epilogue); both
+    diagnose microphysical_fields["qⁱ"] beside qᵛ and qˡ.  The anelastic model takes the equilibrium in its constructor; the compressible
+    constructor attaches the warm-phase adjustment and refuses the mixed one by name, and compressible.set_mixed_phase_equilibrium_(model,
+    MixedPhaseEquilibrium(...)) attaches the mixed form to the built model.  Slab, walled and kinematic models, bulk surface fluxes, TetensFormula constants,
+    set!(T | ℋ), the diagnostics operations and the hydrostatic balances refuse it by name."""
 
     def __init__(self, solver=None, equilibrium=None):
         if equilibrium is None:
@@ -53,8 +59,8 @@ class InstantaneousPrecipitation:
 
     def __init__(self, equilibrium=None, solver=None):
         if isinstance(equilibrium, MixedPhaseEquilibrium):
-            raise NotImplementedError("InstantaneousPrecipitation(equilibrium = MixedPhaseEquilibrium()): the density-based mixed-phase adjustment "
-                                      "of CompressibleDynamics is not implemented; WarmPhaseEquilibrium() is")
+            raise NotImplementedError("InstantaneousPrecipitation(equilibrium = MixedPhaseEquilibrium()): the rain-out kernel runs the warm-phase "
+                                      "density-based adjustment (it has no ice to precipitate); WarmPhaseEquilibrium() is implemented")
         self.saturation_adjustment = SaturationAdjustment(solver=solver, equilibrium=WarmPhaseEquilibrium() if equilibrium is None else equilibrium)
 
 

@@ -145,6 +145,17 @@ typedef struct bz_mixed_phase_equilibrium {
     double ice_latent_heat, ice_heat_capacity;
 } bz_mixed_phase_equilibrium;
 int bz_set_mixed_phase_equilibrium(bz_ctx *ctx, const bz_mixed_phase_equilibrium *params, double *q_ice);
+/* The same equilibrium on a CompressibleDynamics context, called AFTER bz_set_saturation_adjustment: the density-based adjustment
+ * (src/Microphysics/saturation_adjustment.jl:241-293) saturates at the cell's own total density over the surface equilibrated at the
+ * temperature of each evaluation, q^v+ = p^v+ / (rho R^v T), splits the condensate by lambda(T), and the residual, the Newton temperature
+ * (src/Thermodynamics/dynamic_states.jl:197-232), the pressure p = rho R_m T and the acoustic linearisation
+ * (src/CompressibleEquations/acoustic_substepping.jl:390-410) carry both latent heats and c_i q^i.  q^i is diagnosed into `q_ice` (device
+ * parent array) by update_state! and by the fused stage epilogue.  params == NULL returns the context to the warm phase: its steps are then
+ * those of a context that never had the equilibrium attached.  Single-device compressible contexts that are periodic in x and y:
+ * BZ_ERR_UNSUPPORTED, bz_last_error naming the function and the reason, on anelastic, kinematic, y-slab and walled contexts, with
+ * DCMIP2016KesslerMicrophysics or InstantaneousPrecipitation attached, with bulk surface fluxes attached (they form c_pm without q^i; in the
+ * other order bz_set_compressible_surface_fluxes refuses) and without an attached SaturationAdjustment.  Every call invalidates recorded steps. */
+int bz_set_compressible_mixed_phase_equilibrium(bz_ctx *ctx, const bz_mixed_phase_equilibrium *params, double *q_ice);
 /* ThermodynamicConstants(saturation_vapor_pressure = FlatauPolynomial(...)) (src/Thermodynamics/flatau_polynomial.jl): the eighth-order
  * polynomial fits of Flatau et al. (1992), p^v+ = sum_n a_n x^n, n = 0..8, x = max(T - reference_temperature, -minimum_temperature_offset),
  * over liquid and over ice, coefficients in Pa, a_0 first; on the mixed-phase surface lambda p^v+l + (1 - lambda) p^v+i.  While attached,
